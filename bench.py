@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mray/s of the path-tracing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch: rendering the whole image of the workload
@@ -15,6 +15,16 @@ the whole scene, no data-path collective) and the only exchange is the final ima
 
 value = rays (the reference's own `raysTraced` definition: primary samples + occlusion rays + scatter rays,
 path_tracer.cpp:62,219,242,276) of the whole job / wall time of the K steps, max over ranks.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  Everything else the benchmark measures or checks
+runs only with --full, after the timed steps: the roofline block (an untimed counting launch + the committed counter summary),
+the CPU baseline (the compiled reference or the oracle port, with its bit-for-bit image check at depth cap 14) and, with N > 1,
+the check of the gathered image against the one-GPU image.
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0 holds it: DIR/image.npy, the (H, W, 3) float32 image
+(for an image over DUMP_IMAGE_BYTES, a fixed seeded sample of its pixels instead: image_sample.npy, (n, 3) float32, and
+image_sample_pixels.npy, their row-major pixel indices as float64), and DIR/rays_per_step.npy, float64 [rays, occlusion rays]
+of one step.  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -48,6 +58,22 @@ WORKLOADS = {
                            "3840x2160, 1024 spp, depth 12"),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s peak
+DUMP_IMAGE_BYTES = 48 << 20  # --dump-outputs: a larger image is sampled (C3: 24.9 MB whole; C5: 99.5 MB -> 2 M pixels + their indices)
+DUMP_SAMPLE_PIXELS = 2_000_000
+
+
+def dump_outputs(out_dir, image, rays_per_step, occl_per_step):
+    """What the timed path returned in its last step, as .npy files under out_dir (at most ~40 MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes <= DUMP_IMAGE_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+    else:
+        px = img.reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(0).choice(len(px), DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "image_sample.npy"), px[idx])
+        np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "rays_per_step.npy"), np.array([rays_per_step, occl_per_step], dtype=np.float64))
 
 
 def algorithmic_bytes(st):
@@ -229,9 +255,14 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--max-depth", type=int, default=0)
     ap.add_argument("--seed", type=int, default=12345)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=120.0, help="budget of the CPU leg: the whole frame when a probe says it fits, else a window")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the roofline block, the CPU baseline and (N > 1) the gathered-image check")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  A CHILD process (never an exec: this pool
@@ -338,10 +369,13 @@ def main():
     dt = float(t_all.item())
     rays_per_step, occl_per_step = float(rays[0].item()), float(rays[1].item())
     kernel_ms = st["kernelMsSum"] / max(1, st["kernelLaunches"])
+    if rank == 0 and args.dump_outputs:
+        # before anything else renders into fb: it holds the last timed step's image (rank 0's: the gathered one when N > 1)
+        dump_outputs(args.dump_outputs, fb.cpu().numpy(), rays_per_step, occl_per_step)
 
     out = None
     gather_check = None
-    if rank == 0 and world > 1:
+    if args.full and rank == 0 and world > 1:
         # untimed: the image the ranks' tiles were gathered into must equal what one GPU renders alone, bit for bit
         gathered = fb.clone()
         alone = torch.zeros_like(fb)
@@ -353,6 +387,19 @@ def main():
             f"MISMATCH: {int((gathered.view(torch.int32) != alone.view(torch.int32)).any(dim=2).sum().item())} pixels of the gathered image differ from the one-GPU image"
         del gathered, alone
     if rank == 0:
+        value = rays_per_step * args.steps / dt / 1e6
+        name, cus = tracer.device_info()
+        out = {
+            "metric": "Mray/s (primary+secondary) at 1080p/64spp; 1/2/4/8-GPU scaling",
+            "value": value, "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": args.workload, "description": describe, "width": W, "height": H, "spp": spp, "max_depth": depth,
+                       "seed": args.seed, "rays_per_step": int(rays_per_step), "occlusion_rays_per_step": int(occl_per_step),
+                       "sharding": f"16x16 tiles round-robin over {world} rank(s), scene replicated, RCCL send/recv image gather of {tracer.gather_payload_bytes()} B per rank" if world > 1
+                       else "one GPU", "device": name, "compute_units": cus, **({"gather_check": gather_check} if gather_check else {})},
+        }
+    if args.full and rank == 0:
         # algorithmic bytes of THIS rank's launch from an untimed counting launch (deterministic event counts)
         tracer.render_async(0, 0, W - 1, H - 1, spp, d_rgb=fb.data_ptr(), stream=stream, exposure=exposure, rank=rank, nranks=world,
                             count_traffic=True)
@@ -363,22 +410,12 @@ def main():
         ev = counter_evidence(args.workload, world, bool(args.spp or args.width or args.height or args.max_depth))
         traffic_bytes = ev["traffic_bytes_per_frame"] if ev else None
         traffic_rate = traffic_bytes / (kernel_ms * 1e-3) / 1e9 if ev else None
-        value = rays_per_step * args.steps / dt / 1e6
-        name, cus = tracer.device_info()
         # bytes of the tree the traversals gather from (64-byte records of the internal nodes -- (nodes - 1) / 2 of a binary tree -- and
         # 36-byte triangle slots, ~1.12 slots per triangle with the padded leaf blocks): which of the measured gather ceilings applies
         sd = scene.describe().contents
         tree_bytes = sum((sd.meshes[i].nodeCount - 1) // 2 * 64 + sd.meshes[i].primCount * 36 * 1.12 for i in range(sd.meshCount))
         bind, roofs = binding_roof(ev, kernel_ms, tree_bytes) if ev else (None, None)
-        out = {
-            "metric": "Mray/s (primary+secondary) at 1080p/64spp; 1/2/4/8-GPU scaling",
-            "value": value, "unit": "Mray/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": args.workload, "description": describe, "width": W, "height": H, "spp": spp, "max_depth": depth,
-                       "seed": args.seed, "rays_per_step": int(rays_per_step), "occlusion_rays_per_step": int(occl_per_step),
-                       "sharding": f"16x16 tiles round-robin over {world} rank(s), scene replicated, RCCL send/recv image gather of {tracer.gather_payload_bytes()} B per rank" if world > 1
-                       else "one GPU", "device": name, "compute_units": cus, **({"gather_check": gather_check} if gather_check else {})},
+        out.update({
             # `achieved` / `frac` are the contract's ALGORITHMIC figure (layout-independent bytes of the events the
             # reference's algorithm performs, most of them served by L1/L2) -- not a claim that DRAM is busy.  What DRAM and the
             # memory pipeline really do is beside it: `traffic` / `hbm_frac` (fabric-side counters) and `limiter` (from the same file).
@@ -411,7 +448,7 @@ def main():
                          "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": int(B),
                          "events_per_launch": {k: ct[k] for k in ("nBox", "nTri", "nHit", "nTap", "nPx")},
                          "algorithmic_bytes_by_role": algorithmic_split(ct)},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             def gpu_render_cap14(rect):
                 tracer.max_depth = 14
@@ -424,6 +461,7 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(scene, camera, exposure, spp, depth, args.seed, args.cpu_seconds, gpu_render_cap14)
             except Exception as e:  # the baseline is a report, never the product
                 out["cpu_baseline"] = {"value": None, "unit": "Mray/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {type(e).__name__}: {e}"}
+    if rank == 0:
         print(json.dumps(out), file=real_stdout, flush=True)
     if use_dist:
         dist.barrier()

@@ -158,10 +158,11 @@ def test_camera_basis_matches_oracle_for_oblique_views(L):
         assert cam.desc.invWidth == oc.invWidth and cam.desc.invHeight == oc.invHeight
 
 
-def test_obj_reader_matches_teapot_fixture(L):
-    path = "/root/reference/data/teapot/teapot.obj"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this box")
+def test_obj_reader_matches_teapot_fixture(L, tmp_path):
+    import gzip
+    path = str(tmp_path / "teapot.obj")  # the reference's data/teapot/teapot.obj, byte for byte (stored gzip-compressed)
+    with gzip.open(os.path.join(T.GOLDEN, "teapot.obj.gz"), "rb") as f:
+        open(path, "wb").write(f.read())
     scene = prt_amd.Scene()
     m = prt_amd.Mesh.load_obj(path, prt_amd.Material.make(diffuse=(0.9, 0.9, 0.9), reflection=1))
     scene.add(m)
@@ -928,28 +929,24 @@ def test_exr_and_ppm_writers(L, tmp_path):
 
 
 @pytest.mark.ref
-def test_reference_main_cpp_compiles_and_links_unmodified(L, tmp_path):
-    """The drop-in claim of SURVEY.md 8b, checked on the reference's own caller: /root/reference/src/main.cpp, byte for
-    byte, is compiled against include/prt_compat/ (one forwarding header per reference header it includes, each pulling in
+def test_reference_main_cpp_compiles_and_links_unmodified(L):
+    """The drop-in claim of SURVEY.md 8b, checked on the reference's own caller: its src/main.cpp, byte for byte, is compiled
+    against include/prt_compat/ (one forwarding header per reference header it includes, each pulling in
     prt_amd/csrc/host/prt.h) and linked against libprt_hip.so -- with and without PRT_ENABLE_STATS (main.cpp:148-152,
-    176-178).  The file is reached through a symbolic link so that its `#include "scene.h"` resolves to the compat
-    directory, not to the reference's headers beside it.  (Running it needs an MI355X and the reference's teapot asset:
-    examples/main.cpp is the stand-in that the GPU tests run.)"""
-    src = "/root/reference/src/main.cpp"
-    if not os.path.exists(src):
-        pytest.skip("the reference tree is not on this machine")
-    link = tmp_path / "main.cpp"
-    os.symlink(src, link)
-    libdir = os.path.dirname(prt_amd.LIB_PATH)
-    for extra in ([], ["-DPRT_ENABLE_STATS=1"]):
-        exe = tmp_path / ("prt_ref_main" + ("_stats" if extra else ""))
-        cmd = ["g++", "-std=c++17", "-O2", "-Wall", *extra, "-I", os.path.join(T.ROOT, "include", "prt_compat"), str(link), "-o", str(exe),
-               "-L", libdir, "-lprt_hip", f"-Wl,-rpath,{libdir}", "-lpthread"]
-        out = subprocess.run(cmd, capture_output=True, text=True)
-        assert out.returncode == 0, out.stderr
-        assert "/root/reference/src/" not in subprocess.check_output(["g++", "-std=c++17", *extra, "-I", os.path.join(T.ROOT, "include", "prt_compat"),
-                                                                      "-M", str(link)]).decode().replace(src, "")
-        syms = subprocess.check_output(["nm", "-u", "-C", str(exe)]).decode()
+    176-178).  oracle/Makefile does it where the reference's tree is present (oracle/_ref/prt_ref_main{,_stats}, reached
+    through a link so that its `#include "scene.h"` resolves to the compat directory, not to the reference's headers beside it);
+    here, every header it depended on must be the project's and the library must provide what it calls.  (Running it needs
+    an MI355X and the reference's teapot asset: examples/main.cpp is the stand-in that the GPU tests run.)"""
+    for name in ("prt_ref_main", "prt_ref_main_stats"):
+        exe = os.path.join(T.REF_DIR, name)
+        if not os.path.exists(exe):
+            pytest.skip(f"oracle/_ref/{name} is only built where the reference's tree is present")
+        deps = open(exe + ".d").read().replace("\\\n", " ").split(":", 1)[1].split()
+        assert deps[0] == "_ref/main.cpp"
+        for d in deps[1:]:  # (-MMD: system headers are not listed)
+            assert os.path.realpath(os.path.join(T.ORACLE_DIR, d)).startswith(T.ROOT + os.sep), f"{name} compiled against {d}"
+        assert any(d.endswith("prt_compat/scene.h") for d in deps) and any(d.endswith("host/prt.h") for d in deps)
+        syms = subprocess.check_output(["nm", "-u", "-C", exe]).decode()
         for needed in ("prt::PathTracer::TraceBlock", "prt::Bvh::build", "prt::Scene::add", "prt::Image::saveExr", "prt::ThreadPool::queue"):
             assert needed in syms, needed
 
