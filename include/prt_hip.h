@@ -209,6 +209,40 @@ int prt_hip_gather_payload_bytes(prt_hip_ctx* ctx, uint64_t* bytes);
 int prt_hip_gather(prt_hip_ctx* const* ctxs, int n, float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 int prt_hip_get_stats(prt_hip_ctx* ctx, prt_hip_stats* stats);
 
+/* ---- progressive rendering: resumable per-pixel sample accumulation.  The context keeps an ACCUMULATOR, one record per camera
+ * pixel: the generator state after the pixel's last packet, the float RGB sum of its packets and its sample count.  Across
+ * packets the reference carries exactly these two things per pixel (m_rand and color, path_tracer.cpp:57-75), so a pass that
+ * resumes from them continues the pixel's one-shot render: after passes of s1, s2, ..., sk samples the image is, bit for bit,
+ * the image of ONE prt_hip_render of s1 + ... + sk samples.  The total may exceed prt_hip_render's 2040-sample limit. ---- */
+typedef struct {
+    uint32_t width, height;           /* the camera's size */
+    uint32_t seed, maxDepth, rrDepth; /* the estimator the accumulated samples came from (0 when the accumulator is empty) */
+} prt_accum_info;
+/* Empties the accumulator (every count 0) and unbinds the estimator.  prt_hip_set_camera and prt_hip_upload_scene do the same. */
+int prt_hip_accum_reset(prt_hip_ctx* ctx);
+/* One pass: every pixel of the rectangle (or of rank's tiles in it) renders params->samples more samples, starting from its
+ * record (a pixel with count 0 is seeded as prt_hip_render seeds it), stores its state, sum and count back and writes
+ * exposure * sum / count to d_rgb.  Rectangle, rank / tile, framebuffer and stream rules are those of prt_hip_render, and
+ * prt_hip_gather_rccl / prt_hip_gather work on the output unchanged; prt_hip_get_stats counts this pass's rays only.
+ * params->samples: a multiple of 8 from 8 to 2040.  A pass that could take any pixel's count above 2^24 (where a count as a float
+ * stops being exact) is refused.  The first pass after a reset binds seed, maxDepth and rrDepth; a pass with other values is
+ * refused (mixing two estimators would be a silent error).  exposure may change from pass to pass.  All refusals are
+ * PRT_HIP_EINVAL with a message.  The accumulator is allocated at the camera's size on first use; prt_hip_render neither
+ * reads nor changes it. */
+int prt_hip_render_accumulate(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                              const prt_render_params* params, float* d_rgb, void* stream);
+/* Writes exposure * sum / count of the rectangle's records to d_rgb (+0.0 where count is 0) without tracing: the image of the
+ * accumulated passes at another exposure.  Framebuffer and stream rules of prt_hip_render. */
+int prt_hip_accum_resolve(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float exposure,
+                          float* d_rgb, void* stream);
+/* Checkpoint / resume.  export copies the whole accumulator to host arrays (waits for the context's stream): rng width*height
+ * states, sum 3*width*height floats, count width*height; info gets the size and the bound estimator.  import loads such arrays
+ * into a context whose camera has info's size (else PRT_HIP_EINVAL) and binds info's estimator; counts above 2^24 are refused.
+ * A context that imports a checkpoint after uploading the same scene and camera continues it as if it had never stopped. */
+int prt_hip_accum_export(prt_hip_ctx* ctx, prt_accum_info* info, uint32_t* rng, float* sum, uint32_t* count);
+int prt_hip_accum_import(prt_hip_ctx* ctx, const prt_accum_info* info, const uint32_t* rng, const float* sum,
+                         const uint32_t* count);
+
 #ifdef __cplusplus
 }
 #endif

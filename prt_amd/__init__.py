@@ -90,6 +90,10 @@ class HipStats(C.Structure):
         return out
 
 
+class AccumInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("seed", C.c_uint32), ("maxDepth", C.c_uint32), ("rrDepth", C.c_uint32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -106,7 +110,8 @@ EXPORTS = [
     "prt_hip_device_count", "prt_hip_create", "prt_hip_destroy", "prt_hip_last_error", "prt_hip_source_sha16", "prt_hip_device_info",
     "prt_hip_upload_scene", "prt_hip_set_camera", "prt_hip_render", "prt_hip_render_gbuffer", "prt_hip_download", "prt_hip_framebuffer", "prt_hip_gather",
     "prt_hip_build_bvh", "prt_hip_comm_unique_id", "prt_hip_comm_init", "prt_hip_comm_adopt", "prt_hip_comm_destroy", "prt_hip_gather_rccl", "prt_hip_gather_payload_bytes",
-    "prt_hip_get_stats",
+    "prt_hip_get_stats", "prt_hip_accum_reset", "prt_hip_render_accumulate", "prt_hip_accum_resolve", "prt_hip_accum_export",
+    "prt_hip_accum_import",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
@@ -183,6 +188,11 @@ def _load(path, with_test_entry_points):
     L.prt_hip_framebuffer.restype = vp
     L.prt_hip_framebuffer.argtypes = [vp]
     L.prt_hip_get_stats.argtypes = [vp, C.POINTER(HipStats)]
+    L.prt_hip_accum_reset.argtypes = [vp]
+    L.prt_hip_render_accumulate.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RenderParams), vp, vp]
+    L.prt_hip_accum_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]
+    L.prt_hip_accum_export.argtypes = [vp, C.POINTER(AccumInfo), vp, vp, vp]
+    L.prt_hip_accum_import.argtypes = [vp, C.POINTER(AccumInfo), vp, vp, vp]
     if with_test_entry_points:
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
@@ -471,6 +481,91 @@ class PathTracer:
     def render(self, samples, **kw):
         W, H = self._camera.width, self._camera.height
         return self.trace_block(0, 0, W - 1, H - 1, samples, **kw)
+
+    # ---- progressive rendering (include/prt_hip.h "progressive rendering"): passes resume every pixel from the context's accumulator,
+    # and after passes of s1, ..., sk samples the image is bit for bit render(s1 + ... + sk)
+    def _rect(self, x0, y0, x1, y1):
+        W, H = self._camera.width, self._camera.height
+        return x0, y0, W - 1 if x1 is None else x1, H - 1 if y1 is None else y1
+
+    def accumulate_async(self, samples, x0=0, y0=0, x1=None, y1=None, d_rgb=None, stream=None, **kw):
+        """One accumulate pass of `samples` (a multiple of 8, 8..2040) over the inclusive rectangle, queued on the GPU."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        p = self.params(samples, **kw)
+        self._chk(self._L.prt_hip_render_accumulate(self._ctx, x0, y0, x1, y1, C.byref(p), d_rgb, stream), "prt_hip_render_accumulate")
+
+    def accumulate(self, samples, x0=0, y0=0, x1=None, y1=None, exposure=1.0, rank=0, nranks=1, tile=16, count_traffic=False,
+                   max_depth=None):
+        """One accumulate pass; returns the rectangle's image -- the mean over every sample its pixels have -- as (h, w, 3) float32
+        and sets last_stats (the rays of this pass)."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        self.accumulate_async(samples, x0, y0, x1, y1, exposure=exposure, rank=rank, nranks=nranks, tile=tile, count_traffic=count_traffic,
+                              max_depth=max_depth)
+        return self._download_rect(x0, y0, x1, y1, stats=True)
+
+    def _download_rect(self, x0, y0, x1, y1, stats):
+        W, H = self._camera.width, self._camera.height
+        img = np.zeros((H, W, 3), dtype=np.float32)
+        self._download(img, x0, y0, x1, y1)
+        if stats:
+            self.last_stats = self.stats()  # raises on stack overflow
+        return img[y0:y1 + 1, x0:x1 + 1].copy()
+
+    def accum_reset(self):
+        """Empty the accumulator (set_camera and upload_scene do too)."""
+        self._chk(self._L.prt_hip_accum_reset(self._ctx), "prt_hip_accum_reset")
+
+    def accum_resolve(self, exposure=1.0, x0=0, y0=0, x1=None, y1=None):
+        """exposure * sum / count of the accumulator (0 where nothing was rendered) without tracing; returns the rectangle."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        self._chk(self._L.prt_hip_accum_resolve(self._ctx, x0, y0, x1, y1, exposure, None, None), "prt_hip_accum_resolve")
+        return self._download_rect(x0, y0, x1, y1, stats=False)
+
+    def accum_export(self):
+        """Checkpoint: dict(width, height, seed, max_depth, rr_depth, rng (H, W) u32, sum (H, W, 3) f32, count (H, W) u32)."""
+        W, H = self._camera.width, self._camera.height
+        info = AccumInfo()
+        rng = np.zeros((H, W), dtype=np.uint32)
+        total = np.zeros((H, W, 3), dtype=np.float32)
+        count = np.zeros((H, W), dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self._L.prt_hip_accum_export(self._ctx, C.byref(info), ptr(rng), ptr(total), ptr(count)), "prt_hip_accum_export")
+        return dict(width=info.width, height=info.height, seed=info.seed, max_depth=info.maxDepth, rr_depth=info.rrDepth,
+                    rng=rng, sum=total, count=count)
+
+    def accum_import(self, state):
+        """Resume: load a dict made by accum_export into this context (same camera size; upload the same scene and camera first)."""
+        info = AccumInfo(int(state["width"]), int(state["height"]), int(state["seed"]), int(state["max_depth"]), int(state["rr_depth"]))
+        n = info.width * info.height
+        rng = np.ascontiguousarray(state["rng"], dtype=np.uint32).reshape(-1)
+        total = np.ascontiguousarray(state["sum"], dtype=np.float32).reshape(-1)
+        count = np.ascontiguousarray(state["count"], dtype=np.uint32).reshape(-1)
+        if len(rng) != n or len(total) != 3 * n or len(count) != n:
+            raise PrtError(f"accum_import: arrays do not match the {info.width}x{info.height} accumulator they claim to be")
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self._L.prt_hip_accum_import(self._ctx, C.byref(info), ptr(rng), ptr(total), ptr(count)), "prt_hip_accum_import")
+
+    def accum_counts(self):
+        """(H, W) uint32: samples each pixel has in the accumulator."""
+        return self.accum_export()["count"]
+
+    def render_progressive(self, total, step=8, budget_ms=None, callback=None, exposure=1.0, **kw):
+        """The viewer's loop: accumulate passes of `step` samples over the whole image, calling callback(image, samples_so_far) after
+        each, until `total` samples or `budget_ms` of kernel time.  Starts from an empty accumulator; returns (image, samples_reached)."""
+        if total < step or total % 8 or step % 8:
+            raise PrtError("render_progressive: total and step must be multiples of 8 with total >= step")
+        self.accum_reset()
+        done, spent, img = 0, 0.0, None
+        while done < total:
+            n = min(step, total - done)
+            img = self.accumulate(n, exposure=exposure, **kw)
+            done += n
+            spent += self.last_stats["kernelMsSum"]
+            if callback is not None:
+                callback(img, done)
+            if budget_ms is not None and spent >= budget_ms:  # checked after each pass: the first one always runs
+                break
+        return img, done
 
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""

@@ -124,6 +124,16 @@ struct FrameArgs {
     uint32_t spillStride;
 };
 
+// Progressive rendering (prt_hip_render_accumulate): the arguments of frame_kernel_acc are a FrameArgs followed by the
+// context's accumulator, so every FrameArgs field keeps its kernarg offset and frame_kernel's argument block does not change.
+// Across packets the reference carries only the generator state and the colour sum of a pixel (path_tracer.cpp:57-75): a pass
+// that resumes from them continues the one-shot render of the pixel's total sample count bit for bit.
+struct FrameAccArgs {
+    FrameArgs f;
+    uint32_t* accRng; // per camera pixel (x + y * width): generator state after the pixel's last packet
+    float4* accSum;   // per camera pixel: xyz the colour sum of its packets, w bits(samples so far); 0 = never rendered
+};
+
 struct __attribute__((aligned(16))) BlockState { // LDS, one per workgroup
     // one stack column per thread: PRT_STACK_LDS (12) references, or 6 (reference, entry distance) pairs for the packet traversal
     uint32_t stack[PRT_STACK_LDS * PRT_BLOCK];
@@ -224,6 +234,12 @@ __device__ __forceinline__ const FrameArgs& frame_args(uint64_t bits)
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
     return *(const FrameArgs*)(FrameKernargs)(((uint64_t)hi << 32) | lo);
 }
+// frame_kernel_acc only: the same segment read as FrameAccArgs
+__device__ __forceinline__ const FrameAccArgs& frame_acc_args(uint64_t bits)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
+    return *(const FrameAccArgs*)(const __attribute__((address_space(4))) FrameAccArgs*)(((uint64_t)hi << 32) | lo);
+}
 
 // Counting build: a role call's event counts go to the block's 64-bit sums.
 __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& tr)
@@ -250,8 +266,9 @@ __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& t
 // pool state, PRT_NONE for lanes without a group.  Consumes the hits of the group's last rays, runs the bounce of
 // path_tracer.cpp:124-293 and appends the next rays to the block's queues (`tails` = the queue tails, owned by the caller,
 // who holds the shade lock and publishes them).  Returns, in every lane of the group, the group's new pending word: the
-// number of rays emitted, or PEND_DONE when the pixel has been written.
-template <bool COUNT, bool ENV>
+// number of rays emitted, or PEND_DONE when the pixel has been written.  ACC (frame_kernel_acc): the pixel's last packet adds
+// the pass to the accumulator and writes the mean over the pixel's total.
+template <bool COUNT, bool ENV, bool ACC>
 __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t poolLocal)
 {
     // a function of its own: its registers are those of a shade kernel, whatever the caller keeps live around it
@@ -536,7 +553,17 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         if (pk < packets) {
             needCamera = true;
         } else {
-            Vec3 c = scale3(A.p.exposure, div3s(color, (float)samples)); // path_tracer.cpp:28, image.cpp:45
+            uint32_t total = samples;
+            if constexpr (ACC) { // the pixel's state and sum go back with its new count; the image is the mean over all of it
+                const FrameAccArgs& AA = frame_acc_args(kargs);
+                const size_t pi = (size_t)x + (size_t)y * cam.width;
+                total += gld((const uint32_t*)&AA.accSum[pi] + 3);
+                if (slot == 0) {
+                    gst(&AA.accRng[pi], rng);
+                    gst4(&AA.accSum[pi], make_float4(color.x, color.y, color.z, asf(total)));
+                }
+            }
+            Vec3 c = scale3(A.p.exposure, div3s(color, (float)total)); // path_tracer.cpp:28, image.cpp:45
             if (slot == 0) {
                 uint32_t* px = (uint32_t*)(A.rgb + ((size_t)x + (size_t)y * cam.width) * 3);
                 gst(px, asu(c.x));
@@ -948,7 +975,8 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 
 // ---------------------------------------------------------------------------------------------------------------- roles
 // Shade role (the caller holds the lock): give empty rows new work, then sweep the pending words and run the ready groups.
-template <bool COUNT, bool ENV>
+// ACC: a pixel the accumulator has samples of starts from its stored generator state and colour sum instead of its seed.
+template <bool COUNT, bool ENV, bool ACC>
 __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
 {
     const FrameArgs& A = frame_args(kargs);
@@ -991,9 +1019,26 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         if (valid) {
             const uint32_t pixel = work_item_pixel(A, w);
             gst(&A.gPixel[P], pixel);
-            gst(&A.gRng[P], pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u);
-            gst(&A.gInfo[P], (uint32_t)PH_START << 20);
-            gst4(&A.gColor[P], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            if constexpr (ACC) {
+                uint32_t rng = pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u;
+                float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (pixel != 0xffffffffu) {
+                    const FrameAccArgs& AA = frame_acc_args(kargs);
+                    const size_t pi = (size_t)(pixel & 0xffffu) + (size_t)(pixel >> 16) * A.cam.width;
+                    const float4 s = gld4(&AA.accSum[pi]);
+                    if (asu(s.w) != 0u) {
+                        rng = gld(&AA.accRng[pi]);
+                        sum = make_float4(s.x, s.y, s.z, 0.0f);
+                    }
+                }
+                gst(&A.gRng[P], rng);
+                gst(&A.gInfo[P], (uint32_t)PH_START << 20);
+                gst4(&A.gColor[P], sum);
+            } else {
+                gst(&A.gRng[P], pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u);
+                gst(&A.gInfo[P], (uint32_t)PH_START << 20);
+                gst4(&A.gColor[P], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            }
         }
         lds_st(&B->pending[row * PRT_CHUNK + lane], valid ? 0u : PEND_DONE);
         const uint32_t n = (uint32_t)__popcll(__ballot(valid));
@@ -1019,7 +1064,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         const uint32_t j = i + (lane >> 3);
         const bool has = j < n;
         const uint32_t local = has ? lds_ld(&readyList[j]) : 0u;
-        const uint32_t np = shade_pass<COUNT, ENV>(kargs, has ? poolBase + local : PRT_NONE, local);
+        const uint32_t np = shade_pass<COUNT, ENV, ACC>(kargs, has ? poolBase + local : PRT_NONE, local);
         // (shade_pass has published the groups' state, their pending words and the queue tails, in that order)
         const bool head = has && (lane & 7u) == 0u;
         const bool done = head && np == PEND_DONE;
@@ -1043,8 +1088,9 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
     return did;
 }
 
-template <bool COUNT, bool ENV>
-__global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel(const FrameArgs kernargs)
+// The persistent launch (frame_kernel / frame_kernel_acc below): the roles reach the arguments through the kernel-argument segment.
+template <bool COUNT, bool ENV, bool ACC>
+__device__ __forceinline__ void frame_body()
 {
     const uint64_t kargs = frame_kernarg_bits();
     const FrameArgs& A = frame_args(kargs);
@@ -1148,7 +1194,7 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel(const
             half = bcast0(half);
             if (bcast0(got)) {
                 wg_acquire();
-                did = shade_role<COUNT, ENV>(kargs, half);
+                did = shade_role<COUNT, ENV, ACC>(kargs, half);
                 if (lane == 0) lds_st_rel(&B->lock[half], 0u);
                 PROF(tShade, nShade++);
             }
@@ -1233,5 +1279,36 @@ __global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel(const
             atomicAdd(&C[7], 1ull);
             atomicOr(&A.ctrl[PRT_WORK_WORDS], 2u); // sticky: survives the next render's clearing of the counters
         }
+    }
+}
+
+template <bool COUNT, bool ENV>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel(const FrameArgs kernargs)
+{
+    frame_body<COUNT, ENV, false>();
+}
+
+// One pass of progressive rendering: the frame kernel, with each pixel resumed from and returned to the accumulator.
+template <bool COUNT, bool ENV>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel_acc(const FrameAccArgs kernargs)
+{
+    frame_body<COUNT, ENV, true>();
+}
+
+// prt_hip_accum_resolve: exposure * sum / count of the accumulator over a rectangle (rw x rh from x0, y0), +0 where the count is 0 --
+// the expression the frame kernel writes, so a resolve equals the pass that produced the accumulator at another exposure.
+__global__ __launch_bounds__(256) void accum_resolve_kernel(const float4* accSum, uint32_t width, uint32_t x0, uint32_t y0, uint32_t rw,
+                                                            uint32_t rh, float exposure, float* rgb)
+{
+    const uint32_t n = rw * rh;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t pi = (size_t)(x0 + i % rw) + (size_t)(y0 + i / rw) * width;
+        const float4 s = gld4(&accSum[pi]);
+        const uint32_t count = asu(s.w);
+        const Vec3 c = count ? scale3(exposure, div3s(mk3(s.x, s.y, s.z), (float)count)) : mk3(0.0f, 0.0f, 0.0f);
+        uint32_t* px = (uint32_t*)(rgb + pi * 3);
+        gst(px, asu(c.x));
+        gst(px + 1, asu(c.y));
+        gst(px + 2, asu(c.z));
     }
 }

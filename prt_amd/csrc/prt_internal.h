@@ -75,6 +75,13 @@ struct prt_hip_ctx {
     void* frameArgs = nullptr;  // device copies of the frame kernel's argument block (ring)
     uint32_t frameArgSlot = 0;
     bool timed = false;
+    // progressive rendering (prt_hip_render_accumulate): one record per camera pixel, allocated on first use
+    uint32_t* accRng = nullptr;  // generator state
+    float4* accSum = nullptr;    // colour sum, bits(count)
+    size_t accPixels = 0;        // records allocated
+    bool accClear = true;        // the records must be zeroed before the next use (a reset since the last pass)
+    uint32_t accMax = 0;         // upper bound of any pixel's count; 0 = empty, the estimator is not bound yet
+    uint32_t accSeed = 0, accMaxDepth = 0, accRrDepth = 0; // the estimator the accumulated samples came from (accMax > 0)
 };
 
 

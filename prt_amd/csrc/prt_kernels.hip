@@ -456,6 +456,13 @@ int prt_hip_create(int device, prt_hip_ctx** out)
     return PRT_HIP_OK;
 }
 
+// Progressive rendering: the accumulator holds no samples from here on (its records are zeroed before their next use).
+static void accum_forget(prt_hip_ctx* c)
+{
+    c->accClear = true;
+    c->accMax = 0;
+}
+
 static void free_scene(prt_hip_ctx* c)
 {
     for (void* p : c->sceneAllocs) (void)hipFree(p);
@@ -475,6 +482,8 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->spill) (void)hipFree(c->spill);
     if (c->wfBuffer) (void)hipFree(c->wfBuffer);
     if (c->frameArgs) (void)hipFree(c->frameArgs);
+    if (c->accRng) (void)hipFree(c->accRng);
+    if (c->accSum) (void)hipFree(c->accSum);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -557,6 +566,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     if (s->meshCount == 0 || s->meshCount > PRT_MAX_BVH) return fail(PRT_HIP_EINVAL, "meshCount must be 1..8");
     HIP_TRY(hipSetDevice(c->device));
     free_scene(c);
+    accum_forget(c); // the accumulated samples were of the old scene
 
     std::vector<float4> wnodes, shade, bump, mats, alpha;
     std::vector<float> tris;                 // 9 floats per triangle, leaf order
@@ -868,6 +878,7 @@ int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
     static_assert(sizeof(DevCamera) == sizeof(prt_camera_desc), "camera layouts must match");
     memcpy(&c->cam, cam, sizeof(DevCamera));
     c->haveCamera = true;
+    accum_forget(c); // of another view (and perhaps another size)
     return PRT_HIP_OK;
 }
 
@@ -934,7 +945,7 @@ static int frame_layout(prt_hip_ctx* c, uint32_t blocks, bool env, FrameArgs& A)
     return PRT_HIP_OK;
 }
 
-static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s)
+static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s, bool acc)
 {
     const prt_render_params* p = &A.p;
     A.totalWork = (uint32_t)totalWork;
@@ -960,6 +971,17 @@ static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork,
     if (A.totalChunks == 0) return PRT_HIP_OK;
     const FrameArgs& dA = A;
     const bool env = c->sc.hasEnv != 0;
+    if (acc) { // a progressive pass: the same launch with the accumulator behind the arguments
+        const FrameAccArgs dAA{A, c->accRng, c->accSum};
+        if (p->countTraffic) {
+            if (env) hipLaunchKernelGGL((frame_kernel_acc<true, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAA);
+            else hipLaunchKernelGGL((frame_kernel_acc<true, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAA);
+        } else {
+            if (env) hipLaunchKernelGGL((frame_kernel_acc<false, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAA);
+            else hipLaunchKernelGGL((frame_kernel_acc<false, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAA);
+        }
+        return PRT_HIP_OK;
+    }
     if (p->countTraffic) {
         if (env) hipLaunchKernelGGL((frame_kernel<true, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dA);
         else hipLaunchKernelGGL((frame_kernel<true, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dA);
@@ -984,6 +1006,9 @@ static void fold_timing(prt_hip_ctx* c)
     c->ringUsed = 0;
 }
 
+static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
+                        void* stream, bool acc);
+
 int prt_hip_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
                    void* stream)
 {
@@ -993,6 +1018,14 @@ int prt_hip_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32
     if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
     if (p->samples == 0 || p->tileSize == 0 || p->nranks == 0 || p->rank >= p->nranks) return fail(PRT_HIP_EINVAL, "bad render params");
     if (W > 65535 || H > 65535 || p->samples / 8 > 255 || p->maxDepth > 255) return fail(PRT_HIP_EINVAL, "image, sample count or depth too large");
+    return frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, false);
+}
+
+// One launch of the frame kernel over a checked rectangle (prt_hip_render, prt_hip_render_accumulate).
+static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
+                        void* stream, bool acc)
+{
+    const uint32_t W = c->cam.width, H = c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
     // The frame kernel runs on the context's own stream; a caller's stream is ordered around it with two events: work
     // queued on it before this call is finished before the kernel starts, and whatever the caller queues next waits for it.
@@ -1045,10 +1078,10 @@ int prt_hip_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32
     hipEvent_t ev0 = c->evT0[c->ringUsed], ev1 = c->evT1[c->ringUsed];
     c->ringUsed++;
     HIP_TRY(hipEventRecord(ev0, s));
-    int rc = render_frame_kernel(c, A, totalWork, s);
+    int rc = render_frame_kernel(c, A, totalWork, s, acc);
     if (rc) return rc;
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string("frame_kernel launch: ") + hipGetErrorString(le));
+    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(acc ? "frame_kernel_acc" : "frame_kernel") + " launch: " + hipGetErrorString(le));
     HIP_TRY(hipEventRecord(ev1, s));
     c->lastRank = p->rank;
     c->lastNranks = p->nranks;
@@ -1110,6 +1143,157 @@ int prt_hip_render_gbuffer(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1
 }
 
 float* prt_hip_framebuffer(prt_hip_ctx* c) { return c ? c->fb : nullptr; }
+
+// ---- progressive rendering (include/prt_hip.h): the accumulator, one (state, sum, count) record per camera pixel
+#define PRT_ACC_MAX_COUNT (1u << 24) // a pixel's count as a float is exact up to here
+
+// Allocates the accumulator at the camera's size and zeroes it when a reset is pending (on the context's stream, ahead of
+// whatever uses it next).
+static int accum_ready(prt_hip_ctx* c)
+{
+    const size_t n = (size_t)c->cam.width * c->cam.height;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->accPixels != n) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); // the old records may still be in use
+        if (c->accRng) (void)hipFree(c->accRng);
+        if (c->accSum) (void)hipFree(c->accSum);
+        c->accRng = nullptr;
+        c->accSum = nullptr;
+        c->accPixels = 0;
+        HIP_TRY(hipMalloc(&c->accRng, n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->accSum, n * sizeof(float4)));
+        c->accPixels = n;
+        c->accClear = true;
+    }
+    if (c->accClear) {
+        HIP_TRY(hipMemsetAsync(c->accRng, 0, n * sizeof(uint32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->accSum, 0, n * sizeof(float4), c->stream));
+        c->accClear = false;
+        c->accMax = 0;
+    }
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_reset(prt_hip_ctx* c)
+{
+    if (!c) return fail(PRT_HIP_EINVAL, "NULL argument");
+    accum_forget(c);
+    return PRT_HIP_OK;
+}
+
+int prt_hip_render_accumulate(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p,
+                              float* d_rgb, void* stream)
+{
+    if (!c || !p) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveScene || !c->haveCamera) return fail(PRT_HIP_ESTATE, "upload a scene and set a camera first");
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    if (p->tileSize == 0 || p->nranks == 0 || p->rank >= p->nranks) return fail(PRT_HIP_EINVAL, "bad render params");
+    if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
+        return fail(PRT_HIP_EINVAL, "accumulate: samples must be a multiple of 8 from 8 to 2040 per pass");
+    if (W > 65535 || H > 65535 || p->maxDepth > 255) return fail(PRT_HIP_EINVAL, "image or depth too large");
+    if (c->accMax > 0 && !c->accClear && (p->seed != c->accSeed || p->maxDepth != c->accMaxDepth || p->rrDepth != c->accRrDepth))
+        return fail(PRT_HIP_EINVAL, "accumulate: seed, maxDepth and rrDepth must be those of the accumulated samples (reset the accumulator first)");
+    int rc = accum_ready(c);
+    if (rc) return rc;
+    if ((uint64_t)c->accMax + p->samples > PRT_ACC_MAX_COUNT)
+        return fail(PRT_HIP_EINVAL, "accumulate: a pixel's total would exceed 2^24 samples");
+    if ((rc = frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, true))) return rc;
+    c->accMax += p->samples;
+    c->accSeed = p->seed;
+    c->accMaxDepth = p->maxDepth;
+    c->accRrDepth = p->rrDepth;
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_resolve(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float exposure, float* d_rgb, void* stream)
+{
+    if (!c) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    int rc = accum_ready(c);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
+    if (caller) {
+        HIP_TRY(hipEventRecord(c->evIn, caller));
+        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
+    }
+    if (!d_rgb) {
+        if (c->fbPixels != (size_t)W * H) {
+            if (c->fb) (void)hipFree(c->fb);
+            c->fb = nullptr;
+            HIP_TRY(hipMalloc(&c->fb, (size_t)W * H * 3 * sizeof(float)));
+            HIP_TRY(hipMemsetAsync(c->fb, 0, (size_t)W * H * 3 * sizeof(float), s));
+            c->fbPixels = (size_t)W * H;
+        }
+        d_rgb = c->fb;
+    }
+    const uint32_t rw = x1 - x0 + 1, rh = y1 - y0 + 1; // rw * rh < 2^32: both are at most 65535 (checked by the passes)
+    const uint64_t n = (uint64_t)rw * rh;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->computeUnits * 8);
+    hipLaunchKernelGGL(accum_resolve_kernel, dim3(blocks), dim3(256), 0, s, (const float4*)c->accSum, W, x0, y0, rw, rh, exposure, d_rgb);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string("accum_resolve_kernel launch: ") + hipGetErrorString(le));
+    if (caller) {
+        HIP_TRY(hipEventRecord(c->evOut, s));
+        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
+    }
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_export(prt_hip_ctx* c, prt_accum_info* info, uint32_t* rng, float* sum, uint32_t* count)
+{
+    if (!c || !info || !rng || !sum || !count) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    int rc = accum_ready(c);
+    if (rc) return rc;
+    const size_t n = c->accPixels;
+    std::vector<float4> rec(n);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(rng, c->accRng, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rec.data(), c->accSum, n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        sum[3 * i] = rec[i].x;
+        sum[3 * i + 1] = rec[i].y;
+        sum[3 * i + 2] = rec[i].z;
+        memcpy(&count[i], &rec[i].w, sizeof(uint32_t));
+    }
+    const bool bound = c->accMax > 0;
+    *info = prt_accum_info{c->cam.width, c->cam.height, bound ? c->accSeed : 0u, bound ? c->accMaxDepth : 0u, bound ? c->accRrDepth : 0u};
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_import(prt_hip_ctx* c, const prt_accum_info* info, const uint32_t* rng, const float* sum, const uint32_t* count)
+{
+    if (!c || !info || !rng || !sum || !count) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    if (info->width != c->cam.width || info->height != c->cam.height)
+        return fail(PRT_HIP_EINVAL, "accum_import: the accumulator is " + std::to_string(info->width) + "x" + std::to_string(info->height) +
+                                        ", the camera " + std::to_string(c->cam.width) + "x" + std::to_string(c->cam.height));
+    if (info->maxDepth > 255) return fail(PRT_HIP_EINVAL, "accum_import: maxDepth too large");
+    const size_t n = (size_t)c->cam.width * c->cam.height;
+    std::vector<float4> rec(n);
+    uint32_t most = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (count[i] > PRT_ACC_MAX_COUNT) return fail(PRT_HIP_EINVAL, "accum_import: a count exceeds 2^24");
+        float w;
+        memcpy(&w, &count[i], sizeof(float));
+        rec[i] = make_float4(sum[3 * i], sum[3 * i + 1], sum[3 * i + 2], w);
+        most = std::max(most, count[i]);
+    }
+    int rc = accum_ready(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->accRng, rng, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->accSum, rec.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    c->accMax = most;
+    c->accSeed = info->seed;
+    c->accMaxDepth = info->maxDepth;
+    c->accRrDepth = info->rrDepth;
+    return PRT_HIP_OK;
+}
 
 } // extern "C"
 
