@@ -243,6 +243,43 @@ int prt_hip_accum_export(prt_hip_ctx* ctx, prt_accum_info* info, uint32_t* rng, 
 int prt_hip_accum_import(prt_hip_ctx* ctx, const prt_accum_info* info, const uint32_t* rng, const float* sum,
                          const uint32_t* count);
 
+/* ---- adaptive sampling: passes that trace only the pixels whose noise is above a target.  Besides its accumulator record, every
+ * pixel has a MOMENT record {mean, M2, bits(m), 0} (16 bytes): Welford's running mean and sum of squared deviations of the mean
+ * luminance of its packets of 8 samples, over the m packets adaptive passes gave it.  Only adaptive passes update it: at each packet
+ * end, with res the sum of the packet's 8 slot results (f32, no FMA, in this order)
+ *     L = (0.2126f*res.x + 0.7152f*res.y + 0.0722f*res.z) * 0.125f;  m += 1; d = L - mean; mean += d / (float)m; M2 += d * (L - mean);
+ * The ERROR of a pixel with count n (its accumulator count) at an exposure and a floor: +inf when m < 2, otherwise
+ *     var = M2 / (float)(m - 1); se = sqrtf(var / (float)(n >> 3)); err = (exposure * se) / (floor + exposure * mean)
+ * (correctly rounded f32 divide and sqrt): the relative standard error of the displayed pixel; floor, in displayed units, lets black
+ * pixels converge.  A pass covers the work items of prt_hip_render_accumulate over the same rectangle and rank; an owned pixel is
+ * ACTIVE iff n + samples <= maxSamples and (n < minSamples or err > threshold) -- a NaN error counts as converged, +inf as active.
+ * Active pixels get params->samples more samples exactly as an accumulate pass gives them, so every pixel holds, bit for bit, the
+ * one-shot render of its own count.  Every other owned pixel of the rectangle gets exposure * sum / count (+0 where the count is 0)
+ * in d_rgb: after the pass d_rgb over the owned pixels equals prt_hip_accum_resolve at that exposure bit for bit; pixels the rank
+ * does not own are left untouched.  prt_hip_render_accumulate neither reads nor updates the moments (after mixed passes a moment
+ * covers only the adaptive packets; the error still uses the full n).  prt_hip_accum_reset, prt_hip_accum_import, prt_hip_set_camera
+ * and prt_hip_upload_scene zero the moments.  The estimator binding (seed, maxDepth and rrDepth), the multiple of 8 from 8 to 2040
+ * per pass and the 2^24 cap are those of prt_hip_render_accumulate.  All refusals are PRT_HIP_EINVAL with a message. ---- */
+typedef struct {
+    float threshold;     /* relative standard error target (>= 0, finite) */
+    float floor;         /* > 0, displayed units: added to exposure*mean in the error's denominator */
+    uint32_t minSamples; /* multiple of 8: a pixel below it is always traced */
+    uint32_t maxSamples; /* multiple of 8, >= minSamples, <= 2^24: no pixel is taken above it */
+} prt_adaptive_params;
+
+/* One adaptive pass. Selection, then one frame-kernel launch over the active pixels only. Synchronises the context's stream
+ * once, between the two, to read the active count: *active gets the number of pixels traced. With 0 active, nothing is
+ * launched. Rectangle, rank/tile, d_rgb and stream rules are those of prt_hip_render_accumulate.  prt_hip_get_stats counts the
+ * pass's rays, and its nPx is *active. */
+int prt_hip_render_adaptive(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p,
+                            const prt_adaptive_params* a, uint32_t* active, float* d_rgb, void* stream);
+/* err of every pixel of the rectangle (formula above) into a camera-sized host array at (x + y*width); synchronous.  floor > 0. */
+int prt_hip_accum_error(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float exposure, float floor, float* err);
+/* Checkpoint / resume of the moment records: 4*width*height floats {mean, M2, bits(m), 0}. Import after prt_hip_accum_import (which
+ * zeroes them); an m above 2^21 (2^24 samples in packets of 8) is refused. */
+int prt_hip_accum_export_moments(prt_hip_ctx* ctx, float* mom);
+int prt_hip_accum_import_moments(prt_hip_ctx* ctx, const float* mom);
+
 #ifdef __cplusplus
 }
 #endif

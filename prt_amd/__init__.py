@@ -94,6 +94,10 @@ class AccumInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("seed", C.c_uint32), ("maxDepth", C.c_uint32), ("rrDepth", C.c_uint32)]
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -111,7 +115,7 @@ EXPORTS = [
     "prt_hip_upload_scene", "prt_hip_set_camera", "prt_hip_render", "prt_hip_render_gbuffer", "prt_hip_download", "prt_hip_framebuffer", "prt_hip_gather",
     "prt_hip_build_bvh", "prt_hip_comm_unique_id", "prt_hip_comm_init", "prt_hip_comm_adopt", "prt_hip_comm_destroy", "prt_hip_gather_rccl", "prt_hip_gather_payload_bytes",
     "prt_hip_get_stats", "prt_hip_accum_reset", "prt_hip_render_accumulate", "prt_hip_accum_resolve", "prt_hip_accum_export",
-    "prt_hip_accum_import",
+    "prt_hip_accum_import", "prt_hip_render_adaptive", "prt_hip_accum_error", "prt_hip_accum_export_moments", "prt_hip_accum_import_moments",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
@@ -193,6 +197,11 @@ def _load(path, with_test_entry_points):
     L.prt_hip_accum_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, vp]
     L.prt_hip_accum_export.argtypes = [vp, C.POINTER(AccumInfo), vp, vp, vp]
     L.prt_hip_accum_import.argtypes = [vp, C.POINTER(AccumInfo), vp, vp, vp]
+    L.prt_hip_render_adaptive.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RenderParams), C.POINTER(AdaptiveParams),
+                                          C.POINTER(C.c_uint32), vp, vp]
+    L.prt_hip_accum_error.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp]
+    L.prt_hip_accum_export_moments.argtypes = [vp, vp]
+    L.prt_hip_accum_import_moments.argtypes = [vp, vp]
     if with_test_entry_points:
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
@@ -566,6 +575,67 @@ class PathTracer:
             if budget_ms is not None and spent >= budget_ms:  # checked after each pass: the first one always runs
                 break
         return img, done
+
+    # ---- adaptive sampling (include/prt_hip.h "adaptive sampling"): passes trace only the pixels whose relative standard error is
+    # above a threshold; every pixel still holds, bit for bit, the one-shot render of its own sample count
+    def adaptive_pass_async(self, samples, threshold, min_spp, max_spp, floor=0.01, x0=0, y0=0, x1=None, y1=None, d_rgb=None, stream=None,
+                            **kw):
+        """One adaptive pass over the inclusive rectangle: selection, then one launch over the active pixels.  Returns the number of
+        active pixels (it waits for the selection, not for the launch)."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        p = self.params(samples, **kw)
+        a = AdaptiveParams(threshold, floor, min_spp, max_spp)
+        active = C.c_uint32()
+        self._chk(self._L.prt_hip_render_adaptive(self._ctx, x0, y0, x1, y1, C.byref(p), C.byref(a), C.byref(active), d_rgb, stream),
+                  "prt_hip_render_adaptive")
+        return active.value
+
+    def adaptive_pass(self, samples, threshold, min_spp, max_spp, floor=0.01, x0=0, y0=0, x1=None, y1=None, exposure=1.0, rank=0, nranks=1,
+                      tile=16, count_traffic=False, max_depth=None):
+        """One adaptive pass; returns (the rectangle's image, active pixels) and sets last_stats (this pass's rays; nPx = active).
+        Converged pixels are resolved from the accumulator, so the image is that of every pixel's own sample count."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        active = self.adaptive_pass_async(samples, threshold, min_spp, max_spp, floor, x0, y0, x1, y1, exposure=exposure, rank=rank,
+                                          nranks=nranks, tile=tile, count_traffic=count_traffic, max_depth=max_depth)
+        return self._download_rect(x0, y0, x1, y1, stats=True), active
+
+    def render_adaptive(self, threshold, min_spp=32, max_spp=1024, step=16, floor=0.01, budget_ms=None, callback=None, exposure=1.0, **kw):
+        """The adaptive viewer's loop: from an empty accumulator, adaptive passes of `step` samples over the whole image, calling
+        callback(image, active) after each, until a pass has no active pixel or `budget_ms` of kernel time is spent.  Returns
+        (image, per-pixel sample counts)."""
+        self.accum_reset()
+        spent, img = 0.0, None
+        while True:
+            img, active = self.adaptive_pass(step, threshold, min_spp, max_spp, floor, exposure=exposure, **kw)
+            spent += self.last_stats["kernelMsSum"]
+            if callback is not None:
+                callback(img, active)
+            if active == 0 or (budget_ms is not None and spent >= budget_ms):  # checked after each pass: the first one always runs
+                break
+        return img, self.accum_counts()
+
+    def accum_error(self, exposure=1.0, floor=0.01, x0=0, y0=0, x1=None, y1=None):
+        """(h, w) float32: the relative standard error of every pixel of the rectangle at this exposure (+inf below two packets)."""
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        W, H = self._camera.width, self._camera.height
+        err = np.zeros((H, W), dtype=np.float32)
+        self._chk(self._L.prt_hip_accum_error(self._ctx, x0, y0, x1, y1, exposure, floor, err.ctypes.data_as(C.c_void_p)), "prt_hip_accum_error")
+        return err[y0:y1 + 1, x0:x1 + 1].copy()
+
+    def accum_export_moments(self):
+        """(H, W, 4) float32: every pixel's moment record {mean, M2, bits(m), 0} (m = [..., 2].view(uint32), packets of 8 samples)."""
+        W, H = self._camera.width, self._camera.height
+        mom = np.zeros((H, W, 4), dtype=np.float32)
+        self._chk(self._L.prt_hip_accum_export_moments(self._ctx, mom.ctypes.data_as(C.c_void_p)), "prt_hip_accum_export_moments")
+        return mom
+
+    def accum_import_moments(self, mom):
+        """Resume the moments of a checkpoint (after accum_import, which zeroes them): an array made by accum_export_moments."""
+        W, H = self._camera.width, self._camera.height
+        a = np.ascontiguousarray(mom, dtype=np.float32).reshape(-1)
+        if len(a) != 4 * W * H:
+            raise PrtError(f"accum_import_moments: {len(a)} floats do not match the camera's {W}x{H} pixels (4 per pixel)")
+        self._chk(self._L.prt_hip_accum_import_moments(self._ctx, a.ctypes.data_as(C.c_void_p)), "prt_hip_accum_import_moments")
 
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""

@@ -13,6 +13,7 @@ SOURCES = [
     "prt_kernels.hip",
     "prt_gather.hip",
     "prt_bvh_build.hip",
+    "prt_select.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

@@ -134,6 +134,15 @@ struct FrameAccArgs {
     float4* accSum;   // per camera pixel: xyz the colour sum of its packets, w bits(samples so far); 0 = never rendered
 };
 
+// Adaptive sampling (prt_hip_render_adaptive): frame_kernel_adapt's arguments are a FrameAccArgs (so frame_acc_args
+// reads them as a prefix) followed by the launch's compacted pixel list and the per-pixel moment records.  Work item w is the pixel
+// list[w] instead of work_item_pixel(w); every packet end folds the packet's mean luminance into the pixel's moment record.
+struct FrameAdaptArgs {
+    FrameAccArgs acc;
+    const uint32_t* list; // totalWork pixel codes (x | y << 16) in work-item order, padded with 0xffffffff to a multiple of PRT_CHUNK
+    float4* accMom;       // per camera pixel: {mean, M2, bits(m), 0} of the luminance of its adaptive packets (Welford)
+};
+
 struct __attribute__((aligned(16))) BlockState { // LDS, one per workgroup
     // one stack column per thread: PRT_STACK_LDS (12) references, or 6 (reference, entry distance) pairs for the packet traversal
     uint32_t stack[PRT_STACK_LDS * PRT_BLOCK];
@@ -240,6 +249,12 @@ __device__ __forceinline__ const FrameAccArgs& frame_acc_args(uint64_t bits)
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
     return *(const FrameAccArgs*)(const __attribute__((address_space(4))) FrameAccArgs*)(((uint64_t)hi << 32) | lo);
 }
+// frame_kernel_adapt only: the same segment read as FrameAdaptArgs
+__device__ __forceinline__ const FrameAdaptArgs& frame_adapt_args(uint64_t bits)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
+    return *(const FrameAdaptArgs*)(const __attribute__((address_space(4))) FrameAdaptArgs*)(((uint64_t)hi << 32) | lo);
+}
 
 // Counting build: a role call's event counts go to the block's 64-bit sums.
 __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& tr)
@@ -267,10 +282,12 @@ __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& t
 // path_tracer.cpp:124-293 and appends the next rays to the block's queues (`tails` = the queue tails, owned by the caller,
 // who holds the shade lock and publishes them).  Returns, in every lane of the group, the group's new pending word: the
 // number of rays emitted, or PEND_DONE when the pixel has been written.  ACC (frame_kernel_acc): the pixel's last packet adds
-// the pass to the accumulator and writes the mean over the pixel's total.
-template <bool COUNT, bool ENV, bool ACC>
+// the pass to the accumulator and writes the mean over the pixel's total.  ADAPT (frame_kernel_adapt, implies ACC): every packet
+// end also folds the packet's mean luminance into the pixel's moment record.
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
 __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t poolLocal)
 {
+    static_assert(ACC || !ADAPT, "an adaptive pass is an accumulate pass");
     // a function of its own: its registers are those of a shade kernel, whatever the caller keeps live around it
     const FrameArgs& A = frame_args(kargs);
     const BlockLds B = block_lds();
@@ -549,6 +566,17 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
 #pragma unroll
         for (uint32_t l = 0; l < 8; l++) res = add3(res, sh3(result, gbase + l));
         color = add3(color, res);
+        if constexpr (ADAPT) { // Welford: m += 1; d = L - mean; mean += d / m; M2 += d * (L - mean), L the packet's mean luminance
+            if (slot == 0) {   // (the group owns the pixel for the pass; the hand-off between shade rounds orders the record as gColor)
+                const FrameAdaptArgs& AD = frame_adapt_args(kargs);
+                const size_t pi = (size_t)x + (size_t)y * cam.width;
+                const float L = (0.2126f * res.x + 0.7152f * res.y + 0.0722f * res.z) * 0.125f;
+                const float4 mo = gld4(&AD.accMom[pi]);
+                const uint32_t m = asu(mo.z) + 1u;
+                const float d = L - mo.x, mean = mo.x + d / (float)m;
+                gst4(&AD.accMom[pi], make_float4(mean, mo.y + d * (L - mean), asf(m), 0.0f));
+            }
+        }
         pk++;
         if (pk < packets) {
             needCamera = true;
@@ -976,7 +1004,8 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 // ---------------------------------------------------------------------------------------------------------------- roles
 // Shade role (the caller holds the lock): give empty rows new work, then sweep the pending words and run the ready groups.
 // ACC: a pixel the accumulator has samples of starts from its stored generator state and colour sum instead of its seed.
-template <bool COUNT, bool ENV, bool ACC>
+// ADAPT: work item w is the pixel of the launch's compacted list, list[w].
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
 __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
 {
     const FrameArgs& A = frame_args(kargs);
@@ -1017,7 +1046,9 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         const bool valid = w < A.totalWork;
         const uint32_t P = poolBase + row * PRT_CHUNK + lane;
         if (valid) {
-            const uint32_t pixel = work_item_pixel(A, w);
+            uint32_t pixel;
+            if constexpr (ADAPT) pixel = gld(&frame_adapt_args(kargs).list[w]);
+            else pixel = work_item_pixel(A, w);
             gst(&A.gPixel[P], pixel);
             if constexpr (ACC) {
                 uint32_t rng = pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u;
@@ -1064,7 +1095,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         const uint32_t j = i + (lane >> 3);
         const bool has = j < n;
         const uint32_t local = has ? lds_ld(&readyList[j]) : 0u;
-        const uint32_t np = shade_pass<COUNT, ENV, ACC>(kargs, has ? poolBase + local : PRT_NONE, local);
+        const uint32_t np = shade_pass<COUNT, ENV, ACC, ADAPT>(kargs, has ? poolBase + local : PRT_NONE, local);
         // (shade_pass has published the groups' state, their pending words and the queue tails, in that order)
         const bool head = has && (lane & 7u) == 0u;
         const bool done = head && np == PEND_DONE;
@@ -1088,8 +1119,9 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
     return did;
 }
 
-// The persistent launch (frame_kernel / frame_kernel_acc below): the roles reach the arguments through the kernel-argument segment.
-template <bool COUNT, bool ENV, bool ACC>
+// The persistent launch (frame_kernel / frame_kernel_acc / frame_kernel_adapt below): the roles reach the arguments through the
+// kernel-argument segment.
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
 __device__ __forceinline__ void frame_body()
 {
     const uint64_t kargs = frame_kernarg_bits();
@@ -1194,7 +1226,7 @@ __device__ __forceinline__ void frame_body()
             half = bcast0(half);
             if (bcast0(got)) {
                 wg_acquire();
-                did = shade_role<COUNT, ENV, ACC>(kargs, half);
+                did = shade_role<COUNT, ENV, ACC, ADAPT>(kargs, half);
                 if (lane == 0) lds_st_rel(&B->lock[half], 0u);
                 PROF(tShade, nShade++);
             }
@@ -1285,14 +1317,33 @@ __device__ __forceinline__ void frame_body()
 template <bool COUNT, bool ENV>
 __global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel(const FrameArgs kernargs)
 {
-    frame_body<COUNT, ENV, false>();
+    frame_body<COUNT, ENV, false, false>();
 }
 
 // One pass of progressive rendering: the frame kernel, with each pixel resumed from and returned to the accumulator.
 template <bool COUNT, bool ENV>
 __global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel_acc(const FrameAccArgs kernargs)
 {
-    frame_body<COUNT, ENV, true>();
+    frame_body<COUNT, ENV, true, false>();
+}
+
+// One adaptive pass: the accumulating frame kernel over a compacted list of the pixels still to be traced, with every packet's mean
+// luminance folded into the pixel's moment record.
+template <bool COUNT, bool ENV>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel_adapt(const FrameAdaptArgs kernargs)
+{
+    frame_body<COUNT, ENV, true, true>();
+}
+
+// exposure * sum / count of an accumulator record (+0 where the count is 0) into one pixel of a framebuffer
+__device__ __forceinline__ void accum_resolve_pixel(float4 s, float exposure, float* rgb)
+{
+    const uint32_t count = asu(s.w);
+    const Vec3 c = count ? scale3(exposure, div3s(mk3(s.x, s.y, s.z), (float)count)) : mk3(0.0f, 0.0f, 0.0f);
+    uint32_t* px = (uint32_t*)rgb;
+    gst(px, asu(c.x));
+    gst(px + 1, asu(c.y));
+    gst(px + 2, asu(c.z));
 }
 
 // prt_hip_accum_resolve: exposure * sum / count of the accumulator over a rectangle (rw x rh from x0, y0), +0 where the count is 0 --
@@ -1303,12 +1354,52 @@ __global__ __launch_bounds__(256) void accum_resolve_kernel(const float4* accSum
     const uint32_t n = rw * rh;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const size_t pi = (size_t)(x0 + i % rw) + (size_t)(y0 + i / rw) * width;
-        const float4 s = gld4(&accSum[pi]);
-        const uint32_t count = asu(s.w);
-        const Vec3 c = count ? scale3(exposure, div3s(mk3(s.x, s.y, s.z), (float)count)) : mk3(0.0f, 0.0f, 0.0f);
-        uint32_t* px = (uint32_t*)(rgb + pi * 3);
-        gst(px, asu(c.x));
-        gst(px + 1, asu(c.y));
-        gst(px + 2, asu(c.z));
+        accum_resolve_pixel(gld4(&accSum[pi]), exposure, rgb + pi * 3);
+    }
+}
+
+// ---- adaptive sampling (prt_hip_render_adaptive, include/prt_hip.h)
+// The relative standard error of a pixel's displayed value: n its sample count, mo its moment record {mean, M2, bits(m), 0} over m
+// packets of 8 samples.  +inf below two packets; floor (displayed units) keeps the error of black pixels finite.
+__device__ __forceinline__ float adapt_pixel_error(uint32_t n, float4 mo, float exposure, float floor)
+{
+    const uint32_t m = asu(mo.z);
+    if (m < 2u) return __builtin_inff();
+    const float var = mo.y / (float)(m - 1u);
+    const float se = sqrtf(var / (float)(n >> 3));
+    return (exposure * se) / (floor + exposure * mo.x);
+}
+
+// Selection of an adaptive pass: work item w of the pass (the accumulate pass's items, A.totalWork of them) is flagged when its pixel
+// is active -- n + samples <= maxSamples and (n < minSamples or err > threshold), so a NaN error counts as converged -- and an owned
+// pixel that is not active gets its resolved value (accum_resolve_kernel's expression) in A.rgb.  code[w] = the pixel (x | y << 16, or
+// 0xffffffff for an item outside the rectangle or the rank's tiles), for the compaction behind it.
+__global__ __launch_bounds__(256) void adapt_select_kernel(const FrameArgs A, const float4* accSum, const float4* accMom, prt_adaptive_params S,
+                                                           uint32_t* code, uint8_t* flag)
+{
+    for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < A.totalWork; w += gridDim.x * blockDim.x) {
+        const uint32_t pixel = work_item_pixel(A, w);
+        bool active = false;
+        if (pixel != 0xffffffffu) {
+            const size_t pi = (size_t)(pixel & 0xffffu) + (size_t)(pixel >> 16) * A.cam.width;
+            const float4 s = gld4(&accSum[pi]);
+            const uint32_t n = asu(s.w);
+            active = n + A.p.samples <= S.maxSamples &&
+                     (n < S.minSamples || adapt_pixel_error(n, gld4(&accMom[pi]), A.p.exposure, S.floor) > S.threshold);
+            if (!active) accum_resolve_pixel(s, A.p.exposure, A.rgb + pi * 3);
+        }
+        code[w] = pixel;
+        flag[w] = active ? 1u : 0u;
+    }
+}
+
+// prt_hip_accum_error: the error of every pixel of a rectangle (rw x rh from x0, y0) into err[i], i row-major within the rectangle.
+__global__ __launch_bounds__(256) void accum_error_kernel(const float4* accSum, const float4* accMom, uint32_t width, uint32_t x0, uint32_t y0,
+                                                          uint32_t rw, uint32_t rh, float exposure, float floor, float* err)
+{
+    const uint32_t n = rw * rh;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t pi = (size_t)(x0 + i % rw) + (size_t)(y0 + i / rw) * width;
+        err[i] = adapt_pixel_error(asu(gld4(&accSum[pi]).w), gld4(&accMom[pi]), exposure, floor);
     }
 }

@@ -82,6 +82,20 @@ struct prt_hip_ctx {
     bool accClear = true;        // the records must be zeroed before the next use (a reset since the last pass)
     uint32_t accMax = 0;         // upper bound of any pixel's count; 0 = empty, the estimator is not bound yet
     uint32_t accSeed = 0, accMaxDepth = 0, accRrDepth = 0; // the estimator the accumulated samples came from (accMax > 0)
+    // adaptive sampling (prt_hip_render_adaptive): allocated on first use
+    float4* accMom = nullptr;    // per camera pixel: {mean, M2, bits(m), 0}
+    size_t momPixels = 0;        // records allocated
+    bool momClear = true;        // the moment records must be zeroed before their next use
+    uint32_t* adCode = nullptr;  // per work item of a pass: its pixel code (the selection's output)
+    uint32_t* adList = nullptr;  // the compacted codes of the active pixels, padded to a multiple of 64 (the frame kernel's input)
+    uint8_t* adFlag = nullptr;   // per work item: 1 = active
+    size_t adItems = 0;          // work items the three buffers hold
+    void* adTemp = nullptr;      // hipcub scratch of the compaction
+    size_t adTempBytes = 0;
+    uint32_t* adCount = nullptr;     // device: active pixels of the last selection
+    uint32_t* adCountHost = nullptr; // pinned host copy of it
+    float* adErr = nullptr;          // prt_hip_accum_error: the rectangle's errors (device)
+    size_t adErrItems = 0;
 };
 
 
@@ -90,3 +104,7 @@ void prt_gather_release(prt_hip_ctx* c);
 // prt_kernels.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
 // stream must be idle); `clear` consumes it (prt_hip_get_stats), download / gather only report it
 int prt_sticky_error(prt_hip_ctx* c, bool clear);
+// prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
+// temp == nullptr it only sets tempBytes
+hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,
+                              uint64_t n, hipStream_t s);

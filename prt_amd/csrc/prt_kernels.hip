@@ -461,6 +461,7 @@ static void accum_forget(prt_hip_ctx* c)
 {
     c->accClear = true;
     c->accMax = 0;
+    c->momClear = true; // and no moments (adaptive sampling)
 }
 
 static void free_scene(prt_hip_ctx* c)
@@ -484,6 +485,14 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->frameArgs) (void)hipFree(c->frameArgs);
     if (c->accRng) (void)hipFree(c->accRng);
     if (c->accSum) (void)hipFree(c->accSum);
+    if (c->accMom) (void)hipFree(c->accMom);
+    if (c->adCode) (void)hipFree(c->adCode);
+    if (c->adList) (void)hipFree(c->adList);
+    if (c->adFlag) (void)hipFree(c->adFlag);
+    if (c->adTemp) (void)hipFree(c->adTemp);
+    if (c->adCount) (void)hipFree(c->adCount);
+    if (c->adErr) (void)hipFree(c->adErr);
+    if (c->adCountHost) (void)hipHostFree(c->adCountHost);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -945,7 +954,10 @@ static int frame_layout(prt_hip_ctx* c, uint32_t blocks, bool env, FrameArgs& A)
     return PRT_HIP_OK;
 }
 
-static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s, bool acc)
+enum FrameKind { FRAME_ONE_SHOT, FRAME_ACC, FRAME_ADAPT }; // frame_kernel, frame_kernel_acc, frame_kernel_adapt
+static const char* const kFrameKernelName[] = {"frame_kernel", "frame_kernel_acc", "frame_kernel_adapt"};
+
+static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s, FrameKind kind)
 {
     const prt_render_params* p = &A.p;
     A.totalWork = (uint32_t)totalWork;
@@ -971,7 +983,18 @@ static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork,
     if (A.totalChunks == 0) return PRT_HIP_OK;
     const FrameArgs& dA = A;
     const bool env = c->sc.hasEnv != 0;
-    if (acc) { // a progressive pass: the same launch with the accumulator behind the arguments
+    if (kind == FRAME_ADAPT) { // an adaptive pass: the accumulate launch with the pixel list and the moments behind its arguments
+        const FrameAdaptArgs dAD{FrameAccArgs{A, c->accRng, c->accSum}, c->adList, c->accMom};
+        if (p->countTraffic) {
+            if (env) hipLaunchKernelGGL((frame_kernel_adapt<true, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAD);
+            else hipLaunchKernelGGL((frame_kernel_adapt<true, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAD);
+        } else {
+            if (env) hipLaunchKernelGGL((frame_kernel_adapt<false, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAD);
+            else hipLaunchKernelGGL((frame_kernel_adapt<false, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAD);
+        }
+        return PRT_HIP_OK;
+    }
+    if (kind == FRAME_ACC) { // a progressive pass: the same launch with the accumulator behind the arguments
         const FrameAccArgs dAA{A, c->accRng, c->accSum};
         if (p->countTraffic) {
             if (env) hipLaunchKernelGGL((frame_kernel_acc<true, true>), dim3(blocks), dim3(PRT_BLOCK), 0, s, dAA);
@@ -1007,7 +1030,7 @@ static void fold_timing(prt_hip_ctx* c)
 }
 
 static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
-                        void* stream, bool acc);
+                        void* stream, FrameKind kind);
 
 int prt_hip_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
                    void* stream)
@@ -1018,12 +1041,19 @@ int prt_hip_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32
     if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
     if (p->samples == 0 || p->tileSize == 0 || p->nranks == 0 || p->rank >= p->nranks) return fail(PRT_HIP_EINVAL, "bad render params");
     if (W > 65535 || H > 65535 || p->samples / 8 > 255 || p->maxDepth > 255) return fail(PRT_HIP_EINVAL, "image, sample count or depth too large");
-    return frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, false);
+    return frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, FRAME_ONE_SHOT);
 }
 
-// One launch of the frame kernel over a checked rectangle (prt_hip_render, prt_hip_render_accumulate).
-static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
-                        void* stream, bool acc)
+// The set-up of a frame-kernel launch over a checked rectangle, shared by the one-shot, accumulate and adaptive passes: the caller's
+// stream is ordered before the context's, the framebuffer is resolved and the launch's geometry and work items are laid out.
+struct FrameLaunch {
+    FrameArgs A{};
+    uint64_t totalWork = 0; // tile-major work items of the rectangle (or of the rank's tiles in it)
+    hipStream_t s = nullptr, caller = nullptr;
+};
+
+static int frame_setup(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
+                       void* stream, FrameLaunch& F)
 {
     const uint32_t W = c->cam.width, H = c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
@@ -1031,6 +1061,8 @@ static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, u
     // queued on it before this call is finished before the kernel starts, and whatever the caller queues next waits for it.
     hipStream_t s = c->stream;
     hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
+    F.s = s;
+    F.caller = caller;
     if (caller) {
         HIP_TRY(hipEventRecord(c->evIn, caller));
         HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
@@ -1045,7 +1077,7 @@ static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, u
         }
         d_rgb = c->fb;
     }
-    FrameArgs A{};
+    FrameArgs& A = F.A;
     A.sc = c->sc;
     A.cam = c->cam;
     A.p = *p;
@@ -1071,6 +1103,29 @@ static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, u
     }
     if (totalWork > 0xffffffffull) return fail(PRT_HIP_EINVAL, "rectangle too large");
     A.rgb = d_rgb;
+    F.totalWork = totalWork;
+    return PRT_HIP_OK;
+}
+
+// The frame's output has been written (by a launch or, in an adaptive pass without active pixels, by the selection alone): remember
+// the output for the gathers and order the caller's stream behind it.
+static int frame_finish(prt_hip_ctx* c, const FrameLaunch& F)
+{
+    c->lastRank = F.A.p.rank;
+    c->lastNranks = F.A.p.nranks;
+    c->lastTile = F.A.p.tileSize;
+    c->lastTarget = F.A.rgb;
+    if (F.caller) {
+        HIP_TRY(hipEventRecord(c->evOut, F.s));
+        HIP_TRY(hipStreamWaitEvent(F.caller, c->evOut, 0));
+    }
+    return PRT_HIP_OK;
+}
+
+// The launch itself, over `totalWork` work items, timed by the context's event ring.
+static int frame_launch(prt_hip_ctx* c, FrameLaunch& F, uint64_t totalWork, FrameKind kind)
+{
+    hipStream_t s = F.s;
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
     if (c->ringUsed == PRT_TIMING_RING) fold_timing(c);
     if (!c->evT0[c->ringUsed]) HIP_TRY(hipEventCreate(&c->evT0[c->ringUsed]));
@@ -1078,22 +1133,25 @@ static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, u
     hipEvent_t ev0 = c->evT0[c->ringUsed], ev1 = c->evT1[c->ringUsed];
     c->ringUsed++;
     HIP_TRY(hipEventRecord(ev0, s));
-    int rc = render_frame_kernel(c, A, totalWork, s, acc);
+    int rc = render_frame_kernel(c, F.A, totalWork, s, kind);
     if (rc) return rc;
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(acc ? "frame_kernel_acc" : "frame_kernel") + " launch: " + hipGetErrorString(le));
+    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(kFrameKernelName[kind]) + " launch: " + hipGetErrorString(le));
     HIP_TRY(hipEventRecord(ev1, s));
-    c->lastRank = p->rank;
-    c->lastNranks = p->nranks;
-    c->lastTile = p->tileSize;
-    c->lastTarget = d_rgb;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evOut, s));
-        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
-    }
+    if ((rc = frame_finish(c, F))) return rc;
     c->timed = true;
     c->frameLaunched = true;
     return PRT_HIP_OK;
+}
+
+// One launch of the frame kernel over a checked rectangle (prt_hip_render, prt_hip_render_accumulate).
+static int frame_render(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p, float* d_rgb,
+                        void* stream, FrameKind kind)
+{
+    FrameLaunch F;
+    int rc = frame_setup(c, x0, y0, x1, y1, p, d_rgb, stream, F);
+    if (rc) return rc;
+    return frame_launch(c, F, F.totalWork, kind);
 }
 
 int prt_hip_render_gbuffer(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t type, uint32_t seed, float exposure,
@@ -1198,7 +1256,7 @@ int prt_hip_render_accumulate(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t
     if (rc) return rc;
     if ((uint64_t)c->accMax + p->samples > PRT_ACC_MAX_COUNT)
         return fail(PRT_HIP_EINVAL, "accumulate: a pixel's total would exceed 2^24 samples");
-    if ((rc = frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, true))) return rc;
+    if ((rc = frame_render(c, x0, y0, x1, y1, p, d_rgb, stream, FRAME_ACC))) return rc;
     c->accMax += p->samples;
     c->accSeed = p->seed;
     c->accMaxDepth = p->maxDepth;
@@ -1292,6 +1350,190 @@ int prt_hip_accum_import(prt_hip_ctx* c, const prt_accum_info* info, const uint3
     c->accSeed = info->seed;
     c->accMaxDepth = info->maxDepth;
     c->accRrDepth = info->rrDepth;
+    c->momClear = true; // the moments of the imported samples, if any, come with prt_hip_accum_import_moments
+    return PRT_HIP_OK;
+}
+
+// ---- adaptive sampling (include/prt_hip.h): the moment records, the selection and the compacted pixel list
+#define PRT_ADAPT_MAX_PACKETS (PRT_ACC_MAX_COUNT / 8u) // a moment record counts packets of 8 samples
+
+// Allocates the accumulator and the moment records at the camera's size and zeroes what is stale (on the context's stream).
+static int moments_ready(prt_hip_ctx* c)
+{
+    int rc = accum_ready(c);
+    if (rc) return rc;
+    const size_t n = c->accPixels;
+    if (c->momPixels != n) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); // the old records may still be in use
+        if (c->accMom) (void)hipFree(c->accMom);
+        c->accMom = nullptr;
+        c->momPixels = 0;
+        HIP_TRY(hipMalloc(&c->accMom, n * sizeof(float4)));
+        c->momPixels = n;
+        c->momClear = true;
+    }
+    if (c->momClear) {
+        HIP_TRY(hipMemsetAsync(c->accMom, 0, n * sizeof(float4), c->stream));
+        c->momClear = false;
+    }
+    return PRT_HIP_OK;
+}
+
+// The selection's per-item buffers for `items` work items (the list padded to a multiple of PRT_CHUNK), the compaction's scratch and
+// the active count with its pinned host copy.
+static int adapt_buffers(prt_hip_ctx* c, uint64_t items)
+{
+    if (!c->adCount) HIP_TRY(hipMalloc(&c->adCount, sizeof(uint32_t)));
+    if (!c->adCountHost) HIP_TRY(hipHostMalloc((void**)&c->adCountHost, sizeof(uint32_t), hipHostMallocDefault));
+    const size_t padded = (size_t)((items + PRT_CHUNK - 1) / PRT_CHUNK * PRT_CHUNK);
+    if (padded > c->adItems) {
+        HIP_TRY(hipStreamSynchronize(c->stream)); // the old buffers may still be in use
+        for (void* q : {(void*)c->adCode, (void*)c->adList, (void*)c->adFlag})
+            if (q) (void)hipFree(q);
+        c->adCode = c->adList = nullptr;
+        c->adFlag = nullptr;
+        c->adItems = 0;
+        HIP_TRY(hipMalloc(&c->adCode, padded * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->adList, padded * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&c->adFlag, padded * sizeof(uint8_t)));
+        c->adItems = padded;
+    }
+    size_t bytes = 0;
+    HIP_TRY(prt_select_flagged(nullptr, bytes, c->adCode, c->adFlag, c->adList, c->adCount, items, c->stream));
+    if (bytes > c->adTempBytes) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->adTemp) (void)hipFree(c->adTemp);
+        c->adTemp = nullptr;
+        c->adTempBytes = 0;
+        HIP_TRY(hipMalloc(&c->adTemp, bytes));
+        c->adTempBytes = bytes;
+    }
+    return PRT_HIP_OK;
+}
+
+static int check_floor(float floor, const char* who)
+{
+    if (!(floor > 0.0f) || std::isinf(floor)) return fail(PRT_HIP_EINVAL, std::string(who) + ": floor must be finite and > 0");
+    return PRT_HIP_OK;
+}
+
+int prt_hip_render_adaptive(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_render_params* p,
+                            const prt_adaptive_params* a, uint32_t* active, float* d_rgb, void* stream)
+{
+    if (!c || !p || !a || !active) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveScene || !c->haveCamera) return fail(PRT_HIP_ESTATE, "upload a scene and set a camera first");
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    if (p->tileSize == 0 || p->nranks == 0 || p->rank >= p->nranks) return fail(PRT_HIP_EINVAL, "bad render params");
+    if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
+        return fail(PRT_HIP_EINVAL, "adaptive: samples must be a multiple of 8 from 8 to 2040 per pass");
+    if (W > 65535 || H > 65535 || p->maxDepth > 255) return fail(PRT_HIP_EINVAL, "image or depth too large");
+    if (!(a->threshold >= 0.0f) || std::isinf(a->threshold)) return fail(PRT_HIP_EINVAL, "adaptive: threshold must be finite and >= 0");
+    int rc = check_floor(a->floor, "adaptive");
+    if (rc) return rc;
+    if (a->minSamples % 8 != 0 || a->maxSamples % 8 != 0)
+        return fail(PRT_HIP_EINVAL, "adaptive: minSamples and maxSamples must be multiples of 8");
+    if (a->minSamples > a->maxSamples) return fail(PRT_HIP_EINVAL, "adaptive: minSamples must not exceed maxSamples");
+    if (a->maxSamples > PRT_ACC_MAX_COUNT) return fail(PRT_HIP_EINVAL, "adaptive: maxSamples must not exceed 2^24");
+    if (c->accMax > 0 && !c->accClear && (p->seed != c->accSeed || p->maxDepth != c->accMaxDepth || p->rrDepth != c->accRrDepth))
+        return fail(PRT_HIP_EINVAL, "adaptive: seed, maxDepth and rrDepth must be those of the accumulated samples (reset the accumulator first)");
+    if ((rc = moments_ready(c))) return rc;
+    FrameLaunch F;
+    if ((rc = frame_setup(c, x0, y0, x1, y1, p, d_rgb, stream, F))) return rc;
+    if (F.totalWork >= (1ull << 31)) return fail(PRT_HIP_EINVAL, "adaptive: rectangle too large");
+    if ((rc = adapt_buffers(c, F.totalWork))) return rc;
+    hipStream_t s = F.s;
+    // ---- selection: flag the active items, resolve the others into d_rgb; then compact the active pixels' codes, in work-item order
+    uint32_t n = 0;
+    if (F.totalWork > 0) {
+        F.A.totalWork = (uint32_t)F.totalWork;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((F.totalWork + 255) / 256, (uint64_t)c->computeUnits * 8);
+        hipLaunchKernelGGL(adapt_select_kernel, dim3(blocks), dim3(256), 0, s, F.A, (const float4*)c->accSum, (const float4*)c->accMom, *a,
+                           c->adCode, c->adFlag);
+        hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string("adapt_select_kernel launch: ") + hipGetErrorString(le));
+        size_t bytes = c->adTempBytes;
+        HIP_TRY(prt_select_flagged(c->adTemp, bytes, c->adCode, c->adFlag, c->adList, c->adCount, F.totalWork, s));
+        HIP_TRY(hipMemcpyAsync(c->adCountHost, c->adCount, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s)); // the pass's one synchronisation: the launch is sized by the active count
+        n = *c->adCountHost;
+    }
+    *active = n;
+    if (n == 0) { // nothing to trace: the selection has written the whole image; the statistics count no rays
+        HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
+        return frame_finish(c, F);
+    }
+    // the list padded to whole rows with the "no pixel" code, so that a small launch spreads its rows (render_frame_kernel)
+    const uint64_t padded = ((uint64_t)n + PRT_CHUNK - 1) / PRT_CHUNK * PRT_CHUNK;
+    if (padded > n) HIP_TRY(hipMemsetAsync(c->adList + n, 0xff, (size_t)(padded - n) * sizeof(uint32_t), s));
+    if ((rc = frame_launch(c, F, padded, FRAME_ADAPT))) return rc;
+    // no pixel went above maxSamples: the bound stays tight enough for an adaptive run up to 2^24
+    c->accMax = std::min<uint32_t>(c->accMax + p->samples, std::max(c->accMax, a->maxSamples));
+    c->accSeed = p->seed;
+    c->accMaxDepth = p->maxDepth;
+    c->accRrDepth = p->rrDepth;
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_error(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, float exposure, float floor, float* err)
+{
+    if (!c || !err) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    int rc = check_floor(floor, "accum_error");
+    if (rc) return rc;
+    if ((rc = moments_ready(c))) return rc;
+    const uint32_t rw = x1 - x0 + 1, rh = y1 - y0 + 1;
+    const size_t n = (size_t)rw * rh;
+    if (n > 0xffffffffull) return fail(PRT_HIP_EINVAL, "rectangle too large");
+    if (n > c->adErrItems) { // the context keeps the buffer: a viewer may ask once per pass
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->adErr) (void)hipFree(c->adErr);
+        c->adErr = nullptr;
+        c->adErrItems = 0;
+        HIP_TRY(hipMalloc(&c->adErr, n * sizeof(float)));
+        c->adErrItems = n;
+    }
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->computeUnits * 8);
+    hipLaunchKernelGGL(accum_error_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->accSum, (const float4*)c->accMom, W, x0, y0,
+                       rw, rh, exposure, floor, c->adErr);
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string("accum_error_kernel launch: ") + hipGetErrorString(le));
+    std::vector<float> h(n);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(h.data(), c->adErr, n * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) err[(size_t)(x0 + i % rw) + (size_t)(y0 + i / rw) * W] = h[i];
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_export_moments(prt_hip_ctx* c, float* mom)
+{
+    if (!c || !mom) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    int rc = moments_ready(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(mom, c->accMom, c->momPixels * sizeof(float4), hipMemcpyDeviceToHost));
+    return PRT_HIP_OK;
+}
+
+int prt_hip_accum_import_moments(prt_hip_ctx* c, const float* mom)
+{
+    if (!c || !mom) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    const size_t n = (size_t)c->cam.width * c->cam.height;
+    std::vector<float4> rec(n);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t m;
+        memcpy(&m, &mom[4 * i + 2], sizeof(uint32_t));
+        if (m > PRT_ADAPT_MAX_PACKETS) return fail(PRT_HIP_EINVAL, "accum_import_moments: a packet count exceeds 2^21");
+        rec[i] = make_float4(mom[4 * i], mom[4 * i + 1], mom[4 * i + 2], 0.0f);
+    }
+    int rc = moments_ready(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(c->accMom, rec.data(), n * sizeof(float4), hipMemcpyHostToDevice));
     return PRT_HIP_OK;
 }
 
