@@ -280,6 +280,76 @@ int prt_hip_accum_error(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1,
 int prt_hip_accum_export_moments(prt_hip_ctx* ctx, float* mom);
 int prt_hip_accum_import_moments(prt_hip_ctx* ctx, const float* mom);
 
+/* ---- denoised previews: an edge-avoiding a-trous wavelet filter (B3 spline, 5x5 taps, hole size doubling per iteration) over the
+ * whole camera image of the accumulator, guided by first-hit albedo, first-hit normal and the variance of the moment records, with
+ * optional albedo demodulation.  A post-process: it reads the accumulator and the moments and changes neither.  It is specified
+ * exactly, so that a restatement in any language gives the same bits: all arithmetic is f32, no FMA, correctly rounded / and sqrtf,
+ * subnormals not flushed, in the order written.
+ *     lum(c) = 0.2126f*c.x + 0.7152f*c.y + 0.0722f*c.z                                  (left to right)
+ *     f(x):  y = 0.125f*x; r = 1.0f / ((1.0f + y) + (0.5f*y)*y); r = r*r; r = r*r; r = r*r;   result r
+ *            (the eighth power of the reciprocal of e^(x/8)'s series cut after the square: an exp(-x)-like falloff made of exactly
+ *            rounded operations only -- not expf, whose bits differ between libraries)
+ *     h[-2..2] = {1/16, 1/4, 3/8, 1/4, 1/16}
+ * Per pixel p:
+ *     valid_p = count_p > 0
+ *     A_p = albedo guide; G_p = normal guide in the G-buffer's encoding (0.5*n + 0.5 per hit, exactly (0,0,0) per miss, averaged
+ *           over the guide jitters);  N_p = (0,0,0) if G_p is exactly (0,0,0) (every jitter missed), else (G_p - 0.5f) * 2.0f per
+ *           component, NOT renormalised (a pixel straddling an edge has a short normal, hence a small wn to both sides)
+ *     c_p = sum_p / (float)count_p per channel
+ *     v_p = (M2 / (float)(m - 1)) / (float)(n >> 3) when m >= 2, else -1 ("unknown"): moment record {mean, M2, m}, n = count_p;
+ *           the variance of the pixel's mean luminance (se squared, see "adaptive sampling")
+ *     demodulate: d_p = max(A_p, 0.015625f) per channel; C0_p = c_p / d_p; V0_p = v_p < 0 ? -1 : v_p / (lum(d_p)*lum(d_p))
+ *     otherwise:  d_p = 1; C0_p = c_p; V0_p = v_p
+ * Iteration i = 0 .. iterations-1, step s = 1 << i, from planes (C, V) to (C', V').  For a valid p:
+ *     L_p = lum(C_p).  If V_p >= 0: g = the 3x3 average of V around p at stride 1, weights {1/16,1/8,1/16; 1/8,1/4,1/8; 1/16,1/8,1/16},
+ *         over the taps that are inside the image, valid and have V >= 0, row-major: g = sumVW / sumWt (sumVW += wt*V_q; sumWt += wt);
+ *         den = sigmaLuminance * sqrtf(g) + 1e-6f
+ *     taps q = p + s*(dx, dy), dy outer -2..2, dx inner -2..2; a tap outside the image or with !valid_q is skipped
+ *         q == p:  w = h[0]*h[0]
+ *         else     dn = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z; wn = max(dn, 0.0f); then wn = wn*wn, normalPowerLog2 times;
+ *                  da = A_p - A_q; wa = f(((da.x*da.x + da.y*da.y) + da.z*da.z) / (sigmaAlbedo*sigmaAlbedo));
+ *                  wl = V_p < 0 ? 1.0f : f(fabsf(L_p - lum(C_q)) / den);
+ *                  w = (((h[dy]*h[dx]) * wn) * wa) * wl
+ *         sumW += w; sumC += w * C_q per channel; if V_p >= 0: sumV += (w*w) * (V_q >= 0 ? V_q : V_p)
+ *     C'_p = sumC / sumW per channel; V'_p = V_p < 0 ? -1 : sumV / (sumW*sumW)
+ * An invalid p: C'_p = 0, V'_p = -1.
+ * Output: d_rgb_p = exposure * (C_final_p * d_p) per channel; +0.0 for an invalid p.
+ * What follows from these rules: a pixel all of whose guide jitters missed (background) only ever keeps its own value, since every
+ * wn to or from it is 0.  The filter is BIASED where the guides cannot see an edge that the radiance has, most visibly around
+ * directly seen emitters, whose HDR edge pixels dominate the absolute error once the noise is low: it is a preview filter for low
+ * sample counts, not a substitute for convergence.  A pixel whose variance is unknown gets no luminance edge-stopping; a host
+ * that wants it renders with adaptive passes (with minSamples at the target count every pixel below it is active whatever its
+ * error: an accumulate pass that also keeps moments).  There is no depth or position guide.  In a multi-rank run it works on
+ * whatever this context's accumulator holds: pixels the rank does not own (count 0) stay +0.
+ *
+ * Guides: the context owns two camera-sized planes, albedo and normal.  Each is the average of K = guideSamples launches of the
+ * G-buffer kernel (prt_hip_render_gbuffer type 0, respectively type 2, exposure 1; launch k = 0..K-1 with seed boundSeed + k, uint32
+ * wrap-around, boundSeed = the accumulator's bound seed): g = g_0; g = g + g_k (k = 1..K-1); g = g * (1.0f / K), per float.  They
+ * are rendered by the first denoise (or prt_hip_denoise_get_guides) after they became stale: prt_hip_set_camera,
+ * prt_hip_upload_scene, another bound seed and another K make them stale (the first two also drop planes the host had set).
+ * Rendering them is a G-buffer render for prt_hip_get_stats: read a pass's statistics before denoising it. ---- */
+typedef struct {
+    uint32_t iterations;      /* 1..5 */
+    uint32_t normalPowerLog2; /* 0..7: wn is raised to 2^normalPowerLog2 */
+    float sigmaLuminance;     /* > 0, finite */
+    float sigmaAlbedo;        /* > 0, finite */
+    uint32_t demodulate;      /* 0 or 1 */
+    uint32_t guideSamples;    /* K: 1, 2, 4, 8 or 16 */
+} prt_denoise_params;
+/* The host's own guide planes (host pointers, 3*width*height floats each, pixel (x,y) at (x + y*width)*3; taken at the camera's size
+ * on trust); NULL, NULL returns to the library's own.  Synchronous. */
+int prt_hip_denoise_set_guides(prt_hip_ctx* ctx, const float* albedo, const float* normal);
+/* The planes a denoise with this K uses, to host arrays: renders them if stale; the host's own if set.  Synchronous.
+ * PRT_HIP_ESTATE without scene / camera, or with an empty accumulator (no bound seed) unless the host's planes are set. */
+int prt_hip_denoise_get_guides(prt_hip_ctx* ctx, uint32_t guideSamples, float* albedo, float* normal);
+/* Filters the whole image into d_rgb (d_rgb / stream rules of prt_hip_accum_resolve; asynchronous).  PRT_HIP_EINVAL with a message
+ * for a parameter outside its range or a non-finite sigma; PRT_HIP_ESTATE without scene / camera or with an empty (never bound)
+ * accumulator.  Scratch planes (88 bytes per pixel) are allocated at the camera's size on first use and freed with the context. */
+int prt_hip_accum_denoise(prt_hip_ctx* ctx, const prt_denoise_params* params, float exposure, float* d_rgb, void* stream);
+/* V_final of the last denoise into a host array of width*height floats (-1 = unknown or invalid): the variance of the filtered
+ * luminance (demodulated if the denoise was).  Synchronous; PRT_HIP_ESTATE when this view has not been denoised. */
+int prt_hip_denoise_variance(prt_hip_ctx* ctx, float* var);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,14 @@ int prt_hip_test_powf(prt_hip_ctx* ctx, uint32_t n, const float* x, float* y);
 /* Camera::GenerateJitteredRayPacket + Random on the device: out = 8 x {org[3] dir[3] invDir[3] swapXZ swapYZ},
  * avgDir[3], state after (as float bits) = 92 floats */
 int prt_hip_test_camera(prt_hip_ctx* ctx, uint32_t x, uint32_t y, uint32_t state, float* out92);
+/* tools/denoise_bench.py: prt_hip_accum_denoise into the context's framebuffer twice, timed with HIP events; ms[0] = the prepare
+ * kernel, ms[1..5] = the iterations (0 beyond params->iterations) of the second run, ms[6] = the whole first run (no events
+ * inside).  Synchronous. */
+int prt_hip_test_denoise_profile(prt_hip_ctx* ctx, const prt_denoise_params* params, float exposure, float* ms7);
+/* the yardstick of the same tool: one launch (after a warm-up launch) of a plain copy kernel in which every thread reads one element
+ * of read16 16-byte planes and read12 12-byte planes and writes one of write16 16-byte and write12 12-byte planes of `pixels`
+ * elements, in buffers of its own; *ms = its time */
+int prt_hip_test_copy_yardstick(prt_hip_ctx* ctx, uint64_t pixels, int read16, int read12, int write16, int write12, float* ms);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,11 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("normalPowerLog2", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaAlbedo", C.c_float),
+                ("demodulate", C.c_uint32), ("guideSamples", C.c_uint32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -116,6 +121,7 @@ EXPORTS = [
     "prt_hip_build_bvh", "prt_hip_comm_unique_id", "prt_hip_comm_init", "prt_hip_comm_adopt", "prt_hip_comm_destroy", "prt_hip_gather_rccl", "prt_hip_gather_payload_bytes",
     "prt_hip_get_stats", "prt_hip_accum_reset", "prt_hip_render_accumulate", "prt_hip_accum_resolve", "prt_hip_accum_export",
     "prt_hip_accum_import", "prt_hip_render_adaptive", "prt_hip_accum_error", "prt_hip_accum_export_moments", "prt_hip_accum_import_moments",
+    "prt_hip_denoise_set_guides", "prt_hip_denoise_get_guides", "prt_hip_accum_denoise", "prt_hip_denoise_variance",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
@@ -124,7 +130,8 @@ EXPORTS = [
 ]
 
 # include/prt_hip_test.h: row-level entry points of the TEST build of the library (libprt_hip_test.so); the product does not export them
-TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera"]
+TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
+                "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -202,12 +209,18 @@ def _load(path, with_test_entry_points):
     L.prt_hip_accum_error.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, vp]
     L.prt_hip_accum_export_moments.argtypes = [vp, vp]
     L.prt_hip_accum_import_moments.argtypes = [vp, vp]
+    L.prt_hip_denoise_set_guides.argtypes = [vp, vp, vp]
+    L.prt_hip_denoise_get_guides.argtypes = [vp, C.c_uint32, vp, vp]
+    L.prt_hip_accum_denoise.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float, vp, vp]
+    L.prt_hip_denoise_variance.argtypes = [vp, vp]
     if with_test_entry_points:
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
         L.prt_hip_test_sincos.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.prt_hip_test_powf.argtypes = [vp, C.c_uint32, vp, vp]
         L.prt_hip_test_camera.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.prt_hip_test_denoise_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float, vp]
+        L.prt_hip_test_copy_yardstick.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     for n in ("prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
               "prt_host_mesh_atrium", "prt_host_scene_create"):
         getattr(L, n).restype = vp
@@ -636,6 +649,58 @@ class PathTracer:
         if len(a) != 4 * W * H:
             raise PrtError(f"accum_import_moments: {len(a)} floats do not match the camera's {W}x{H} pixels (4 per pixel)")
         self._chk(self._L.prt_hip_accum_import_moments(self._ctx, a.ctypes.data_as(C.c_void_p)), "prt_hip_accum_import_moments")
+
+    # ---- denoised previews (include/prt_hip.h "denoised previews"): an a-trous filter over the accumulator's image, guided by first-hit
+    # albedo and normal and by the variance of the moments; it reads the accumulator and changes nothing
+    @staticmethod
+    def denoise_params(iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True, guide_samples=8):
+        return DenoiseParams(iterations, normal_power_log2, sigma_luminance, sigma_albedo, int(demodulate), guide_samples)
+
+    def denoise_async(self, iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True, guide_samples=8,
+                      exposure=1.0, d_rgb=None, stream=None):
+        """Queue the filter over the whole image; d_rgb = device pointer (int) or None for the context's framebuffer."""
+        p = self.denoise_params(iterations, normal_power_log2, sigma_luminance, sigma_albedo, demodulate, guide_samples)
+        self._chk(self._L.prt_hip_accum_denoise(self._ctx, C.byref(p), exposure, d_rgb, stream), "prt_hip_accum_denoise")
+
+    def denoise(self, iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True, guide_samples=8,
+                exposure=1.0):
+        """The denoised image of the accumulator as (H, W, 3) float32 (+0 where nothing was rendered)."""
+        self.denoise_async(iterations, normal_power_log2, sigma_luminance, sigma_albedo, demodulate, guide_samples, exposure)
+        W, H = self._camera.width, self._camera.height
+        return self._download_rect(0, 0, W - 1, H - 1, stats=False)
+
+    def denoise_guides(self, guide_samples=8):
+        """(albedo, normal), each (H, W, 3) float32: the guide planes a denoise with this guide_samples uses (rendered if stale; the
+        host's own if set_denoise_guides set them)."""
+        W, H = self._camera.width, self._camera.height
+        albedo = np.zeros((H, W, 3), dtype=np.float32)
+        normal = np.zeros((H, W, 3), dtype=np.float32)
+        self._chk(self._L.prt_hip_denoise_get_guides(self._ctx, guide_samples, albedo.ctypes.data_as(C.c_void_p),
+                                                     normal.ctypes.data_as(C.c_void_p)), "prt_hip_denoise_get_guides")
+        return albedo, normal
+
+    def set_denoise_guides(self, albedo, normal):
+        """Supply the guide planes ((H, W, 3) each: albedo, and the normal as 0.5*n + 0.5 with (0, 0, 0) for a miss); None, None returns
+        to the library's own."""
+        if albedo is None and normal is None:
+            self._chk(self._L.prt_hip_denoise_set_guides(self._ctx, None, None), "prt_hip_denoise_set_guides")
+            return
+        if albedo is None or normal is None:
+            raise PrtError("set_denoise_guides: both planes or neither")
+        W, H = self._camera.width, self._camera.height
+        a = np.ascontiguousarray(albedo, dtype=np.float32)
+        n = np.ascontiguousarray(normal, dtype=np.float32)
+        if a.shape != (H, W, 3) or n.shape != (H, W, 3):
+            raise PrtError(f"set_denoise_guides: planes of shape {a.shape} and {n.shape} do not match the camera's ({H}, {W}, 3)")
+        self._chk(self._L.prt_hip_denoise_set_guides(self._ctx, a.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p)),
+                  "prt_hip_denoise_set_guides")
+
+    def denoise_variance(self):
+        """(H, W) float32: the filtered variance V_final of the last denoise (-1 where unknown or nothing was rendered)."""
+        W, H = self._camera.width, self._camera.height
+        var = np.zeros((H, W), dtype=np.float32)
+        self._chk(self._L.prt_hip_denoise_variance(self._ctx, var.ctypes.data_as(C.c_void_p)), "prt_hip_denoise_variance")
+        return var
 
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""

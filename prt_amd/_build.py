@@ -14,6 +14,7 @@ SOURCES = [
     "prt_gather.hip",
     "prt_bvh_build.hip",
     "prt_select.hip",
+    "prt_denoise.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

@@ -96,6 +96,17 @@ struct prt_hip_ctx {
     uint32_t* adCountHost = nullptr; // pinned host copy of it
     float* adErr = nullptr;          // prt_hip_accum_error: the rectangle's errors (device)
     size_t adErrItems = 0;
+    // denoised previews (prt_denoise.hip): guide and scratch planes at the camera's size, allocated on first use
+    float* dnAlbedo = nullptr;   // guide planes, 3 floats per pixel: the average of dnGuideK G-buffer launches, or the host's own
+    float* dnNormal = nullptr;
+    float4* dnGuideA = nullptr;  // packed for the taps: {A.xyz, valid ? 1 : 0}
+    float4* dnGuideN = nullptr;  // {N.xyz, 0}
+    float4* dnPlane[2] = {nullptr, nullptr}; // ping-pong {C.xyz, V}
+    size_t dnPixels = 0;         // pixels all of them hold
+    bool dnGuidesValid = false;  // dnAlbedo / dnNormal hold the library's guides for (dnGuideSeed, dnGuideK) and the current view
+    bool dnHostGuides = false;   // dnAlbedo / dnNormal hold planes the host supplied (prt_hip_denoise_set_guides)
+    uint32_t dnGuideSeed = 0, dnGuideK = 0;
+    int dnLast = -1;             // dnPlane[dnLast].w is V_final of the last denoise (-1: none yet)
 };
 
 
@@ -104,6 +115,9 @@ void prt_gather_release(prt_hip_ctx* c);
 // prt_kernels.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
 // stream must be idle); `clear` consumes it (prt_hip_get_stats), download / gather only report it
 int prt_sticky_error(prt_hip_ctx* c, bool clear);
+// prt_denoise.hip: the view or the scene changed (guides of either origin are dropped); frees the planes
+void prt_denoise_forget(prt_hip_ctx* c);
+void prt_denoise_release(prt_hip_ctx* c);
 // prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
 // temp == nullptr it only sets tempBytes
 hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,

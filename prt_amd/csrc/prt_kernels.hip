@@ -493,6 +493,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->adCount) (void)hipFree(c->adCount);
     if (c->adErr) (void)hipFree(c->adErr);
     if (c->adCountHost) (void)hipHostFree(c->adCountHost);
+    prt_denoise_release(c);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -576,6 +577,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     HIP_TRY(hipSetDevice(c->device));
     free_scene(c);
     accum_forget(c); // the accumulated samples were of the old scene
+    prt_denoise_forget(c);
 
     std::vector<float4> wnodes, shade, bump, mats, alpha;
     std::vector<float> tris;                 // 9 floats per triangle, leaf order
@@ -888,6 +890,7 @@ int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
     memcpy(&c->cam, cam, sizeof(DevCamera));
     c->haveCamera = true;
     accum_forget(c); // of another view (and perhaps another size)
+    prt_denoise_forget(c);
     return PRT_HIP_OK;
 }
 

@@ -1,0 +1,358 @@
+"""Denoised previews on the MI355X (include/prt_hip.h "denoised previews").  The filter is specified exactly in float32, so every
+comparison below is at tolerance 0 against the numpy restatement of the header (prt_denoise_ref): the image and the filtered
+variance, on synthetic state (imported accumulator, moments and guides) and on rendered state.  Only the last test is about
+quality: at 16 samples per pixel the denoised image is closer to a converged render than the undenoised one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import prt_amd
+import prt_denoise_ref as R
+import prt_testlib as T
+
+pytestmark = pytest.mark.gpu
+DEFAULTS = dict(iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_bits_equal(a, b, what=""):
+    a, b = bits(a), bits(b)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    bad = np.nonzero(a != b)
+    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
+
+
+@pytest.fixture(scope="module")
+def tracer():
+    prt_amd.build()
+    t = prt_amd.PathTracer()
+    yield t
+    t.close()
+
+
+@pytest.fixture(scope="module")
+def box_scene():
+    return prt_amd.setup_cornell_box(64, 64)[0]
+
+
+def camera_of(width, height):
+    return prt_amd.setup_cornell_box(width, height)[1]
+
+
+def synthetic_state(width, height, seed):
+    """Random accumulator, moments and guides with every special case of the header in them: count 0, m < 2, miss normals, zero
+    variance, albedo 0, radiance from 1e-6 to 1e3 (HDR emitters next to dark walls)."""
+    rng = np.random.default_rng(seed)
+    shape = (height, width)
+    count = (rng.integers(1, 9, shape) * 8).astype(np.uint32)
+    count[rng.random(shape) < 0.15] = 0
+    count[0, 0] = 8  # (an import whose counts are all 0 leaves the accumulator empty, which is a refusal)
+    mean = (rng.random(shape + (3,)) * 10.0 ** rng.uniform(-6, 3, shape + (1,))).astype(np.float32)
+    total = (mean * count[..., None].astype(np.float32)).astype(np.float32)
+    m = np.minimum(rng.integers(0, 9, shape), count >> 3).astype(np.uint32)  # a share with m = 0 or 1: variance unknown
+    mom = np.zeros(shape + (4,), np.float32)
+    lum = R.lum(mean)
+    mom[..., 0] = lum
+    mom[..., 1] = (lum * lum * rng.random(shape) * 4.0).astype(np.float32)
+    mom[..., 1][rng.random(shape) < 0.1] = 0.0  # zero variance
+    mom[..., 2] = m.view(np.float32)
+    albedo = rng.random(shape + (3,)).astype(np.float32)
+    albedo[rng.random(shape) < 0.1] = 0.0
+    # guides that make regions, so that the weights are not all ~0: a few albedos and normals, blockwise, plus jitter
+    by, bx = np.meshgrid(np.arange(height) // 7, np.arange(width) // 5, indexing="ij")
+    palette = rng.random((8, 3)).astype(np.float32)
+    region = (by * 3 + bx) % 8
+    albedo = np.where(rng.random(shape)[..., None] < 0.7, palette[region] + rng.normal(0, 0.01, shape + (3,)).astype(np.float32), albedo)
+    albedo = np.abs(albedo).astype(np.float32)
+    albedo[rng.random(shape) < 0.05] = 0.0
+    n = rng.normal(size=(8, 3))
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    nn = n[(by + bx) % 8] + rng.normal(0, 0.05, shape + (3,))
+    nn *= rng.uniform(0.3, 1.0, shape + (1,)) / np.linalg.norm(nn, axis=-1, keepdims=True)  # averaged guide normals are short, never long
+    normal = (0.5 * nn + 0.5).astype(np.float32)
+    normal[rng.random(shape) < 0.1] = 0.0  # misses
+    state = dict(width=width, height=height, seed=12345, max_depth=14, rr_depth=4, rng=rng.integers(0, 2 ** 32, shape, dtype=np.uint32),
+                 sum=total, count=count)
+    return state, mom, albedo, normal
+
+
+def load_synthetic(t, scene, width, height, seed):
+    t.upload_scene(scene)
+    t.set_camera(camera_of(width, height))
+    state, mom, albedo, normal = synthetic_state(width, height, seed)
+    t.accum_import(state)
+    t.accum_import_moments(mom)
+    t.set_denoise_guides(albedo, normal)
+    return state, mom, albedo, normal
+
+
+def check(t, state, mom, albedo, normal, exposure=1.0, what="", **kw):
+    p = dict(DEFAULTS, **kw)
+    img = t.denoise(exposure=exposure, **p)
+    var = t.denoise_variance()
+    want, want_var = R.denoise(state["sum"], state["count"], mom, albedo, normal, exposure=exposure, **p)
+    assert_bits_equal(img, want, f"{what} {kw}: image")
+    assert_bits_equal(var, want_var, f"{what} {kw}: variance")
+    return img
+
+
+@pytest.mark.parametrize("size", [(97, 61), (33, 200), (1, 1), (5, 3)])
+def test_synthetic_state_matches_the_restatement(tracer, box_scene, size):
+    w, h = size
+    s = load_synthetic(tracer, box_scene, w, h, seed=w * 1000 + h)
+    assert (s[0]["count"] == 0).any() or w * h < 10
+    for iterations in (1, 2, 3, 4, 5):
+        for demodulate in (False, True):
+            for power in (0, 7):
+                check(tracer, *s, exposure=1.0 if demodulate else 0.75, what=f"{w}x{h}", iterations=iterations, demodulate=demodulate,
+                      normal_power_log2=power)
+    check(tracer, *s, what=f"{w}x{h} defaults")
+    check(tracer, *s, what=f"{w}x{h} sigmas", sigma_luminance=0.5, sigma_albedo=2.0, normal_power_log2=3)
+
+
+def test_synthetic_state_1080p(tracer, box_scene):
+    s = load_synthetic(tracer, box_scene, 1920, 1080, seed=77)
+    check(tracer, *s, what="1920x1080")
+    check(tracer, *s, what="1920x1080", iterations=3, demodulate=False, normal_power_log2=7, exposure=2.0)
+
+
+def test_all_variances_unknown_without_moments(tracer, box_scene):
+    """An imported accumulator without imported moments: the moment records are zero, every V is -1."""
+    tracer.upload_scene(box_scene)
+    tracer.set_camera(camera_of(40, 30))
+    state, mom, albedo, normal = synthetic_state(40, 30, 5)
+    tracer.accum_import(state)
+    tracer.set_denoise_guides(albedo, normal)
+    check(tracer, state, np.zeros_like(mom), albedo, normal, what="no moments")
+    assert (tracer.denoise_variance() == -1).all()
+
+
+def rendered(t, scene, camera, adaptive, spp=64, step=16, **kw):
+    t.upload_scene(scene)
+    t.set_camera(camera)
+    for _ in range(spp // step):
+        if adaptive:
+            t.adaptive_pass(step, 0.0, spp, spp, 0.01, **kw)
+        else:
+            t.accumulate(step, **kw)
+    return t.accum_export(), t.accum_export_moments()
+
+
+@pytest.fixture(scope="module")
+def c1_scene():
+    return prt_amd.setup_cornell_box(256, 256, teapot_mesh=T.teapot_product_mesh())
+
+
+def test_rendered_state_adaptive(tracer, c1_scene):
+    scene, camera, exposure = c1_scene
+    state, mom = rendered(tracer, scene, camera, adaptive=True)
+    assert (state["count"] == 64).all() and (mom[..., 2].view(np.uint32) == 8).all()
+    albedo, normal = tracer.denoise_guides()
+    img = check(tracer, state, mom, albedo, normal, exposure=exposure, what="cornell adaptive")
+    assert np.isfinite(img).all() and (tracer.denoise_variance() >= 0).all()
+    check(tracer, state, mom, albedo, normal, what="cornell adaptive", demodulate=False, iterations=2)
+
+
+def test_rendered_state_accumulate(tracer, c1_scene):
+    scene, camera, exposure = c1_scene
+    state, mom = rendered(tracer, scene, camera, adaptive=False)
+    assert (mom == 0).all()
+    albedo, normal = tracer.denoise_guides()
+    check(tracer, state, mom, albedo, normal, exposure=exposure, what="cornell accumulate")
+    assert (tracer.denoise_variance() == -1).all()
+
+
+def env_scene():
+    scene, camera, _ = prt_amd.setup_cornell_box(128, 128, teapot_mesh=T.teapot_product_mesh())
+    scene.set_infinite_area_light(T.sky_env(48, 24, black_rows=True))
+    return scene, camera
+
+
+def test_rendered_state_env_light(tracer):
+    scene, camera = env_scene()
+    state, mom = rendered(tracer, scene, camera, adaptive=True, spp=32, step=8, max_depth=8)
+    albedo, normal = tracer.denoise_guides()
+    check(tracer, state, mom, albedo, normal, what="env light")
+
+
+@pytest.mark.parametrize("k", [1, 4, 8])
+def test_guides_are_the_average_of_gbuffer_launches(tracer, c1_scene, k):
+    scene, camera, _ = c1_scene
+    rendered(tracer, scene, camera, adaptive=True, spp=8, step=8)
+    albedo, normal = tracer.denoise_guides(k)
+    seed = tracer.seed
+    try:
+        planes = {0: [], 2: []}
+        for j in range(k):
+            tracer.seed = seed + j
+            for kind in planes:
+                planes[kind].append(tracer.gbuffer(kind))
+    finally:
+        tracer.seed = seed
+    assert_bits_equal(albedo, R.guide_average(planes[0]), f"albedo guide, K = {k}")
+    assert_bits_equal(normal, R.guide_average(planes[2]), f"normal guide, K = {k}")
+    if k == 1:
+        assert_bits_equal(albedo, planes[0][0], "K = 1 is gbuffer itself")
+
+
+def test_denoise_is_a_pure_read(tracer, c1_scene):
+    scene, camera, exposure = c1_scene
+    tracer.upload_scene(scene)
+    tracer.set_camera(camera)
+    before_render = tracer.render(16)
+    tracer.adaptive_pass(16, 0.0, 32, 32, 0.01)
+    tracer.adaptive_pass(16, 0.0, 32, 32, 0.01)
+    state, mom, resolve = tracer.accum_export(), tracer.accum_export_moments(), tracer.accum_resolve(exposure)
+    tracer.denoise(exposure=exposure)
+    after, mom_after = tracer.accum_export(), tracer.accum_export_moments()
+    for key in ("rng", "count", "seed", "max_depth", "rr_depth"):
+        assert np.array_equal(state[key], after[key]), key
+    assert_bits_equal(state["sum"], after["sum"], "sums")
+    assert_bits_equal(mom, mom_after, "moments")
+    assert_bits_equal(resolve, tracer.accum_resolve(exposure), "resolve")
+    assert_bits_equal(before_render, tracer.render(16), "render after a denoise")
+    # and the accumulator continues as if the denoise had not happened
+    img = tracer.accumulate(8)
+    tracer.accum_reset()
+    tracer.accumulate(32)
+    assert_bits_equal(img, tracer.accumulate(8), "continued accumulation")
+
+
+def test_guides_go_stale(tracer, c1_scene):
+    scene, camera, _ = c1_scene
+    rendered(tracer, scene, camera, adaptive=True, spp=8, step=8)
+    first = tracer.denoise_guides(1)
+    scene2, camera2 = env_scene()
+    tracer.upload_scene(scene2)
+    tracer.set_camera(camera2)
+    tracer.accumulate(8, max_depth=8)
+    a, n = tracer.denoise_guides(1)
+    assert_bits_equal(a, tracer.gbuffer(0), "albedo after upload_scene + set_camera")
+    assert_bits_equal(n, tracer.gbuffer(2), "normal after upload_scene + set_camera")
+    # same size, other view
+    cam3 = prt_amd.Camera().create((0.3, 1.1, 2.4), (-0.1, -0.05, -1.0), 128, 128)
+    tracer.set_camera(cam3)
+    tracer.accumulate(8, max_depth=8)
+    a3, n3 = tracer.denoise_guides(1)
+    assert_bits_equal(a3, tracer.gbuffer(0), "albedo after set_camera")
+    assert (bits(a3) != bits(a)).any()
+    # the host's own, and back
+    mine_a, mine_n = np.full((128, 128, 3), 0.25, np.float32), np.full((128, 128, 3), 0.75, np.float32)
+    tracer.set_denoise_guides(mine_a, mine_n)
+    got = tracer.denoise_guides(4)
+    assert_bits_equal(got[0], mine_a, "host albedo")
+    assert_bits_equal(got[1], mine_n, "host normal")
+    state, mom = tracer.accum_export(), tracer.accum_export_moments()
+    check(tracer, state, mom, mine_a, mine_n, what="host guides")
+    tracer.set_denoise_guides(None, None)
+    back = tracer.denoise_guides(1)
+    assert_bits_equal(back[0], a3, "library albedo again")
+    assert_bits_equal(back[1], n3, "library normal again")
+    check(tracer, state, mom, *tracer.denoise_guides(8), what="library guides again")
+    with pytest.raises(prt_amd.PrtError, match="shape"):
+        tracer.set_denoise_guides(mine_a[:64], mine_n)
+    assert first[0].shape == (256, 256, 3)
+
+
+def test_explicit_target_on_a_callers_stream(tracer, box_scene):
+    s = load_synthetic(tracer, box_scene, 97, 61, seed=3)
+    want, _ = R.denoise(s[0]["sum"], s[0]["count"], s[1], s[2], s[3], **DEFAULTS)
+    tracer.accum_resolve(1.0)
+    fb_before = np.zeros((61, 97, 3), np.float32)
+    tracer._download(fb_before, 0, 0, 96, 60)
+    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
+    nbytes = 61 * 97 * 3 * 4
+    stream, target = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
+    try:
+        assert hip.hipMemsetAsync(target, 0xff, C.c_size_t(nbytes), stream) == 0
+        tracer.denoise_async(d_rgb=target.value, stream=stream.value, **DEFAULTS)
+        got = np.zeros((61, 97, 3), np.float32)
+        # queued on the caller's stream only: the result must be there when that stream gets to the copy
+        assert hip.hipMemcpyAsync(got.ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
+        assert hip.hipStreamSynchronize(stream) == 0
+    finally:
+        hip.hipFree(target)
+        hip.hipStreamDestroy(stream)
+    assert_bits_equal(got, want, "caller's buffer")
+    fb_after = np.zeros((61, 97, 3), np.float32)
+    tracer._download(fb_after, 0, 0, 96, 60)
+    assert_bits_equal(fb_after, fb_before, "the context's framebuffer")
+
+
+def test_refusals(tracer, box_scene):
+    EINVAL, ESTATE = "(-2)", "(-5)"
+    load_synthetic(tracer, box_scene, 16, 16, seed=1)
+    bad = [dict(iterations=0), dict(iterations=6), dict(normal_power_log2=8), dict(sigma_luminance=0.0), dict(sigma_luminance=-1.0),
+           dict(sigma_luminance=float("inf")), dict(sigma_luminance=float("nan")), dict(sigma_albedo=0.0), dict(sigma_albedo=float("nan")),
+           dict(sigma_albedo=float("inf")), dict(guide_samples=0), dict(guide_samples=3), dict(guide_samples=32)]
+    for kw in bad:
+        with pytest.raises(prt_amd.PrtError) as e:
+            tracer.denoise(**dict(DEFAULTS, **kw))
+        assert EINVAL in str(e.value) and "denoise" in str(e.value), (kw, str(e.value))
+    p = tracer.denoise_params()
+    p.demodulate = 2
+    assert tracer._L.prt_hip_accum_denoise(tracer._ctx, C.byref(p), 1.0, None, None) == -2
+    assert b"demodulate" in tracer._L.prt_hip_last_error()
+    with pytest.raises(prt_amd.PrtError, match="guideSamples"):
+        tracer.denoise_guides(5)
+    tracer.denoise()  # the state itself is fine
+    tracer.accum_reset()
+    with pytest.raises(prt_amd.PrtError) as e:
+        tracer.denoise()
+    assert ESTATE in str(e.value) and "empty" in str(e.value)
+    fresh = prt_amd.PathTracer()
+    try:
+        with pytest.raises(prt_amd.PrtError) as e:
+            fresh.denoise_async()
+        assert ESTATE in str(e.value)
+        fresh.upload_scene(box_scene)
+        fresh.set_camera(camera_of(16, 16))
+        with pytest.raises(prt_amd.PrtError) as e:
+            fresh.denoise()
+        assert ESTATE in str(e.value) and "empty" in str(e.value)
+        with pytest.raises(prt_amd.PrtError) as e:
+            fresh.denoise_variance()
+        assert ESTATE in str(e.value)
+    finally:
+        fresh.close()
+
+
+def error_ratios(img, noisy, ref):
+    """(a) mean squared error, (b) mean of |x - ref|^2 / (|ref|^2 + 0.01) per pixel, (c) median absolute error: denoised / noisy."""
+    def figures(x):
+        d = x.astype(np.float64) - ref
+        sq = (d * d).sum(-1)
+        return sq.mean(), (sq / ((ref * ref).sum(-1) + 0.01)).mean(), np.median(np.abs(d))
+    return tuple(a / b for a, b in zip(figures(img), figures(noisy)))
+
+
+def test_it_helps_at_16_spp(tracer):
+    """Cornell box with teapot, 128x128, against a 1024-spp render: after two 8-spp adaptive passes (every pixel traced twice, two
+    packets per pixel) the denoised image has a smaller mean squared error and a smaller relative error than the undenoised resolve.
+    Ratio < 1 is the whole condition; the figures are printed (the CPU prototype of the filter's design gave 0.40 and 0.085; on
+    the MI355X: 0.395 and 0.085, without demodulation 0.362 and 0.090).  The 64-spp rows are recorded without a condition: there the
+    mean squared error is 1.258 of the undenoised one with demodulation (0.731 without) -- the emitter-edge bias the header names --
+    while the relative error is 0.116."""
+    scene, camera, exposure = prt_amd.setup_cornell_box(128, 128, teapot_mesh=T.teapot_product_mesh())
+    tracer.upload_scene(scene)
+    tracer.set_camera(camera)
+    ref = tracer.render(1024, exposure=exposure).astype(np.float64)
+    tracer.accum_reset()
+    rows = {}
+    for spp in (16, 64):
+        while int(tracer.accum_counts().max()) < spp:
+            tracer.adaptive_pass(8, 0.0, spp, spp, 0.01, exposure=exposure)
+        assert (tracer.accum_counts() == spp).all()
+        noisy = tracer.accum_resolve(exposure)
+        for demodulate in (True, False):
+            img = tracer.denoise(exposure=exposure, **dict(DEFAULTS, demodulate=demodulate))
+            rows[spp, demodulate] = error_ratios(img, noisy, ref)
+            print(f"denoised / undenoised at {spp} spp, demodulate {int(demodulate)}: mse {rows[spp, demodulate][0]:.3f}, "
+                  f"relative {rows[spp, demodulate][1]:.3f}, median abs {rows[spp, demodulate][2]:.3f}")
+    mse, rel, _ = rows[16, True]
+    assert mse < 1.0 and rel < 1.0, rows
