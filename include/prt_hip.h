@@ -350,6 +350,108 @@ int prt_hip_accum_denoise(prt_hip_ctx* ctx, const prt_denoise_params* params, fl
  * luminance (demodulated if the denoise was).  Synchronous; PRT_HIP_ESTATE when this view has not been denoised. */
 int prt_hip_denoise_variance(prt_hip_ctx* ctx, float* var);
 
+/* ---- temporal reprojection: denoised previews that survive camera moves.  What was learnt in the last view is carried into the next
+ * one wherever the same surface is still visible: the temporal stage of SVGF in front of the a-trous filter above.  It needs a
+ * first-hit POSITION per pixel, which is the guide that filter lacks.  A post-process like the denoiser: it reads the accumulator and
+ * the moments and changes neither, and prt_hip_accum_denoise ignores everything below and gives the bits it always gave.  All new
+ * arithmetic is specified exactly, as for the filter: f32, no FMA, correctly rounded / and sqrtf, subnormals kept, in the order
+ * written.  dot3(u, w) = (u.x*w.x + u.y*w.y) + u.z*w.z.
+ *
+ * Position guide: one ray per pixel (x, y) through the pixel's CENTRE -- camera_dir (camera.cpp:46-56) with both jitter terms 0.0f:
+ *     kAspect = (float)W / (float)H
+ *     nx = 2.0f * ((float)x * invWidth - 0.5f + 0.0f) * 0.6f * kAspect                   (left to right)
+ *     ny = -2.0f * ((float)y * invHeight - 0.5f + 0.0f) * 0.6f
+ *     v = (nx*right + ny*up) + dir per component
+ *     dirp = (1.0f / sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z)) * v
+ * from pos with maxT = 100000.0f through the single-ray nearest-hit traversal: the G-buffer kernel's ray, alpha tests included,
+ * without the jitter.  The plane holds {X.x, X.y, X.z, t} per pixel at (x + y*width)*4: for a hit X = pos + t*dirp per component
+ * (the product is rounded, then the sum); a miss is {0, 0, 0, -1}.  It is a function of scene and camera only: rendered on first
+ * use per view by one launch of a persistent traversal kernel with neither surface fetch nor texture tap, stale after
+ * prt_hip_set_camera / prt_hip_upload_scene (which also drop a plane the host had set).  Rendering it is a G-buffer render for
+ * prt_hip_get_stats (a stack overflow is reported there, as for prt_hip_render_gbuffer): read a pass's statistics first.
+ *
+ * Records: the context keeps a HISTORY and a PENDING record, each a camera plus three camera-sized float4 planes
+ * {hC.xyz, hV}, {hX.xyz, hLen}, {hN.xyz, 0}: hC is radiance (sum / count, not demodulated, no exposure), hV the variance of its mean
+ * luminance (-1 = unknown), hLen the number of samples it stands for, as a float (0 = nothing), hX and hN the position guide and
+ * the guide normal N of that view.
+ *
+ * prt_hip_accum_denoise_temporal does, per pixel p = (x, y), with valid_p, c_p, v_p, N_p, A_p, d_p exactly as "denoised previews"
+ * defines them (for an invalid p: c_p = (0,0,0), v_p = -1), {X_p, t_p} from the position guide, hc the history's camera and W, H the
+ * image size, which is also the history's:
+ *     have = false
+ *     if valid_p and t_p >= 0 and a history exists and maxHistory > 0:
+ *         e = X_p - hc.pos;  a = dot3(e, hc.right);  b = dot3(e, hc.up);  z = dot3(e, hc.dir)
+ *         if z > 0:
+ *             fx = ((a / z) / ((2.0f*0.6f) * kAspect) + 0.5f) * (float)W
+ *             fy = (0.5f - (b / z) / (2.0f*0.6f)) * (float)H
+ *             if fx >= -1.0f and fx < (float)W and fy >= -1.0f and fy < (float)H:          (false for NaN)
+ *                 ix = floorf(fx); iy = floorf(fy); tx = fx - ix; ty = fy - iy
+ *                 lim = (positionTolerance*positionTolerance) * (t_p*t_p)
+ *                 sumW = sumL = sumVh = sumWv = 0; sumC = (0,0,0)
+ *                 taps q = (ix + i, iy + j), j = 0,1 outer, i = 0,1 inner; skipped when outside the image or !(hLen_q > 0)
+ *                     g = X_p - hX_q;  accepted iff dot3(g, g) <= lim and dot3(N_p, hN_q) >= normalCos
+ *                     wb = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty)
+ *                     sumW += wb; sumC += wb * hC_q (per channel); sumL += wb * hLen_q
+ *                     if hV_q >= 0: sumVh += wb * hV_q; sumWv += wb
+ *                 have = sumW > 0.015625f
+ *     if have:
+ *         Hc = sumC / sumW;  q = sumL / sumW;  Hl = q < maxHistory ? q : maxHistory;  Hv = sumWv > 0 ? sumVh / sumWv : -1
+ *         n = (float)count_p;  tot = n + Hl
+ *         cm = (n * c_p + Hl * Hc) / tot                                   (per channel)
+ *         vm = v_p >= 0 and Hv >= 0 ? ((n*n)*v_p + (Hl*Hl)*Hv) / (tot*tot)
+ *            : v_p >= 0 ? (v_p * n) / tot      (a history without a variance is taken to have the pixel's own per-sample variance)
+ *            : Hv  >= 0 ? (Hv * Hl) / tot      (and the other way round: the first 8-spp pass of a new view gets its edge-stopping from the history)
+ *            : -1
+ *         len = tot
+ *     else:
+ *         cm = c_p;  vm = v_p;  len = valid_p ? (float)count_p : 0
+ *     demodulate: C0_p = cm / d_p (per channel);  V0_p = vm < 0 ? -1 : vm / (lum(d_p)*lum(d_p))
+ *     otherwise:  C0_p = cm;  V0_p = vm          (no division: lum(1,1,1) is not exactly 1.0f, and without a history these are the plain denoiser's bits)
+ *     an invalid p: C0_p = (0,0,0), V0_p = -1, as in the plain denoiser
+ *     pending_p = {cm, vm}, {X_p, (valid_p and t_p >= 0) ? len : 0}, {N_p, 0};  pending camera = the current camera
+ * The iterations of "denoised previews" then run on (C0, V0) unchanged and write d_rgb.  The history is merged in RADIANCE space,
+ * before demodulation (the albedo guide of one surface point differs between two views), and no material or primitive id is used.
+ * An invalid pixel stays invalid.  A pixel whose centre ray misses never takes history and never becomes history.  Without a
+ * history (fresh context, after a reset, maxHistory = 0) the result is prt_hip_accum_denoise's, bit for bit.
+ *
+ * Life cycle (what keeps samples from being counted twice):
+ *   - a temporal denoise merges with the HISTORY only, never with pending, and overwrites pending: denoising the same view again
+ *     after more passes is idempotent in the history and never double counts;
+ *   - prt_hip_set_camera with a pending record promotes it to history when the new camera has the same width and height, otherwise
+ *     both are dropped; without a pending record (a view that was never denoised) it keeps the history under the same size rule;
+ *   - prt_hip_upload_scene and prt_hip_history_reset drop both; prt_hip_accum_reset / prt_hip_accum_import touch neither;
+ *   - prt_hip_accum_denoise ignores both.
+ * The history is BIASED for view-dependent radiance (reflections, highlights): a first-hit position says where the surface is,
+ * not what it reflects; maxHistory bounds the history's weight, so that new samples take over (once the noise is low a few such
+ * pixels dominate the squared error, as the emitter edges do for the filter).  A host that sets the SAME camera again gets the
+ * same per-pixel seeds and therefore the same samples: varying `seed` per view (allowed after the reset that prt_hip_set_camera
+ * implies) makes the merged samples independent.  Memory: 16 bytes (position) plus 2 x 48 bytes (history, pending) per pixel,
+ * allocated on first use.  In a multi-rank run the stage works on what this context holds, as the denoiser does.  With host guides
+ * (prt_hip_denoise_set_guides) the position plane may be the host's too or the library's for the current view. ---- */
+typedef struct {
+    float positionTolerance; /* finite, > 0: a tap is accepted within positionTolerance * t_p of X_p (0.01) */
+    float normalCos;         /* in [-1, 1]: least dot3 of the two guide normals (0.9) */
+    float maxHistory;        /* finite, >= 0: cap of the history's length in samples; 0 disables the merge (256) */
+} prt_temporal_params;
+/* The position plane of the current view into a host array of 4*width*height floats: renders it if stale; the host's own if set.
+ * Synchronous.  PRT_HIP_ESTATE without scene / camera. */
+int prt_hip_denoise_get_position(prt_hip_ctx* ctx, float* xyzt);
+/* The host's own position plane (4*width*height floats, taken at the camera's size on trust); NULL returns to the library's. */
+int prt_hip_denoise_set_position(prt_hip_ctx* ctx, const float* xyzt);
+/* prt_hip_accum_denoise with the temporal stage in place of its prepare step: parameters, d_rgb / stream rules, refusals and
+ * prt_hip_denoise_variance as there; PRT_HIP_EINVAL with a message naming the field for a prt_temporal_params value outside its range
+ * or non-finite, PRT_HIP_ESTATE without scene / camera / samples. */
+int prt_hip_accum_denoise_temporal(prt_hip_ctx* ctx, const prt_denoise_params* params, const prt_temporal_params* temporal, float exposure,
+                                   float* d_rgb, void* stream);
+/* Drops history and pending. */
+int prt_hip_history_reset(prt_hip_ctx* ctx);
+/* Checkpoint and test access.  export: which 0 = history, 1 = pending, into host arrays of 4*width*height floats each ({hC, hV},
+ * {hX, hLen}, {hN, 0}) and its camera; synchronous; PRT_HIP_ESTATE when there is none.  import: the arrays become the HISTORY seen
+ * from `camera`, whose width and height must be the current camera's (else PRT_HIP_EINVAL); pending is left as it is. */
+int prt_hip_history_export(prt_hip_ctx* ctx, uint32_t which, prt_camera_desc* camera, float* colorVar, float* posLen, float* normal);
+int prt_hip_history_import(prt_hip_ctx* ctx, const prt_camera_desc* camera, const float* colorVar, const float* posLen,
+                           const float* normal);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,11 @@ int prt_hip_test_denoise_profile(prt_hip_ctx* ctx, const prt_denoise_params* par
  * of read16 16-byte planes and read12 12-byte planes and writes one of write16 16-byte and write12 12-byte planes of `pixels`
  * elements, in buffers of its own; *ms = its time */
 int prt_hip_test_copy_yardstick(prt_hip_ctx* ctx, uint64_t pixels, int read16, int read12, int write16, int write12, float* ms);
+/* tools/temporal_bench.py: HIP-event times on the context's stream; ms[0] = the merge kernel alone, ms[1] = merge + iterations (a whole
+ * prt_hip_accum_denoise_temporal into the context's framebuffer), ms[2] = one position pass (0 with a host's plane), ms[3] = one
+ * prt_hip_render_gbuffer launch (type 0) of the same view; the last two include the two small memsets of a launch.  Synchronous. */
+int prt_hip_test_temporal_profile(prt_hip_ctx* ctx, const prt_denoise_params* params, const prt_temporal_params* temporal, float exposure,
+                                  float* ms4);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,10 @@ class DenoiseParams(C.Structure):
                 ("demodulate", C.c_uint32), ("guideSamples", C.c_uint32)]
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("positionTolerance", C.c_float), ("normalCos", C.c_float), ("maxHistory", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -122,6 +126,8 @@ EXPORTS = [
     "prt_hip_get_stats", "prt_hip_accum_reset", "prt_hip_render_accumulate", "prt_hip_accum_resolve", "prt_hip_accum_export",
     "prt_hip_accum_import", "prt_hip_render_adaptive", "prt_hip_accum_error", "prt_hip_accum_export_moments", "prt_hip_accum_import_moments",
     "prt_hip_denoise_set_guides", "prt_hip_denoise_get_guides", "prt_hip_accum_denoise", "prt_hip_denoise_variance",
+    "prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
+    "prt_hip_history_export", "prt_hip_history_import",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
@@ -131,7 +137,7 @@ EXPORTS = [
 
 # include/prt_hip_test.h: row-level entry points of the TEST build of the library (libprt_hip_test.so); the product does not export them
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
-                "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick"]
+                "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -213,6 +219,12 @@ def _load(path, with_test_entry_points):
     L.prt_hip_denoise_get_guides.argtypes = [vp, C.c_uint32, vp, vp]
     L.prt_hip_accum_denoise.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float, vp, vp]
     L.prt_hip_denoise_variance.argtypes = [vp, vp]
+    L.prt_hip_denoise_get_position.argtypes = [vp, vp]
+    L.prt_hip_denoise_set_position.argtypes = [vp, vp]
+    L.prt_hip_accum_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_float, vp, vp]
+    L.prt_hip_history_reset.argtypes = [vp]
+    L.prt_hip_history_export.argtypes = [vp, C.c_uint32, C.POINTER(CameraDesc), vp, vp, vp]
+    L.prt_hip_history_import.argtypes = [vp, C.POINTER(CameraDesc), vp, vp, vp]
     if with_test_entry_points:
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
@@ -221,6 +233,7 @@ def _load(path, with_test_entry_points):
         L.prt_hip_test_camera.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
         L.prt_hip_test_denoise_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float, vp]
         L.prt_hip_test_copy_yardstick.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        L.prt_hip_test_temporal_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_float, vp]
     for n in ("prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
               "prt_host_mesh_atrium", "prt_host_scene_create"):
         getattr(L, n).restype = vp
@@ -701,6 +714,73 @@ class PathTracer:
         var = np.zeros((H, W), dtype=np.float32)
         self._chk(self._L.prt_hip_denoise_variance(self._ctx, var.ctypes.data_as(C.c_void_p)), "prt_hip_denoise_variance")
         return var
+
+    # ---- temporal reprojection (include/prt_hip.h "temporal reprojection"): the denoiser with the previous view's result merged in
+    # wherever the same surface is still visible; set_camera promotes the last temporal denoise of a view to the history
+    @staticmethod
+    def temporal_params(position_tolerance=0.01, normal_cos=0.9, max_history=256.0):
+        return TemporalParams(position_tolerance, normal_cos, max_history)
+
+    def denoise_temporal_async(self, position_tolerance=0.01, normal_cos=0.9, max_history=256.0, iterations=5, normal_power_log2=5,
+                               sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True, guide_samples=8, exposure=1.0, d_rgb=None,
+                               stream=None):
+        """Queue the temporal stage and the filter over the whole image; d_rgb / stream as in denoise_async."""
+        p = self.denoise_params(iterations, normal_power_log2, sigma_luminance, sigma_albedo, demodulate, guide_samples)
+        t = self.temporal_params(position_tolerance, normal_cos, max_history)
+        self._chk(self._L.prt_hip_accum_denoise_temporal(self._ctx, C.byref(p), C.byref(t), exposure, d_rgb, stream),
+                  "prt_hip_accum_denoise_temporal")
+
+    def denoise_temporal(self, position_tolerance=0.01, normal_cos=0.9, max_history=256.0, iterations=5, normal_power_log2=5,
+                         sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True, guide_samples=8, exposure=1.0):
+        """The denoised image of the accumulator merged with the history, as (H, W, 3) float32; this view's result becomes the
+        pending record, which the next set_camera of the same size promotes to the history."""
+        self.denoise_temporal_async(position_tolerance, normal_cos, max_history, iterations, normal_power_log2, sigma_luminance,
+                                    sigma_albedo, demodulate, guide_samples, exposure)
+        W, H = self._camera.width, self._camera.height
+        return self._download_rect(0, 0, W - 1, H - 1, stats=False)
+
+    def denoise_position(self):
+        """(H, W, 4) float32 {X.xyz, t}: the first-hit position guide of the current view ({0, 0, 0, -1} for a miss); rendered if
+        stale, the host's own if set_denoise_position set it."""
+        W, H = self._camera.width, self._camera.height
+        pos = np.zeros((H, W, 4), dtype=np.float32)
+        self._chk(self._L.prt_hip_denoise_get_position(self._ctx, pos.ctypes.data_as(C.c_void_p)), "prt_hip_denoise_get_position")
+        return pos
+
+    def set_denoise_position(self, position):
+        """Supply the position plane ((H, W, 4): {X.xyz, t}, t < 0 for a miss); None returns to the library's own."""
+        if position is None:
+            self._chk(self._L.prt_hip_denoise_set_position(self._ctx, None), "prt_hip_denoise_set_position")
+            return
+        W, H = self._camera.width, self._camera.height
+        a = np.ascontiguousarray(position, dtype=np.float32)
+        if a.shape != (H, W, 4):
+            raise PrtError(f"set_denoise_position: a plane of shape {a.shape} does not match the camera's ({H}, {W}, 4)")
+        self._chk(self._L.prt_hip_denoise_set_position(self._ctx, a.ctypes.data_as(C.c_void_p)), "prt_hip_denoise_set_position")
+
+    def history_reset(self):
+        """Drop the history and the pending record."""
+        self._chk(self._L.prt_hip_history_reset(self._ctx), "prt_hip_history_reset")
+
+    def history_export(self, which=0):
+        """which 0 = history, 1 = pending: dict(camera=CameraDesc, color_var, pos_len, normal), planes (H, W, 4) float32
+        ({hC, hV}, {hX, hLen}, {hN, 0}); raises when there is none."""
+        W, H = self._camera.width, self._camera.height
+        cam = CameraDesc()
+        planes = [np.zeros((H, W, 4), dtype=np.float32) for _ in range(3)]
+        self._chk(self._L.prt_hip_history_export(self._ctx, which, C.byref(cam), *[p.ctypes.data_as(C.c_void_p) for p in planes]),
+                  "prt_hip_history_export")
+        return dict(camera=cam, color_var=planes[0], pos_len=planes[1], normal=planes[2])
+
+    def history_import(self, record):
+        """Make a record of history_export the history (its size must be the current camera's)."""
+        W, H = self._camera.width, self._camera.height
+        planes = [np.ascontiguousarray(record[k], dtype=np.float32) for k in ("color_var", "pos_len", "normal")]
+        cam = record["camera"]
+        if (cam.width, cam.height) == (W, H) and any(p.shape != (H, W, 4) for p in planes):
+            raise PrtError(f"history_import: planes of shape {[p.shape for p in planes]} do not match the camera's ({H}, {W}, 4)")
+        self._chk(self._L.prt_hip_history_import(self._ctx, C.byref(cam), *[p.ctypes.data_as(C.c_void_p) for p in planes]),
+                  "prt_hip_history_import")
 
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""

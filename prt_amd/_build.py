@@ -15,6 +15,7 @@ SOURCES = [
     "prt_bvh_build.hip",
     "prt_select.hip",
     "prt_denoise.hip",
+    "prt_temporal.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

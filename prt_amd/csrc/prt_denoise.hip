@@ -285,6 +285,17 @@ int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, floa
                        (const float*)c->dnNormal, n, (int)d->demodulate, c->dnPlane[0], c->dnGuideA, c->dnGuideN);
     if ((rc = launched("dn_prepare_kernel"))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    return prt_denoise_iterations(c, d, exposure, d_rgb, ev ? ev + 2 : nullptr);
+}
+
+} // namespace
+
+// The iterations on dnPlane[0] (what a prepare step left there) into d_rgb.  ev (optional, `iterations` events): one after every launch.
+int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev)
+{
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    hipStream_t s = c->stream;
+    int rc;
     const dim3 grid((W + DN_TILE_X - 1) / DN_TILE_X, (H + DN_TILE_Y - 1) / DN_TILE_Y);
     int cur = 0;
     for (uint32_t i = 0; i < d->iterations; i++) {
@@ -295,12 +306,14 @@ int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, floa
         else
             hipLaunchKernelGGL(dn_iter_kernel<false>, grid, dim3(DN_TILE_X * DN_TILE_Y), 0, s, A);
         if ((rc = launched("dn_iter_kernel"))) return rc;
-        if (ev) HIP_TRY(hipEventRecord(ev[2 + i], s));
+        if (ev) HIP_TRY(hipEventRecord(ev[i], s));
         cur ^= 1;
     }
     c->dnLast = cur;
     return PRT_HIP_OK;
 }
+
+namespace {
 
 int denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
 {
@@ -331,6 +344,9 @@ int own_framebuffer(prt_hip_ctx* c, float** d_rgb)
 
 } // namespace
 
+int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d) { return denoise_checks(c, d); }
+int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K) { return guides_ready(c, K); }
+int prt_denoise_own_framebuffer(prt_hip_ctx* c, float** d_rgb) { return own_framebuffer(c, d_rgb); }
 void prt_denoise_forget(prt_hip_ctx* c)
 {
     c->dnGuidesValid = false;
@@ -435,9 +451,9 @@ namespace {
 // (16-byte planes as float4, 12-byte planes as three floats, as the filter's kernels access them); the inputs are summed so
 // that no load can be dropped.
 struct CopyArgs {
-    const float4* r16[4];
+    const float4* r16[6];
     const float* r12[2];
-    float4* w16[3];
+    float4* w16[6];
     float* w12;
     int nr16, nr12, nw16, nw12;
     size_t n;
@@ -491,8 +507,8 @@ int prt_hip_test_denoise_profile(prt_hip_ctx* c, const prt_denoise_params* d, fl
 int prt_hip_test_copy_yardstick(prt_hip_ctx* c, uint64_t pixels, int read16, int read12, int write16, int write12, float* ms)
 {
     if (!c || !ms || pixels == 0) return fail(PRT_HIP_EINVAL, "NULL argument");
-    if (read16 < 0 || read16 > 4 || read12 < 0 || read12 > 2 || write16 < 0 || write16 > 3 || write12 < 0 || write12 > 1)
-        return fail(PRT_HIP_EINVAL, "copy_yardstick: at most 4 + 2 input and 3 + 1 output planes");
+    if (read16 < 0 || read16 > 6 || read12 < 0 || read12 > 2 || write16 < 0 || write16 > 6 || write12 < 0 || write12 > 1)
+        return fail(PRT_HIP_EINVAL, "copy_yardstick: at most 6 + 2 input and 6 + 1 output planes");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)pixels;
     const size_t bytes = n * (size_t)(16 * (read16 + write16) + 12 * (read12 + write12));

@@ -107,6 +107,15 @@ struct prt_hip_ctx {
     bool dnHostGuides = false;   // dnAlbedo / dnNormal hold planes the host supplied (prt_hip_denoise_set_guides)
     uint32_t dnGuideSeed = 0, dnGuideK = 0;
     int dnLast = -1;             // dnPlane[dnLast].w is V_final of the last denoise (-1: none yet)
+    // temporal reprojection (prt_temporal.hip): the position guide and the history / pending records, allocated on first use
+    float4* tpPos = nullptr;     // {X.xyz, t} per camera pixel: the library's (tpPosValid) or the host's own (tpHostPos)
+    size_t tpPosPixels = 0;
+    bool tpPosValid = false, tpHostPos = false;
+    float4* tpHist[3] = {nullptr, nullptr, nullptr}; // {hC.xyz, hV}, {hX.xyz, hLen}, {hN.xyz, 0}
+    float4* tpPend[3] = {nullptr, nullptr, nullptr};
+    size_t tpPixels = 0;         // pixels each of the six planes holds
+    bool tpHaveHist = false, tpHavePend = false;
+    prt_camera_desc tpHistCam{}, tpPendCam{};
 };
 
 
@@ -118,6 +127,20 @@ int prt_sticky_error(prt_hip_ctx* c, bool clear);
 // prt_denoise.hip: the view or the scene changed (guides of either origin are dropped); frees the planes
 void prt_denoise_forget(prt_hip_ctx* c);
 void prt_denoise_release(prt_hip_ctx* c);
+// prt_denoise.hip, for the temporal stage (prt_temporal.hip), which replaces the prepare step and then runs the same iterations:
+// the checks of prt_hip_accum_denoise; the guide planes for K jitters; the context's own framebuffer; the iterations on
+// dnPlane[0] -> d_rgb (ev, optional: one event recorded after every launch)
+int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d);
+int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K);
+int prt_denoise_own_framebuffer(prt_hip_ctx* c, float** d_rgb);
+int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev);
+// prt_kernels.hip: the spill columns of the traversal stacks for a launch of `blocks` workgroups
+int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks);
+// prt_temporal.hip: the view changes to `next` (pending becomes history when the size stays, else both go; the position guide
+// goes stale); the scene changed or prt_hip_history_reset (both records go); frees the planes
+void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next);
+void prt_temporal_forget(prt_hip_ctx* c);
+void prt_temporal_release(prt_hip_ctx* c);
 // prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
 // temp == nullptr it only sets tempBytes
 hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,

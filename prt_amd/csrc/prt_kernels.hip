@@ -494,6 +494,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->adErr) (void)hipFree(c->adErr);
     if (c->adCountHost) (void)hipHostFree(c->adCountHost);
     prt_denoise_release(c);
+    prt_temporal_release(c);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -578,6 +579,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     free_scene(c);
     accum_forget(c); // the accumulated samples were of the old scene
     prt_denoise_forget(c);
+    prt_temporal_forget(c);
 
     std::vector<float4> wnodes, shade, bump, mats, alpha;
     std::vector<float> tris;                 // 9 floats per triangle, leaf order
@@ -887,6 +889,7 @@ int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
     if (!c || !cam) return fail(PRT_HIP_EINVAL, "NULL argument");
     if (cam->width == 0 || cam->height == 0) return fail(PRT_HIP_EINVAL, "empty image");
     static_assert(sizeof(DevCamera) == sizeof(prt_camera_desc), "camera layouts must match");
+    prt_temporal_camera_change(c, cam); // before the view goes: a pending record becomes the history
     memcpy(&c->cam, cam, sizeof(DevCamera));
     c->haveCamera = true;
     accum_forget(c); // of another view (and perhaps another size)
@@ -1545,6 +1548,8 @@ int prt_hip_accum_import_moments(prt_hip_ctx* c, const float* mom)
 // Errors of launches since the last prt_hip_get_stats.  Every render clears its own control words and counters, so a watchdog
 // abort or a stack overflow of an EARLIER frame of an asynchronous sequence (bench steps, render + gather loops) would be gone by
 // the time anybody looks; the frame kernel therefore also ORs them into words no render clears.
+int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks) { return ensure_launch_resources(c, blocks); }
+
 int prt_sticky_error(prt_hip_ctx* c, bool clear)
 {
     uint32_t S[PRT_STICKY_WORDS] = {0};
