@@ -218,7 +218,8 @@ typedef struct {
     uint32_t width, height;           /* the camera's size */
     uint32_t seed, maxDepth, rrDepth; /* the estimator the accumulated samples came from (0 when the accumulator is empty) */
 } prt_accum_info;
-/* Empties the accumulator (every count 0) and unbinds the estimator.  prt_hip_set_camera and prt_hip_upload_scene do the same. */
+/* Empties the accumulator (every count 0) and unbinds the estimator.  prt_hip_set_camera and prt_hip_upload_scene do the same, and so
+ * does prt_hip_update_meshes. */
 int prt_hip_accum_reset(prt_hip_ctx* ctx);
 /* One pass: every pixel of the rectangle (or of rank's tiles in it) renders params->samples more samples, starting from its
  * record (a pixel with count 0 is seeded as prt_hip_render seeds it), stores its state, sum and count back and writes
@@ -420,6 +421,7 @@ int prt_hip_denoise_variance(prt_hip_ctx* ctx, float* var);
  *   - prt_hip_set_camera with a pending record promotes it to history when the new camera has the same width and height, otherwise
  *     both are dropped; without a pending record (a view that was never denoised) it keeps the history under the same size rule;
  *   - prt_hip_upload_scene and prt_hip_history_reset drop both; prt_hip_accum_reset / prt_hip_accum_import touch neither;
+ *   - prt_hip_update_meshes promotes a pending record as a prt_hip_set_camera of unchanged size does ("geometry updates");
  *   - prt_hip_accum_denoise ignores both.
  * The history is BIASED for view-dependent radiance (reflections, highlights): a first-hit position says where the surface is,
  * not what it reflects; maxHistory bounds the history's weight, so that new samples take over (once the noise is low a few such
@@ -451,6 +453,47 @@ int prt_hip_history_reset(prt_hip_ctx* ctx);
 int prt_hip_history_export(prt_hip_ctx* ctx, uint32_t which, prt_camera_desc* camera, float* colorVar, float* posLen, float* normal);
 int prt_hip_history_import(prt_hip_ctx* ctx, const prt_camera_desc* camera, const float* colorVar, const float* posLen,
                            const float* normal);
+
+/* ---- geometry updates: move and deform meshes of the uploaded scene in place.  A mesh's TOPOLOGY stays (the tree's shape, primRemapping,
+ * indices, materials, textures, lights); its vertex positions, and optionally its vertex normals, are replaced, and everything
+ * prt_hip_upload_scene derives from positions is rewritten on the device by two kernels (prt_refit.hip): the leaf triangles, the face
+ * normals of meshes without vertex normals, the vertex normals when given, dp01 / dp02 of the bump records, the child boxes of every
+ * node record and their hot copies, the root boxes, the radius.  Node boxes are REFITTED bottom up, in f32:
+ *     leaf:      lower = min, upper = max per component over the 3 x primCount vertices of its triangles
+ *     internal:  lower = min(child0.lower, child1.lower), upper = max(child0.upper, child1.upper)
+ * (min / max of finite floats: exact and order independent except for the sign of a zero).  After the call the context is in exactly
+ * the state prt_hip_upload_scene produces from the descriptor with the same topology, the new positions and normals, the given radius
+ * and node boxes refitted by this rule.  The reference's builder sets every node's box by the same rule (bvh.cpp:21-29), so for a
+ * change that leaves the builder's decisions alone (a translation, a uniform scale by a power of two, ...) that is the state of a
+ * rebuild.  A refit never improves a tree: after a large deformation build again (prt_hip_build_bvh) and upload.  Non-finite
+ * positions are the caller's error, as they are for the upload.
+ *
+ * Refusals: PRT_HIP_ESTATE without a scene; PRT_HIP_EINVAL with a message for count 0, a mesh index out of range, a vertexCount other
+ * than the uploaded mesh's, NULL positions, normals for a mesh uploaded without, a mesh named twice in one call, a negative or
+ * non-finite radius.  A refused call changes nothing.
+ *
+ * What the call invalidates (the samples and guides of the old geometry):
+ *   - the accumulator and the moments are emptied and the estimator unbound, as by prt_hip_accum_reset;
+ *   - the denoise guides and the position plane go stale and are rendered again on next use; planes a host had set are dropped, as
+ *     prt_hip_set_camera drops them;
+ *   - temporal records: a pending record is promoted to the history exactly as prt_hip_set_camera with an unchanged size promotes it;
+ *     without a pending record the history is kept.  The position and normal tests of the merge reject every pixel whose first hit
+ *     moved, so untouched surfaces keep their history and moved ones start fresh; what the history cannot see -- shadows and
+ *     reflections of the moved object on surfaces that did not move -- is biased as view-dependent radiance is, until new samples
+ *     outweigh it (maxHistory);
+ *   - prt_hip_render after the call renders the new geometry.
+ * stream as in prt_hip_render: the update is ordered after the work queued on it.  The call then SYNCHRONISES the context's stream
+ * once: the refitted root boxes come back to the host, which hands them to every later launch by value.  Memory: 12 bytes per triangle
+ * slot and 12 bytes per internal node kept from the upload, plus 12 bytes per vertex (24 with normals) of every mesh ever updated. ---- */
+typedef struct {
+    uint32_t mesh;           /* index into prt_scene_desc.meshes of the uploaded scene */
+    uint32_t vertexCount;    /* must equal the uploaded mesh's */
+    const float* positions;  /* 3*vertexCount, host pointer (the library copies) */
+    const float* normals;    /* 3*vertexCount, or NULL = keep the uploaded vertex normals; must be NULL for a mesh uploaded without */
+    float radius;            /* Scene::getRadius() after the change (scene.cpp:23-26); 0 = keep the current one.  With several
+                              * updates in one call the last non-zero one holds */
+} prt_mesh_update;
+int prt_hip_update_meshes(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, void* stream);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,17 @@ int prt_hip_test_copy_yardstick(prt_hip_ctx* ctx, uint64_t pixels, int read16, i
 int prt_hip_test_temporal_profile(prt_hip_ctx* ctx, const prt_denoise_params* params, const prt_temporal_params* temporal, float exposure,
                                   float* ms4);
 
+/* The device scene arrays as they stand, to host buffers (any of them may be NULL): counts[0] node records (16 floats each),
+ * [1] hot copies (16 floats each), [2] triangle slots (tris: 9 floats each, shade: 16 floats each), [3] bump records (12 floats
+ * each; 0 when the scene has no bump map), [4] meshes; rootBoxes: PRT_HIP_MAX_BVH x 6 floats, radius: 1 float.  Call it with NULL
+ * buffers for the counts first.  Synchronous. */
+int prt_hip_test_scene_arrays(prt_hip_ctx* ctx, uint64_t counts[5], float* wnodes, float* hot, float* tris, float* shade, float* bump,
+                              float* rootBoxes, float* radius);
+/* tools/refit_bench.py: prt_hip_update_meshes' device work queued `reps` times between HIP events on the context's stream; ms[0] =
+ * median time of the gather kernels, ms[1] = median of the level launches and the finish kernel (the copies of the caller's arrays
+ * lie before both).  Ends with one real prt_hip_update_meshes.  Synchronous. */
+int prt_hip_test_refit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, uint32_t reps, float* ms2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,12 @@ int prt_host_scene_load_env_light(prt_host_scene* s, const char* path);
 /* the descriptor of the scene as it stands; valid until the scene is changed or destroyed */
 const prt_scene_desc* prt_host_scene_describe(prt_host_scene* s);
 void prt_host_scene_bbox(const prt_host_scene* s, float lowerUpper[6]);
+/* Scene::updatePositions (an addition to the mirrored surface; the reference has no such method): new positions, and optionally new
+ * vertex normals (NULL = keep), for mesh `mesh` of the scene.  The tree keeps its shape; every node's box is refitted bottom up
+ * (leaf: min / max over its triangles' vertices, internal: union of its children), mesh and scene bounds and the radius are
+ * recomputed as Scene::add computes them (scene.cpp:23-26).  PRT_HIP_EINVAL for a bad index, another vertexCount, NULL positions or
+ * normals for a mesh without.  The descriptor of prt_host_scene_describe afterwards is the updated scene's. */
+int prt_host_scene_update_positions(prt_host_scene* s, uint32_t mesh, uint32_t vertexCount, const float* positions, const float* normals);
 
 /* Image::saveExr (image.cpp:82-139: half-float B,G,R OpenEXR) and Image::savePpm (image.cpp:52-80: tone map, gamma, 8 bit)
  * for a float RGB image of width*height*3 values, row 0 first; 0 or -1 */

@@ -107,6 +107,11 @@ class TemporalParams(C.Structure):
     _fields_ = [("positionTolerance", C.c_float), ("normalCos", C.c_float), ("maxHistory", C.c_float)]
 
 
+class MeshUpdate(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("vertexCount", C.c_uint32), ("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
+                ("radius", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -127,17 +132,18 @@ EXPORTS = [
     "prt_hip_accum_import", "prt_hip_render_adaptive", "prt_hip_accum_error", "prt_hip_accum_export_moments", "prt_hip_accum_import_moments",
     "prt_hip_denoise_set_guides", "prt_hip_denoise_get_guides", "prt_hip_accum_denoise", "prt_hip_denoise_variance",
     "prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
-    "prt_hip_history_export", "prt_hip_history_import",
+    "prt_hip_history_export", "prt_hip_history_import", "prt_hip_update_meshes",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
-    "prt_host_scene_add_mesh", "prt_host_scene_set_directional_light", "prt_host_scene_set_env_light", "prt_host_scene_load_env_light", "prt_host_scene_describe", "prt_host_scene_bbox", "prt_host_save_exr", "prt_host_save_ppm",
+    "prt_host_scene_add_mesh", "prt_host_scene_set_directional_light", "prt_host_scene_set_env_light", "prt_host_scene_load_env_light", "prt_host_scene_describe", "prt_host_scene_bbox", "prt_host_scene_update_positions", "prt_host_save_exr", "prt_host_save_ppm",
     "prt_host_camera_create", "prt_host_bvh_build", "prt_host_free",
 ]
 
 # include/prt_hip_test.h: row-level entry points of the TEST build of the library (libprt_hip_test.so); the product does not export them
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
-                "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile"]
+                "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
+                "prt_hip_test_refit_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -225,7 +231,10 @@ def _load(path, with_test_entry_points):
     L.prt_hip_history_reset.argtypes = [vp]
     L.prt_hip_history_export.argtypes = [vp, C.c_uint32, C.POINTER(CameraDesc), vp, vp, vp]
     L.prt_hip_history_import.argtypes = [vp, C.POINTER(CameraDesc), vp, vp, vp]
+    L.prt_hip_update_meshes.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), vp]
     if with_test_entry_points:
+        L.prt_hip_test_scene_arrays.argtypes = [vp, C.POINTER(C.c_uint64), vp, vp, vp, vp, vp, vp, vp]
+        L.prt_hip_test_refit_profile.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), C.c_uint32, vp]
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
         L.prt_hip_test_sincos.argtypes = [vp, C.c_uint32, vp, vp, vp]
@@ -266,6 +275,7 @@ def _load(path, with_test_entry_points):
     L.prt_host_scene_describe.restype = C.POINTER(SceneDesc)
     L.prt_host_scene_bbox.argtypes = [vp, f32p]
     L.prt_host_scene_bbox.restype = None
+    L.prt_host_scene_update_positions.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
     L.prt_host_camera_create.argtypes = [f32p, f32p, C.c_uint32, C.c_uint32, C.POINTER(CameraDesc)]
     L.prt_host_camera_create.restype = None
     L.prt_host_bvh_build.argtypes = [C.c_uint32, vp, vp, C.c_int, C.POINTER(C.POINTER(BvhNode)), u32p, C.POINTER(u32p)]
@@ -366,6 +376,17 @@ class Scene:
     def describe(self):
         return lib().prt_host_scene_describe(self._h)
 
+    def update_positions(self, mesh, positions, normals=None):
+        """Scene::updatePositions: new positions ((V, 3) float32, V unchanged) and optionally new vertex normals (None keeps them) for
+        mesh number `mesh`.  The tree keeps its shape and is refitted; bounds and radius are recomputed.  describe() / arrays()
+        afterwards describe the updated scene, and PathTracer.update_meshes sends it to the device without a new upload."""
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if n is not None and n.shape != p.shape:
+            raise PrtError(f"update_positions: {n.shape[0]} normals for {p.shape[0]} positions")
+        _check(lib().prt_host_scene_update_positions(self._h, mesh, len(p), p.ctypes.data_as(C.c_void_p),
+                                                     None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_host_scene_update_positions")
+
     def bbox(self):
         b = (C.c_float * 6)()
         lib().prt_host_scene_bbox(self._h, b)
@@ -459,6 +480,39 @@ class PathTracer:
     def upload_scene(self, scene):
         self._chk(self._L.prt_hip_upload_scene(self._ctx, scene.describe()), "prt_hip_upload_scene")
         self._scene = scene
+
+    def update_meshes(self, scene, meshes=None, stream=None, keep_normals=False):
+        """prt_hip_update_meshes: send the CURRENT positions (and vertex normals, unless keep_normals) of the scene's meshes `meshes`
+        (indices; None = all) and its radius to the device, where the scene was uploaded with the same topology: the viewer's path
+        after Scene.update_positions.  Empties the accumulator; a pending temporal record becomes the history."""
+        d = scene.describe().contents
+        ids = list(range(d.meshCount)) if meshes is None else [int(m) for m in meshes]
+        ups = (MeshUpdate * max(len(ids), 1))()
+        for k, m in enumerate(ids):
+            if not 0 <= m < d.meshCount:
+                raise PrtError(f"update_meshes: the scene has no mesh {m}")
+            md = d.meshes[m]
+            ups[k].mesh, ups[k].vertexCount, ups[k].positions = m, md.vertexCount, md.positions
+            ups[k].normals = None if keep_normals else md.normals
+            ups[k].radius = d.radius
+        self._chk(self._L.prt_hip_update_meshes(self._ctx, len(ids), ups, stream), "prt_hip_update_meshes")
+        self._scene = scene
+
+    def scene_arrays(self):
+        """Test build only: the device scene arrays as dict(wnodes (R, 16), hot (256, 16), tris (S, 9), shade (S, 16), bump (S or 0, 12),
+        root_boxes (meshes, 6), radius) of float32."""
+        self._need_row_level()
+        counts = (C.c_uint64 * 5)()
+        self._chk(self._L.prt_hip_test_scene_arrays(self._ctx, counts, None, None, None, None, None, None, None), "prt_hip_test_scene_arrays")
+        r, h, s, b, m = [int(x) for x in counts]
+        out = dict(wnodes=np.zeros((r, 16), np.float32), hot=np.zeros((h, 16), np.float32), tris=np.zeros((s, 9), np.float32),
+                   shade=np.zeros((s, 16), np.float32), bump=np.zeros((b, 12), np.float32), root_boxes=np.zeros((8, 6), np.float32),
+                   radius=np.zeros(1, np.float32))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self._L.prt_hip_test_scene_arrays(self._ctx, counts, *[ptr(out[k]) for k in ("wnodes", "hot", "tris", "shade", "bump", "root_boxes",
+                                                                                          "radius")]), "prt_hip_test_scene_arrays")
+        out["root_boxes"] = out["root_boxes"][:m].copy()
+        return out
 
     def set_camera(self, camera):
         self._chk(self._L.prt_hip_set_camera(self._ctx, C.byref(camera.desc)), "prt_hip_set_camera")

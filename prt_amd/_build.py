@@ -16,6 +16,7 @@ SOURCES = [
     "prt_select.hip",
     "prt_denoise.hip",
     "prt_temporal.hip",
+    "prt_refit.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

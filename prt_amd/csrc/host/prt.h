@@ -211,6 +211,10 @@ public:
     void setInfiniteAreaLight(const char* path);                                   // scene.h:42-45
     void setInfiniteAreaLight(int32_t width, int32_t height, const float* rgba);   // same, texels already in memory
     const InfiniteAreaLight& getInfiniteAreaLight() const { return m_infiniteAreaLight; }
+    // Not in the reference: new positions (and optionally vertex normals; nullptr keeps them) for the mesh of m_bvh[meshIndex], whose
+    // vertex count stays.  The tree keeps its shape and every node box is refitted bottom up; bounds and radius follow as in add().
+    // False (nothing changed) for a bad index, or normals for a mesh without vertex normals.
+    bool updatePositions(uint32_t meshIndex, const Vector3f* positions, const Vector3f* normals = nullptr);
     float getRadius() const { return m_radius; }
     const BBox& getBBox() const { return m_bbox; }
     const std::vector<Bvh*>& getBvhs() const { return m_bvh; }

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -141,6 +142,45 @@ void Scene::add(Bvh* bvh)
     auto center = m_bbox.center();
     m_radius = length(m_bbox.upper - center);
     m_revision = nextRevision();
+}
+
+bool Scene::updatePositions(uint32_t meshIndex, const Vector3f* positions, const Vector3f* normals)
+{
+    if (meshIndex >= m_bvh.size() || !positions) return false;
+    Bvh& bvh = *m_bvh[meshIndex];
+    Mesh& mesh = bvh.m_mesh;
+    if (normals && !mesh.hasVertexNormal()) return false;
+    std::copy(positions, positions + mesh.getVertexCount(), mesh.m_positions.begin());
+    if (normals) std::copy(normals, normals + mesh.getVertexCount(), mesh.m_normals.begin());
+    // Refit: nodes are in depth-first order, both children of node i lie behind it, so one backward sweep sees children first.  A
+    // node's box is the min / max over the vertices of the triangles below it, which is what the builder stores (bvh.cpp:21-29).
+    std::vector<prt_bvh_node>& nodes = bvh.m_nodes;
+    for (size_t i = nodes.size(); i-- > 0;) {
+        prt_bvh_node& n = nodes[i];
+        BBox box = BBox::init();
+        if (n.primCount == 0xf) {
+            for (const prt_bvh_node* ch : {&nodes[i + 1], &nodes[n.primOrSecondNodeIndex]}) {
+                BBox cb;
+                cb.lower = Vector3f(ch->lower[0], ch->lower[1], ch->lower[2]);
+                cb.upper = Vector3f(ch->upper[0], ch->upper[1], ch->upper[2]);
+                box.merge(cb);
+            }
+        } else {
+            for (uint32_t t = 0; t < n.primCount; t++) {
+                const uint32_t prim = bvh.m_primRemapping[n.primOrSecondNodeIndex + t];
+                for (uint32_t j = 0; j < 3; j++) box.merge(mesh.m_positions[mesh.m_indices[3 * prim + j]]);
+            }
+        }
+        memcpy(n.lower, &box.lower, 12);
+        memcpy(n.upper, &box.upper, 12);
+    }
+    mesh.calculateBounds();
+    m_bbox = BBox::init();
+    for (const Bvh* b : m_bvh) m_bbox.merge(b->m_mesh.getBBox()); // scene.cpp:23-26, over the meshes in add() order
+    auto center = m_bbox.center();
+    m_radius = length(m_bbox.upper - center);
+    m_revision = nextRevision();
+    return true;
 }
 
 void Scene::setDirectionalLight(const Vector3f& dir, const Vector3f& intensity) // scene.h:30-35

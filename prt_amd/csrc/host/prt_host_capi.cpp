@@ -139,6 +139,14 @@ const prt_scene_desc* prt_host_scene_describe(prt_host_scene* s)
     return &s->desc;
 }
 
+int prt_host_scene_update_positions(prt_host_scene* s, uint32_t mesh, uint32_t vertexCount, const float* positions, const float* normals)
+{
+    if (!s || !positions || mesh >= s->bvhs.size()) return PRT_HIP_EINVAL;
+    if (vertexCount != s->bvhs[mesh]->getMesh().getVertexCount()) return PRT_HIP_EINVAL;
+    return s->scene.updatePositions(mesh, reinterpret_cast<const Vector3f*>(positions), reinterpret_cast<const Vector3f*>(normals)) ? PRT_HIP_OK
+                                                                                                                                  : PRT_HIP_EINVAL;
+}
+
 static int saveImage(const char* path, uint32_t w, uint32_t h, const float* rgb, bool tonemap, bool exr, bool zip)
 {
     if (!path || !rgb || w == 0 || h == 0) return -1;

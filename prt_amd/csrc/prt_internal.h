@@ -32,6 +32,30 @@ const std::string& prt_last_error_string();
                             std::string(#expr) + ": " + hipGetErrorString(e_));                         \
     } while (0)
 
+// Geometry updates (prt_refit.hip): what prt_hip_update_meshes needs beside the arrays of DevScene, kept at upload.  It lives in the
+// context, not in DevScene, which is a by-value argument of the render kernels.
+struct PrtRefitMesh {
+    uint32_t slotBase = 0, slotCount = 0; // the mesh's triangle slots in tris / shade / bump
+    uint32_t vertexCount = 0, hasNormals = 0;
+    uint32_t rootKid = 0;                 // the root as a kid word (see PrtRefit::kids)
+    std::vector<std::pair<uint32_t, uint32_t>> levels; // per depth (root's record first): {first entry in levelList, entries}
+    float* dPos = nullptr;                // staging of the caller's positions / normals (3 * vertexCount floats), allocated by the first update
+    float* dNrm = nullptr;
+};
+struct PrtRefit {
+    std::vector<PrtRefitMesh> meshes;
+    uint32_t* slotVtx = nullptr;   // 3 vertex ids (within the mesh) per triangle slot; 0xffffffff in a pad slot
+    uint2* kids = nullptr;         // per wide record: its two children -- a leaf reference as the record holds it, or the child's own
+                                   // record index (a PRT_REF_HOT reference resolved)
+    uint32_t* levelList = nullptr; // record indices by mesh and depth (PrtRefitMesh::levels)
+    uint32_t* hotOrder = nullptr;  // record index of every hot slot
+    uint32_t hotCount = 0;
+    uint64_t records = 0, slots = 0;
+    bool anyBump = false;
+    float* rootOut = nullptr;      // device: PRT_MAX_BVH x 6 floats, the refitted root boxes
+    float* rootHost = nullptr;     // pinned host copy of it
+};
+
 struct prt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -49,6 +73,7 @@ struct prt_hip_ctx {
     DevScene sc{};
     DevCamera cam{};
     std::vector<void*> sceneAllocs;
+    PrtRefit rf;                // device allocations of it are in sceneAllocs
     // render resources
     float* fb = nullptr;
     size_t fbPixels = 0;
@@ -124,6 +149,19 @@ void prt_gather_release(prt_hip_ctx* c);
 // prt_kernels.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
 // stream must be idle); `clear` consumes it (prt_hip_get_stats), download / gather only report it
 int prt_sticky_error(prt_hip_ctx* c, bool clear);
+// Progressive rendering: the accumulator holds no samples from here on (its records are zeroed before their next use).
+inline void prt_accum_forget(prt_hip_ctx* c)
+{
+    c->accClear = true;
+    c->accMax = 0;
+    c->momClear = true; // and no moments (adaptive sampling)
+}
+// prt_refit.hip: called by prt_hip_upload_scene once the scene arrays are on the device, with the wide records as uploaded (hot
+// references in place), the record of every hot slot, and per mesh its slot range, vertex count and root reference
+// (PrtRefitMesh::rootKid = DevScene::rootRef on entry); prt_refit_forget drops the state with the scene
+int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
+                    const std::vector<uint32_t>& slotVtx, bool anyBump);
+void prt_refit_forget(prt_hip_ctx* c);
 // prt_denoise.hip: the view or the scene changed (guides of either origin are dropped); frees the planes
 void prt_denoise_forget(prt_hip_ctx* c);
 void prt_denoise_release(prt_hip_ctx* c);

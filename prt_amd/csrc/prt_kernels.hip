@@ -456,18 +456,11 @@ int prt_hip_create(int device, prt_hip_ctx** out)
     return PRT_HIP_OK;
 }
 
-// Progressive rendering: the accumulator holds no samples from here on (its records are zeroed before their next use).
-static void accum_forget(prt_hip_ctx* c)
-{
-    c->accClear = true;
-    c->accMax = 0;
-    c->momClear = true; // and no moments (adaptive sampling)
-}
-
 static void free_scene(prt_hip_ctx* c)
 {
     for (void* p : c->sceneAllocs) (void)hipFree(p);
     c->sceneAllocs.clear();
+    prt_refit_forget(c);
     c->haveScene = false;
 }
 
@@ -577,7 +570,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     if (s->meshCount == 0 || s->meshCount > PRT_MAX_BVH) return fail(PRT_HIP_EINVAL, "meshCount must be 1..8");
     HIP_TRY(hipSetDevice(c->device));
     free_scene(c);
-    accum_forget(c); // the accumulated samples were of the old scene
+    prt_accum_forget(c); // the accumulated samples were of the old scene
     prt_denoise_forget(c);
     prt_temporal_forget(c);
 
@@ -588,6 +581,9 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     std::vector<uint32_t> classWordOf;       // per texture: first word of its cell classes in alphaClass, 0xffffffff = not built yet
     std::vector<uint4> texDesc;
     std::vector<uint8_t> texels;
+    std::vector<uint32_t> slotVtx;           // 3 vertex ids per triangle slot, for prt_hip_update_meshes (prt_refit.hip)
+    std::vector<PrtRefitMesh> refitMeshes;
+    std::vector<uint32_t> hotOrder;
     DevScene sc{};
     sc.bvhCount = s->meshCount;
 
@@ -712,6 +708,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
                 tris.insert(tris.end(), 9, 0.0f);
                 triAlpha.push_back(0u);
                 triPrim.push_back(0u);
+                slotVtx.insert(slotVtx.end(), 3, 0xffffffffu);
                 continue;
             }
             uint32_t prim = md.primRemapping[kOfSlot[slot]];
@@ -738,8 +735,17 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
             HVec3 p0 = P(v0), p1 = P(v1), p2 = P(v2);
             const float corners[9] = {p0.x, p0.y, p0.z, p1.x, p1.y, p1.z, p2.x, p2.y, p2.z};
             tris.insert(tris.end(), corners, corners + 9);
+            slotVtx.insert(slotVtx.end(), {v0, v1, v2});
             triAlpha.push_back(alphaRef);
             triPrim.push_back(prim);
+        }
+        {
+            PrtRefitMesh rm;
+            rm.slotBase = triBase;
+            rm.slotCount = slotCount;
+            rm.vertexCount = md.vertexCount;
+            rm.hasNormals = md.normals ? 1u : 0u;
+            refitMeshes.push_back(std::move(rm));
         }
         // shading records (Mesh::getSurfaceProperties, mesh.cpp:311-364) in LEAF order, like the triangles: a hit names its
         // triangle by that index
@@ -804,6 +810,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
         }
         for (uint32_t m = 0; m < sc.bvhCount; m++) sc.rootRef[m] = hotRef(sc.rootRef[m]);
         for (size_t k = 0; k < order.size(); k++) memcpy(&hot[k * 4], &wnodes[(size_t)order[k] * 4], 4 * sizeof(float4));
+        hotOrder = order;
     }
     sc.hasLight = s->hasDirectionalLight ? 1u : 0u;
     memcpy(sc.lightDir, s->lightDir, 12);
@@ -880,6 +887,8 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     if ((rc = upload_vec(c, texDesc, &sc.texDesc))) return rc;
     if ((rc = upload_vec(c, texels, &sc.texels))) return rc;
     c->sc = sc;
+    for (uint32_t m = 0; m < sc.bvhCount; m++) refitMeshes[m].rootKid = sc.rootRef[m];
+    if ((rc = prt_refit_build(c, wnodes, hotOrder, std::move(refitMeshes), slotVtx, anyBump))) return rc;
     c->haveScene = true;
     return PRT_HIP_OK;
 }
@@ -892,7 +901,7 @@ int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
     prt_temporal_camera_change(c, cam); // before the view goes: a pending record becomes the history
     memcpy(&c->cam, cam, sizeof(DevCamera));
     c->haveCamera = true;
-    accum_forget(c); // of another view (and perhaps another size)
+    prt_accum_forget(c); // of another view (and perhaps another size)
     prt_denoise_forget(c);
     return PRT_HIP_OK;
 }
@@ -1241,7 +1250,7 @@ static int accum_ready(prt_hip_ctx* c)
 int prt_hip_accum_reset(prt_hip_ctx* c)
 {
     if (!c) return fail(PRT_HIP_EINVAL, "NULL argument");
-    accum_forget(c);
+    prt_accum_forget(c);
     return PRT_HIP_OK;
 }
 
