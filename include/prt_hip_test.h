@@ -57,6 +57,11 @@ int prt_hip_test_scene_arrays(prt_hip_ctx* ctx, uint64_t counts[5], float* wnode
  * median time of the gather kernels, ms[1] = median of the level launches and the finish kernel (the copies of the caller's arrays
  * lie before both).  Ends with one real prt_hip_update_meshes.  Synchronous. */
 int prt_hip_test_refit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, uint32_t reps, float* ms2);
+/* Occlusion rays of the context's last render (or accumulate / adaptive pass) that the frame kernel answered without a walk: the
+ * surface faces away from the slot's light, so an unoccluded answer would add +-0.  They are part of
+ * prt_hip_stats.occludedTraced and raysTraced, which count the reference's rays; 0 for a render with countTraffic, which walks every
+ * ray.  Synchronous. */
+int prt_hip_test_occlusion_skipped(prt_hip_ctx* ctx, uint64_t* skipped);
 
 #ifdef __cplusplus
 }

@@ -143,7 +143,7 @@ EXPORTS = [
 # include/prt_hip_test.h: row-level entry points of the TEST build of the library (libprt_hip_test.so); the product does not export them
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
-                "prt_hip_test_refit_profile"]
+                "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -243,6 +243,7 @@ def _load(path, with_test_entry_points):
         L.prt_hip_test_denoise_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.c_float, vp]
         L.prt_hip_test_copy_yardstick.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.prt_hip_test_temporal_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_float, vp]
+        L.prt_hip_test_occlusion_skipped.argtypes = [vp, C.POINTER(C.c_uint64)]
     for n in ("prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
               "prt_host_mesh_atrium", "prt_host_scene_create"):
         getattr(L, n).restype = vp
@@ -882,6 +883,13 @@ class PathTracer:
         self._chk(self._L.prt_hip_trace_rays(self._ctx, mode, len(org), org.ctypes.data_as(C.c_void_p), dirs.ctypes.data_as(C.c_void_p),
                                         max_t, hits.ctypes.data_as(C.c_void_p)), "prt_hip_trace_rays")
         return hits
+
+    def occlusion_skipped(self):
+        """Occlusion rays of the last render that were answered without a walk (part of occludedTraced)."""
+        self._need_row_level()
+        n = C.c_uint64()
+        self._chk(self._L.prt_hip_test_occlusion_skipped(self._ctx, C.byref(n)), "prt_hip_test_occlusion_skipped")
+        return int(n.value)
 
     def test_leaf(self, records):
         self._need_row_level()

@@ -29,6 +29,13 @@
 #ifndef PRT_IDLE_BREAK
 #define PRT_IDLE_BREAK 24 // finished rays that send the wave back to its refill point (a refill turn costs about four rounds: 8 -> 463, 16 -> 424, 24-32 -> 412-422 ms on C3)
 #endif
+// ... per traversal kind (the loops of the four kinds differ in length: an occlusion ray's loop turn is a quarter of a scatter ray's)
+#ifndef PRT_IDLE_BREAK_SCATTER
+#define PRT_IDLE_BREAK_SCATTER PRT_IDLE_BREAK
+#endif
+#ifndef PRT_IDLE_BREAK_OCC
+#define PRT_IDLE_BREAK_OCC PRT_IDLE_BREAK
+#endif
 // ---------------------------------------------------------------------------- device scene
 // wnodes: 4 x float4 (64 B) per INTERNAL node, (lo, hi) pairs per axis so that the slab arithmetic runs on packed
 //         f32 pairs: {lo0.x hi0.x lo0.y hi0.y} {lo0.z hi0.z lo1.z hi1.z} {lo1.x hi1.x lo1.y hi1.y} {ref0 ref1 splitAxis 0}
@@ -119,6 +126,11 @@ __device__ __forceinline__ float sse_max(float a, float b) { return a > b ? a : 
 __device__ __forceinline__ float std_max(float a, float b) { return (a < b) ? b : a; }
 __device__ __forceinline__ float asf(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t asu(float f) { return __float_as_uint(f); }
+// neither an infinity nor a NaN in any component (on the bits: no flag of the compiler can fold it away)
+__device__ __forceinline__ bool finite3(Vec3 v)
+{
+    return (asu(v.x) & 0x7f800000u) != 0x7f800000u && (asu(v.y) & 0x7f800000u) != 0x7f800000u && (asu(v.z) & 0x7f800000u) != 0x7f800000u;
+}
 
 // Scene and state arrays live in global memory (hipMalloc).  Where a pointer VALUE reaches the code through memory (an
 // argument block, a struct passed by reference) the compiler can no longer see that and emits flat loads, which take the
@@ -1086,6 +1098,11 @@ __device__ __forceinline__ bool ref_is_leaf(uint32_t ref) { return (ref & PRT_RE
 #ifndef PRT_EMPTY_GAIN
 #define PRT_EMPTY_GAIN 16u
 #endif
+// the refill point of a traversal kind (PRT_MODE_*, defined below: 0 primary packets, 1 scatter rays, 2 / 3 occlusion rays)
+__device__ __forceinline__ constexpr uint32_t idle_break(int mode)
+{
+    return mode == 1 ? (uint32_t)(PRT_IDLE_BREAK_SCATTER) : mode >= 2 ? (uint32_t)(PRT_IDLE_BREAK_OCC) : (uint32_t)(PRT_IDLE_BREAK);
+}
 struct NoQueue {
     __device__ __forceinline__ uint32_t operator()() const { return 0u; }
 };
@@ -1152,7 +1169,7 @@ __device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, 
             if (onLeaf) tracer_tri<MODE, COUNT>(sc, T, st, tr);
         }
         const uint32_t done = (uint32_t)__popcll(__ballot(active && T.ref == PRT_REF_NONE));
-        if (done >= PRT_IDLE_BREAK) break;
+        if (done >= idle_break(MODE)) break;
         if (PRT_EMPTY_BREAK && empty + done >= PRT_EMPTY_BREAK && (++round & 3u) == 0u) {
             const uint32_t gain = empty + done < PRT_EMPTY_GAIN ? empty + done : PRT_EMPTY_GAIN;
             if (queued() >= gain) break;

@@ -101,7 +101,7 @@ struct FrameArgs {
     uint32_t rowsPerBlock; // rows a block may hold at a time (<= PRT_POOL_CHUNKS; fewer when the launch is small)
     uint32_t spreadRows;   // rows are 8 clusters of 8 work items spread over the launch instead of 64 consecutive items
     float* rgb;
-    unsigned long long* counters; // PRT_STAT_SHARDS copies of: rays, occl, nBox, nTri, nHit, nTap, nPx, overflow
+    unsigned long long* counters; // PRT_STAT_SHARDS copies of: rays, occl, nBox, nTri, nHit, nTap, nPx, overflow; word PRT_STAT_OCCL_SKIPPED
     uint32_t* ctrl;               // row cursors, watchdog flag and report (PRT_CTRL_CURSORS)
     // per pool group (block * PRT_POOL_GROUPS + i)
     uint32_t* gRng;
@@ -162,6 +162,7 @@ struct __attribute__((aligned(16))) BlockState { // LDS, one per workgroup
     uint32_t exited;    // waves that have left the role loop: the last one writes the block's statistics out
     uint32_t overflow;  // a traversal needed more than 64 stack entries
     uint32_t rays, occl, px;                        // stats.h:10-16
+    uint32_t occlSkipped;                           // occlusion rays answered without a walk (of occl; read by the test build only)
     unsigned long long nBox, nTri, nHit, nTap;      // counting build only
 };
 typedef __attribute__((address_space(3))) BlockState* BlockLds;
@@ -174,7 +175,7 @@ __device__ __forceinline__ BlockLds block_lds()
 }
 
 struct WaveStats {
-    uint32_t rays, occl, px;
+    uint32_t rays, occl, px, occlSkipped;
 };
 
 // LDS words are reached through address-space-3 pointers (ds_* instructions with constant offsets); a generic reference to
@@ -292,7 +293,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
     const FrameArgs& A = frame_args(kargs);
     const BlockLds B = block_lds();
     uint32_t* blockQ = A.qE + (size_t)blockIdx.x * Q_COUNT * PRT_POOL_SLOTS;
-    WaveStats ws{0, 0, 0};
+    WaveStats ws{0, 0, 0, 0};
     Traffic tr{};
     const uint32_t lane = threadIdx.x & 63u, slot = lane & 7u, gbase = lane & ~7u;
     const bool inRange = P != PRT_NONE;
@@ -531,8 +532,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         if (directLighting && active) { // :196-252: every alive path gets an occlusion ray
             emitShadow = true; // the occlusion traversal builds org = pos + kFar*L, dir = -L from the slot's state
             shadowPacket = (alive & 0xfu) > 2u; // :198
-            sflags |= SLOT_HAS_SHADOW;
-            // (counted below: one ray, one occlusion ray)
+            // (counted below: one ray, one occlusion ray; whether it is also TRACED is decided at the end of the bounce)
         }
         bool survive = active;
         if (depth > rrDepth) { // one draw per alive slot, in slot order
@@ -551,6 +551,31 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
             ndir = normalize3(nextDir); // :267
             emitScatter = true;
             sflags |= SLOT_SURVIVE;
+        }
+        if (emitShadow) { // (decided here, behind the Russian roulette, where the bounce's temporaries are dead: the shade functions' stack stays as it was)
+            // An unoccluded answer adds beta * (max(dot(L, normal), 0) * I / pi) in the next round (:226-231, 246-249, above).  With
+            // !(dot > 0), dot not NaN, and beta and I finite that addend is +-0 in every component, and result + (+-0) differs from
+            // result at most in the sign of a zero, which the packet sum (+0) + result[0] + ... erases: the answer cannot reach the
+            // image, so the timed build asks nothing (DESIGN.md 4.2 has the proof; the counting build walks every ray).  L, normal
+            // and beta are the values the next round would read back from the slot.  An env-lit slot that keeps an older bounce's
+            // light has its direction in S5, not in registers: it is traced.
+            bool skip = false;
+            if (!COUNT) {
+                Vec3 L = mk3(0, 0, 0), I = mk3(0, 0, 0);
+                bool known = true;
+                if (lightSet) {
+                    if (ENV) {
+                        L = envL;
+                        I = envI;
+                        known = envSampled;
+                    } else {
+                        L = mk3(sc.lightDir[0], sc.lightDir[1], sc.lightDir[2]);
+                        I = mk3(sc.lightIntensity[0], sc.lightIntensity[1], sc.lightIntensity[2]);
+                    }
+                }
+                skip = known && dot3(L, normal) <= 0.0f && finite3(beta) && finite3(I);
+            }
+            if (!skip) sflags |= SLOT_HAS_SHADOW; // a skipped slot is counted (emitShadow) but neither queued nor awaited nor read back
         }
         phase = PH_WAIT_BOUNCE;
     }
@@ -616,7 +641,8 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
     // ---- the rays of the next round go to the block's queues: lane rank by wave ballot + popcount behind a RESERVATION of the
     // pass's entries (PRT_SHADERS shade roles append to the same queues: qRes is an LDS atomic, the tails are published below in
     // reservation order)
-    const bool want[Q_COUNT] = {emitPrimary, emitScatter, emitShadow && shadowPacket, emitShadow && !shadowPacket};
+    const bool traceShadow = emitShadow && (sflags & SLOT_HAS_SHADOW) != 0u; // (emitShadow: sflags are this bounce's)
+    const bool want[Q_COUNT] = {emitPrimary, emitScatter, traceShadow && shadowPacket, traceShadow && !shadowPacket};
     const uint32_t owner = poolLocal * 8u + slot; // slot index inside the block's pool (< PRT_POOL_SLOTS)
     uint32_t emitted = 0, newTail[Q_COUNT], qBase[Q_COUNT];
 #pragma unroll
@@ -671,10 +697,12 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         const uint32_t nShadow = (uint32_t)__popcll(__ballot(emitShadow)), nScatter = (uint32_t)__popcll(__ballot(emitScatter));
         ws.rays = nShadow + nScatter + samples * (uint32_t)__popcll(__ballot(statSamples));
         ws.occl = nShadow;
+        ws.occlSkipped = (uint32_t)__popcll(__ballot(emitShadow && !traceShadow));
         ws.px = (uint32_t)__popcll(__ballot(statPx));
         if (lane == 0) {
             if (ws.rays) lds_add(&B->rays, ws.rays);
             if (ws.occl) lds_add(&B->occl, ws.occl);
+            if (ws.occlSkipped) lds_add(&B->occlSkipped, ws.occlSkipped);
             if (ws.px) lds_add(&B->px, ws.px);
         }
         if (COUNT) block_count_traffic(B, tr);
@@ -1150,7 +1178,7 @@ __device__ __forceinline__ void frame_body()
         B->abort = 0;
         B->exited = 0;
         B->overflow = 0;
-        B->rays = B->occl = B->px = 0;
+        B->rays = B->occl = B->px = B->occlSkipped = 0;
         B->nBox = B->nTri = B->nHit = B->nTap = 0;
     }
     __syncthreads();
@@ -1301,6 +1329,7 @@ __device__ __forceinline__ void frame_body()
         if (r) atomicAdd(&C[0], (unsigned long long)r);
         if (o) atomicAdd(&C[1], (unsigned long long)o);
         if (px) atomicAdd(&C[6], (unsigned long long)px);
+        if (const uint32_t sk = lds_ld(&B->occlSkipped)) atomicAdd(&C[PRT_STAT_OCCL_SKIPPED], (unsigned long long)sk);
         if (COUNT) {
             if (B->nBox) atomicAdd(&C[2], (unsigned long long)B->nBox);
             if (B->nTri) atomicAdd(&C[3], (unsigned long long)B->nTri);

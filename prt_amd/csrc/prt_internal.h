@@ -18,6 +18,7 @@
 #else
 #define PRT_STAT_STRIDE 32 // 64-bit words per copy (256 B apart)
 #endif
+#define PRT_STAT_OCCL_SKIPPED 15 // word of a copy: occlusion rays the frame kernel answered without a walk (prt_frame.h; read by the test build only)
 #define PRT_TIMING_RING 32
 
 // thread-local message behind prt_hip_last_error(); returns `code`

@@ -1694,6 +1694,19 @@ struct DevBuf {
 } // namespace
 extern "C" {
 
+int prt_hip_test_occlusion_skipped(prt_hip_ctx* c, uint64_t* skipped)
+{
+    if (!c || !skipped) return fail(PRT_HIP_EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<unsigned long long> all((size_t)PRT_STAT_SHARDS * PRT_STAT_STRIDE);
+    HIP_TRY(hipMemcpy(all.data(), c->counters, all.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    uint64_t n = 0;
+    for (int sh = 0; sh < PRT_STAT_SHARDS; sh++) n += all[(size_t)sh * PRT_STAT_STRIDE + PRT_STAT_OCCL_SKIPPED];
+    *skipped = n;
+    return PRT_HIP_OK;
+}
+
 int prt_hip_trace_rays(prt_hip_ctx* c, int mode, uint32_t n, const float* org, const float* dir, float maxT, prt_hit* hits)
 {
     if (!c || !org || !dir || !hits) return fail(PRT_HIP_EINVAL, "NULL argument");
