@@ -11,6 +11,8 @@ TEST_LIB = os.path.join(LIB_DIR, "libprt_hip_test.so")  # same sources + -DPRT_T
 
 SOURCES = [
     "prt_kernels.hip",
+    "prt_context.hip",
+    "prt_upload.hip",
     "prt_gather.hip",
     "prt_bvh_build.hip",
     "prt_select.hip",

@@ -1,0 +1,352 @@
+// prt_context.hip -- the context behind the C-ABI handle (include/prt_hip.h): its lifetime, the last-error string, the camera, the
+// scaffold every entry point shares (prt_internal.h), and what reads a context back: download, statistics and the sticky error
+// words.  Host code only: no kernel is defined or launched here, so that the frame kernels' code objects (prt_kernels.hip) do not
+// move when it changes.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "prt_internal.h"
+
+namespace {
+thread_local std::string g_err;
+int fail(int code, const std::string& msg) { return prt_fail(code, msg); }
+} // namespace
+int prt_fail(int code, const std::string& msg)
+{
+    g_err = msg;
+    return code;
+}
+const std::string& prt_last_error_string() { return g_err; }
+
+// ============================================================================ the scaffold of an entry point
+int prt_check_rect(const prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
+{
+    const uint32_t W = c->cam.width, H = c->cam.height;
+    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    return PRT_HIP_OK;
+}
+
+int prt_stream_enter(prt_hip_ctx* c, void* stream, hipStream_t* out)
+{
+    hipStream_t s = c->stream;
+    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
+    *out = caller;
+    if (caller) {
+        HIP_TRY(hipEventRecord(c->evIn, caller));
+        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
+    }
+    return PRT_HIP_OK;
+}
+
+int prt_stream_leave(prt_hip_ctx* c, hipStream_t caller)
+{
+    hipStream_t s = c->stream;
+    if (caller) {
+        HIP_TRY(hipEventRecord(c->evOut, s));
+        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
+    }
+    return PRT_HIP_OK;
+}
+
+int prt_own_framebuffer(prt_hip_ctx* c, float** d_rgb)
+{
+    if (*d_rgb) return PRT_HIP_OK;
+    const size_t n = (size_t)c->cam.width * c->cam.height;
+    if (c->fbPixels != n) {
+        if (c->fb) (void)hipFree(c->fb);
+        c->fb = nullptr;
+        HIP_TRY(hipMalloc(&c->fb, n * 3 * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(c->fb, 0, n * 3 * sizeof(float), c->stream));
+        c->fbPixels = n;
+    }
+    *d_rgb = c->fb;
+    return PRT_HIP_OK;
+}
+
+int prt_launched(const char* kernel)
+{
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(kernel) + " launch: " + hipGetErrorString(le));
+    return PRT_HIP_OK;
+}
+
+// Per-thread spill columns of the traversal stacks (entries beyond those kept in LDS): [entry][thread], two words per entry.
+int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks)
+{
+    uint32_t threads = blocks * PRT_BLOCK;
+    if (threads > c->spillThreads) {
+        if (c->spill) (void)hipFree(c->spill);
+        c->spill = nullptr;
+        HIP_TRY(hipMalloc(&c->spill, (size_t)threads * 2 * (PRT_STACK_MAX - PRT_STACK_LDS_PACKET) * sizeof(uint32_t)));
+        c->spillThreads = threads;
+    }
+    return PRT_HIP_OK;
+}
+
+// Folds the recorded launches of the timing ring into the context's totals (waits for them: they were queued long ago).
+static void fold_timing(prt_hip_ctx* c)
+{
+    for (uint32_t i = 0; i < c->ringUsed; i++) {
+        float ms = 0.0f;
+        if (hipEventSynchronize(c->evT1[i]) == hipSuccess && hipEventElapsedTime(&ms, c->evT0[i], c->evT1[i]) == hipSuccess) {
+            c->lastMs = ms;
+            c->accMs += ms;
+            c->accLaunches++;
+        }
+    }
+    c->ringUsed = 0;
+}
+
+int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1)
+{
+    if (c->ringUsed == PRT_TIMING_RING) fold_timing(c);
+    if (!c->evT0[c->ringUsed]) HIP_TRY(hipEventCreate(&c->evT0[c->ringUsed]));
+    if (!c->evT1[c->ringUsed]) HIP_TRY(hipEventCreate(&c->evT1[c->ringUsed]));
+    *ev0 = c->evT0[c->ringUsed];
+    *ev1 = c->evT1[c->ringUsed];
+    c->ringUsed++;
+    return PRT_HIP_OK;
+}
+
+// Errors of launches since the last prt_hip_get_stats.  Every render clears its own control words and counters, so a watchdog
+// abort or a stack overflow of an EARLIER frame of an asynchronous sequence (bench steps, render + gather loops) would be gone by
+// the time anybody looks; the frame kernel therefore also ORs them into words no render clears.
+int prt_sticky_error(prt_hip_ctx* c, bool clear)
+{
+    uint32_t S[PRT_STICKY_WORDS] = {0};
+    if (!c->work) return PRT_HIP_OK;
+    HIP_TRY(hipMemcpy(S, c->work + PRT_WORK_WORDS, sizeof(S), hipMemcpyDeviceToHost));
+    if (S[0] == 0) return PRT_HIP_OK;
+    if (clear) HIP_TRY(hipMemset(c->work + PRT_WORK_WORDS, 0, sizeof(S)));
+    if (S[0] & 1u) {
+        std::string msg = "frame kernel: scheduler watchdog fired in a launch since the last prt_hip_get_stats (a workgroup waited for work that never came; its image is incomplete);";
+        for (uint32_t k = 0; k < std::min<uint32_t>(S[2], 8u); k++) {
+            const uint32_t* D = S + 8 + 16 * k;
+            char line[256];
+            snprintf(line, sizeof(line), " [block %u wave %u: ready %u live %u exhausted %u lock %u, %u groups wait for %u rays, tails %u %u %u %u heads %u %u %u %u]",
+                     D[0], D[1], D[2], D[3], D[4], D[5], D[6], D[7], D[8], D[9], D[10], D[11], D[12], D[13], D[14], D[15]);
+            msg += line;
+        }
+        return fail(PRT_HIP_ELAUNCH, msg);
+    }
+    return fail(PRT_HIP_ESTACK, "BVH traversal needed more than 64 stack entries in a launch since the last prt_hip_get_stats (the reference asserts here, bvh.cpp:552)");
+}
+
+extern "C" {
+
+const char* prt_hip_last_error(void) { return g_err.c_str(); }
+
+#ifndef PRT_SOURCE_SHA16
+#define PRT_SOURCE_SHA16 "unstamped"
+#endif
+const char* prt_hip_source_sha16(void) { return PRT_SOURCE_SHA16; }
+
+int prt_hip_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+static int create_resources(prt_hip_ctx* c)
+{
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+    c->computeUnits = prop.multiProcessorCount;
+    c->name = prop.name[0] ? prop.name : prop.gcnArchName;
+    HIP_TRY(hipStreamCreate(&c->stream));
+    HIP_TRY(hipEventCreateWithFlags(&c->evIn, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->evOut, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&c->work, (PRT_WORK_WORDS + PRT_STICKY_WORDS) * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(c->work, 0, (PRT_WORK_WORDS + PRT_STICKY_WORDS) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&c->counters, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long)));
+    return PRT_HIP_OK;
+}
+
+// The library touches neither the process environment nor the HIP runtime's configuration: a render is one kernel on one
+// stream of the context.
+int prt_hip_create(int device, prt_hip_ctx** out)
+{
+    if (!out) return fail(PRT_HIP_EINVAL, "out is NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
+        return fail(PRT_HIP_ENODEVICE, "no HIP device: libprt_hip has no CPU path (the GPU kernels are the product)");
+    if (device < 0 || device >= n) return fail(PRT_HIP_EINVAL, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    prt_hip_ctx* c = new prt_hip_ctx();
+    c->device = device;
+    int rc = create_resources(c);
+    if (rc != PRT_HIP_OK) {
+        std::string why = prt_last_error_string(); // prt_hip_destroy makes HIP calls of its own
+        prt_hip_destroy(c);      // frees whatever was created before the failure
+        return fail(rc, why);
+    }
+    *out = c;
+    return PRT_HIP_OK;
+}
+
+void prt_hip_destroy(prt_hip_ctx* c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    prt_free_scene(c);
+    if (c->fb) (void)hipFree(c->fb);
+    if (c->work) (void)hipFree(c->work);
+    if (c->counters) (void)hipFree(c->counters);
+    if (c->spill) (void)hipFree(c->spill);
+    if (c->wfBuffer) (void)hipFree(c->wfBuffer);
+    if (c->frameArgs) (void)hipFree(c->frameArgs);
+    if (c->accRng) (void)hipFree(c->accRng);
+    if (c->accSum) (void)hipFree(c->accSum);
+    if (c->accMom) (void)hipFree(c->accMom);
+    if (c->adCode) (void)hipFree(c->adCode);
+    if (c->adList) (void)hipFree(c->adList);
+    if (c->adFlag) (void)hipFree(c->adFlag);
+    if (c->adTemp) (void)hipFree(c->adTemp);
+    if (c->adCount) (void)hipFree(c->adCount);
+    if (c->adErr) (void)hipFree(c->adErr);
+    if (c->adCountHost) (void)hipHostFree(c->adCountHost);
+    prt_denoise_release(c);
+    prt_temporal_release(c);
+    prt_gather_release(c);
+    for (int k = 0; k < PRT_TIMING_RING; k++) {
+        if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
+        if (c->evT1[k]) (void)hipEventDestroy(c->evT1[k]);
+    }
+    if (c->evIn) (void)hipEventDestroy(c->evIn);
+    if (c->evOut) (void)hipEventDestroy(c->evOut);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+int prt_hip_device_info(prt_hip_ctx* c, char* name, size_t cap, int* computeUnits)
+{
+    if (!c) return fail(PRT_HIP_EINVAL, "ctx is NULL");
+    if (name && cap) {
+        strncpy(name, c->name.c_str(), cap - 1);
+        name[cap - 1] = 0;
+    }
+    if (computeUnits) *computeUnits = c->computeUnits;
+    return PRT_HIP_OK;
+}
+
+int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
+{
+    if (!c || !cam) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (cam->width == 0 || cam->height == 0) return fail(PRT_HIP_EINVAL, "empty image");
+    static_assert(sizeof(DevCamera) == sizeof(prt_camera_desc), "camera layouts must match");
+    prt_temporal_camera_change(c, cam); // before the view goes: a pending record becomes the history
+    memcpy(&c->cam, cam, sizeof(DevCamera));
+    c->haveCamera = true;
+    prt_accum_forget(c); // of another view (and perhaps another size)
+    prt_denoise_forget(c);
+    return PRT_HIP_OK;
+}
+
+float* prt_hip_framebuffer(prt_hip_ctx* c) { return c ? c->fb : nullptr; }
+
+int prt_hip_download(prt_hip_ctx* c, float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
+{
+    if (!c || !rgb_host) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->fb) return fail(PRT_HIP_ESTATE, "nothing rendered into the context framebuffer");
+    const uint32_t W = c->cam.width;
+    int rc = prt_check_rect(c, x0, y0, x1, y1);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    size_t rowBytes = (size_t)(x1 - x0 + 1) * 3 * sizeof(float);
+    size_t off = ((size_t)y0 * W + x0) * 3;
+    HIP_TRY(hipMemcpy2D(rgb_host + off, (size_t)W * 3 * sizeof(float), c->fb + off, (size_t)W * 3 * sizeof(float), rowBytes,
+                        y1 - y0 + 1, hipMemcpyDeviceToHost));
+    return prt_sticky_error(c, false); // the pixels are delivered, but a caller must learn that a launch behind them was cut short
+}
+
+int prt_hip_get_stats(prt_hip_ctx* c, prt_hip_stats* st)
+{
+    if (!c || !st) return fail(PRT_HIP_EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long h[PRT_STAT_STRIDE] = {0};
+    {
+        std::vector<unsigned long long> all((size_t)PRT_STAT_SHARDS * PRT_STAT_STRIDE);
+        HIP_TRY(hipMemcpy(all.data(), c->counters, all.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int sh = 0; sh < PRT_STAT_SHARDS; sh++)
+            for (int k = 0; k < PRT_STAT_STRIDE; k++) h[k] += all[(size_t)sh * PRT_STAT_STRIDE + k];
+    }
+    // errors of ANY launch since the last call (the last one included): see prt_sticky_error
+    const int sticky = prt_sticky_error(c, true);
+#ifdef PRT_PROFILE
+    if (h[14])
+        fprintf(stderr, "frame profile: waves %llu, per wave: shade %.1f%% (%.0f calls) trace %.1f%% (%.0f calls) idle/decide %.1f%% of %.2f Mcycles\n", h[14],
+                100.0 * h[8] / h[13], (double)h[11] / h[14], 100.0 * h[9] / h[13], (double)h[12] / h[14], 100.0 * h[10] / h[13], h[13] / 1e6 / h[14]);
+    if (h[14]) {
+        for (int m = 0; m < 4; m++)
+            fprintf(stderr, "  trace mode %d: %.1f M loop turns, %.1f lanes with a ray per turn, %.1f Gcycles in the loops => %.0f cycles per turn\n", m, h[16 + 3 * m] / 1e6,
+                    (double)h[17 + 3 * m] / (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1), h[18 + 3 * m] * 1024.0 / 1e9,
+                    h[18 + 3 * m] * 1024.0 / (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1));
+        for (int m = 0; m < 4; m++) {
+            const unsigned long long* q = h + 32 + 8 * m;
+            fprintf(stderr, "  mode %d rounds: node %.1f M with %.1f lanes, leaf %.1f M with %.1f lanes on a leaf (%.1f pair lanes working; serial build: lanes on a second triangle); refills %.1f M with %.1f lanes\n", m,
+                    q[0] / 1e6, (double)q[1] / (double)(q[0] ? q[0] : 1), q[2] / 1e6, (double)q[3] / (double)(q[2] ? q[2] : 1),
+                    (double)q[4] / (double)(q[2] ? q[2] : 1), q[6] / 1e6, (double)q[5] / (double)(q[6] ? q[6] : 1));
+        }
+        for (int m = 0; m < 4; m++) {
+            const unsigned long long* q = h + 32 + 8 * m;
+            const unsigned long long* w = h + 64 + 8 * m;
+            const double nr = (double)(q[0] ? q[0] : 1), lr = (double)(q[2] ? q[2] : 1);
+            fprintf(stderr, "  mode %d lanes sitting out: node rounds %.1f on a leaf, %.1f finished, %.1f without a ray; leaf rounds %.1f on a node, %.1f finished, %.1f without a ray; %.2f hit-update turns per leaf round; %.1f distinct records per node round\n",
+                    m, w[0] / nr, w[1] / nr, w[2] / nr, w[3] / lr, w[4] / lr, w[5] / lr, w[6] / lr, w[7] / nr);
+        }
+        for (int m = 0; m < 4; m++) {
+            const unsigned long long* w = h + 96 + 4 * m;
+            const double turns = (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1);
+            fprintf(stderr, "  mode %d cycles per loop turn: refill + result hand-off %.0f, entering / leaving BVHs %.0f, step phase %.0f\n", m, w[0] * 1024.0 / turns,
+                    w[1] * 1024.0 / turns, w[2] * 1024.0 / turns);
+        }
+        if (h[112])
+            fprintf(stderr, "  refills that left lanes empty: %.1f M, %.1f lanes each; at that moment %.1f rays in the block's OTHER queues, %.1f groups ready for shading, shade role taken %.2f of the time\n",
+                    h[112] / 1e6, (double)h[113] / h[112], (double)h[114] / h[112], (double)h[115] / h[112], (double)h[116] / h[112]);
+        if (h[118])
+            fprintf(stderr, "  shade passes with a bounce: %.1f M, %.1f of 64 lanes carry a path through it; the shade role is held %.2f of a block's time (sum of its waves' shade shares)\n",
+                    h[118] / 1e6, (double)h[119] / h[118], 4.0 * h[8] / h[13]);
+        fprintf(stderr, "  node steps that leave a lane on an internal record outside the hot set: %.2f G by descending from the parent, %.2f G by a pop (%.2f of them direct)\n",
+                h[120] / 1e9, h[121] / 1e9, (double)h[120] / (double)(h[120] + h[121] ? h[120] + h[121] : 1));
+        fprintf(stderr, "  cooperative leaf rounds in which a candidate of a leaf with alpha-tested triangles came up: %.1f M, %.0f cycles each from the candidate test to the end of the alpha tests = %.1f Gcycles of wave time\n",
+                h[122] / 1e6, h[123] * 1024.0 / (double)(h[122] ? h[122] : 1), h[123] * 1024.0 / 1e9);
+        fprintf(stderr, "  stack pops of modes 1-3: %.1f G, of them from the spill area in HBM: %.2f G\n", (h[32 + 15] + h[32 + 23] + h[32 + 31]) / 1e9, h[39] / 1e9);
+        fprintf(stderr, "  claims %.1f M, empty %.1f M; shade passes %.1f M with %.2f groups each\n", h[28] / 1e6, h[29] / 1e6, h[30] / 1e6, (double)h[31] / (double)(h[30] ? h[30] : 1));
+    }
+#endif
+    st->raysTraced = h[0];
+    st->occludedTraced = h[1];
+    st->nBox = h[2];
+    st->nTri = h[3];
+    st->nHit = h[4];
+    st->nTap = h[5];
+    st->nPx = h[6];
+    for (int m = 0; m < 4; m++) {
+#ifdef PRT_PROFILE
+        st->modeBox[m] = st->modeTri[m] = st->modeTap[m] = 0; // the words carry the profile build's loop statistics
+#else
+        st->modeBox[m] = h[16 + 3 * m];
+        st->modeTri[m] = h[17 + 3 * m];
+        st->modeTap[m] = h[18 + 3 * m];
+#endif
+    }
+    st->stackOverflow = h[7];
+    fold_timing(c);
+    st->kernelMs = c->accLaunches ? c->lastMs : 0.0;
+    st->kernelMsSum = c->accMs;
+    st->kernelLaunches = c->accLaunches;
+    c->accMs = c->lastMs = 0.0;
+    c->accLaunches = 0;
+    if (sticky) return sticky;
+    if (h[7]) return fail(PRT_HIP_ESTACK, "BVH traversal needed more than 64 stack entries (the reference asserts here, bvh.cpp:552)");
+    return PRT_HIP_OK;
+}
+
+} // extern "C"

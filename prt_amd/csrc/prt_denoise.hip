@@ -233,16 +233,11 @@ int planes_ready(prt_hip_ctx* c)
 
 uint32_t grid1d(prt_hip_ctx* c, size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, (size_t)c->computeUnits * 16); }
 
-int launched(const char* what)
-{
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(what) + " launch: " + hipGetErrorString(le));
-    return PRT_HIP_OK;
-}
+} // namespace
 
 // The guide planes a denoise with K jitters uses, on the context's stream: the host's own, or the average of K launches of the
 // G-buffer kernel per plane (seed boundSeed + k), rendered when they are stale.  dnPlane[1] is the launches' target in between.
-int guides_ready(prt_hip_ctx* c, uint32_t K)
+int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K)
 {
     if (!c->haveScene || !c->haveCamera) return fail(PRT_HIP_ESTATE, "upload a scene and set a camera first");
     int rc = planes_ready(c);
@@ -261,7 +256,7 @@ int guides_ready(prt_hip_ctx* c, uint32_t K)
             if ((rc = prt_hip_render_gbuffer(c, 0, 0, W - 1, H - 1, plane == 0 ? 0u : 2u, c->accSeed + k, 1.0f, tmp, nullptr))) return rc;
             hipLaunchKernelGGL(dn_guide_sum_kernel, dim3(grid1d(c, nf)), dim3(256), 0, c->stream, g, (const float*)tmp, nf, k == 0 ? 1 : 0,
                                k == K - 1 ? 1 : 0, 1.0f / (float)K);
-            if ((rc = launched("dn_guide_sum_kernel"))) return rc;
+            if ((rc = prt_launched("dn_guide_sum_kernel"))) return rc;
         }
     }
     c->dnGuidesValid = true;
@@ -270,6 +265,8 @@ int guides_ready(prt_hip_ctx* c, uint32_t K)
     c->dnLast = -1; // dnPlane[1] was overwritten
     return PRT_HIP_OK;
 }
+
+namespace {
 
 // Prepare + iterations on the context's stream.  ev (optional, iterations + 2 events): recorded before the prepare kernel and
 // after every launch.
@@ -283,7 +280,7 @@ int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, floa
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     hipLaunchKernelGGL(dn_prepare_kernel, dim3(grid1d(c, n)), dim3(256), 0, s, (const float4*)c->accSum, mom, (const float*)c->dnAlbedo,
                        (const float*)c->dnNormal, n, (int)d->demodulate, c->dnPlane[0], c->dnGuideA, c->dnGuideN);
-    if ((rc = launched("dn_prepare_kernel"))) return rc;
+    if ((rc = prt_launched("dn_prepare_kernel"))) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
     return prt_denoise_iterations(c, d, exposure, d_rgb, ev ? ev + 2 : nullptr);
 }
@@ -305,7 +302,7 @@ int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float ex
             hipLaunchKernelGGL(dn_iter_kernel<true>, grid, dim3(DN_TILE_X * DN_TILE_Y), 0, s, A);
         else
             hipLaunchKernelGGL(dn_iter_kernel<false>, grid, dim3(DN_TILE_X * DN_TILE_Y), 0, s, A);
-        if ((rc = launched("dn_iter_kernel"))) return rc;
+        if ((rc = prt_launched("dn_iter_kernel"))) return rc;
         if (ev) HIP_TRY(hipEventRecord(ev[i], s));
         cur ^= 1;
     }
@@ -313,9 +310,7 @@ int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float ex
     return PRT_HIP_OK;
 }
 
-namespace {
-
-int denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
+int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
 {
     if (!c || !d) return fail(PRT_HIP_EINVAL, "NULL argument");
     int rc = check_params(d);
@@ -328,25 +323,6 @@ int denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
     return PRT_HIP_OK;
 }
 
-int own_framebuffer(prt_hip_ctx* c, float** d_rgb)
-{
-    const size_t n = (size_t)c->cam.width * c->cam.height;
-    if (c->fbPixels != n) {
-        if (c->fb) (void)hipFree(c->fb);
-        c->fb = nullptr;
-        HIP_TRY(hipMalloc(&c->fb, n * 3 * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(c->fb, 0, n * 3 * sizeof(float), c->stream));
-        c->fbPixels = n;
-    }
-    *d_rgb = c->fb;
-    return PRT_HIP_OK;
-}
-
-} // namespace
-
-int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d) { return denoise_checks(c, d); }
-int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K) { return guides_ready(c, K); }
-int prt_denoise_own_framebuffer(prt_hip_ctx* c, float** d_rgb) { return own_framebuffer(c, d_rgb); }
 void prt_denoise_forget(prt_hip_ctx* c)
 {
     c->dnGuidesValid = false;
@@ -399,7 +375,7 @@ int prt_hip_denoise_get_guides(prt_hip_ctx* c, uint32_t guideSamples, float* alb
     if (!c || !albedo || !normal) return fail(PRT_HIP_EINVAL, "NULL argument");
     int rc = check_guide_samples(guideSamples);
     if (rc) return rc;
-    if ((rc = guides_ready(c, guideSamples))) return rc;
+    if ((rc = prt_denoise_guides_ready(c, guideSamples))) return rc;
     const size_t bytes = c->dnPixels * 3 * sizeof(float);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(albedo, c->dnAlbedo, bytes, hipMemcpyDeviceToHost));
@@ -409,23 +385,14 @@ int prt_hip_denoise_get_guides(prt_hip_ctx* c, uint32_t guideSamples, float* alb
 
 int prt_hip_accum_denoise(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, void* stream)
 {
-    int rc = denoise_checks(c, d);
+    int rc = prt_denoise_checks(c, d);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evIn, caller));
-        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
-    }
-    if ((rc = guides_ready(c, d->guideSamples))) return rc;
-    if (!d_rgb && (rc = own_framebuffer(c, &d_rgb))) return rc;
-    if ((rc = run_filter(c, d, exposure, d_rgb, nullptr))) return rc;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evOut, s));
-        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
-    }
-    return PRT_HIP_OK;
+    hipStream_t caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = prt_denoise_guides_ready(c, d->guideSamples)) || (rc = prt_own_framebuffer(c, &d_rgb)) ||
+        (rc = run_filter(c, d, exposure, d_rgb, nullptr)))
+        return rc;
+    return prt_stream_leave(c, caller);
 }
 
 int prt_hip_denoise_variance(prt_hip_ctx* c, float* var)
@@ -483,11 +450,11 @@ extern "C" {
 int prt_hip_test_denoise_profile(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* ms)
 {
     if (!ms) return fail(PRT_HIP_EINVAL, "NULL argument");
-    int rc = denoise_checks(c, d);
+    int rc = prt_denoise_checks(c, d);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     float* rgb = nullptr;
-    if ((rc = guides_ready(c, d->guideSamples)) || (rc = own_framebuffer(c, &rgb))) return rc;
+    if ((rc = prt_denoise_guides_ready(c, d->guideSamples)) || (rc = prt_own_framebuffer(c, &rgb))) return rc;
     hipEvent_t ev[8] = {};
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
     // the whole filter between two events, then the same again with an event after every launch
@@ -534,7 +501,7 @@ int prt_hip_test_copy_yardstick(prt_hip_ctx* c, uint64_t pixels, int read16, int
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     (void)hipFree(buf);
-    return launched("dn_copy_kernel");
+    return prt_launched("dn_copy_kernel");
 }
 
 } // extern "C"

@@ -42,7 +42,7 @@
 //         child 0 is the reference's node i+1, child 1 its m_nodes[primOrSecondNodeIndex]; refs: see PRT_REF_LEAF
 // roots:  per BVH the root's reference and box (rootRef, rootBox)
 // tris:   9 floats (36 B) per triangle SLOT: primRemapping (LEAF) order, all BVHs behind one another, a leaf's triangles contiguous;
-//         a leaf may start a few unused slots late so that it touches one 128-byte line less (prt_kernels.hip leaf_slots): p0 p1 p2.  A traversal reads
+//         a leaf may start a few unused slots late so that it touches one 128-byte line less (prt_upload.hip leaf_slots): p0 p1 p2.  A traversal reads
 //         nothing else of a triangle unless it is a candidate: trees far larger than the caches are bound by the rate of L2 misses
 //         (profiles/r03_frame_c4_counters.json), so every byte a leaf visit does not need is kept out of its lines
 // triAlpha: per triangle slot: 0, or 1 + index of its alpha record (read for candidates of leaves whose reference says

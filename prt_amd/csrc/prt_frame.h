@@ -24,6 +24,8 @@
 // no agent-scope fence, no cross-XCD traffic and no inter-workgroup dependency exists -- a block that starts late or runs
 // alone still completes.  The only global words are the row cursor, the statistics and the watchdog flag.
 #pragma once
+#include "prt_internal.h"
+#include "prt_lanes.h"
 
 #ifndef PRT_POOL_CHUNKS
 #define PRT_POOL_CHUNKS 16 // rows of 64 pixel groups a block keeps in flight (per wave: one row, as with round 2's 4 rows for 4 waves)

@@ -305,12 +305,8 @@ int prt_hip_gather_rccl(prt_hip_ctx* c, float* d_rgb, int root, void* stream)
     const uint32_t totalTiles = ((W + T - 1) / T) * ((H + T - 1) / T);
     const uint32_t n = (uint32_t)c->commSize, me = (uint32_t)c->commRank;
     const size_t tileFloats = (size_t)T * T * 3;
-    hipStream_t s = c->stream;
-    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evIn, caller));
-        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
-    }
+    hipStream_t s = c->stream, caller;
+    if ((rc = prt_stream_enter(c, stream, &caller))) return rc;
     if (n > 1) {
         if (me != (uint32_t)root) {
             const uint32_t mine = tiles_owned(totalTiles, me, n);
@@ -336,11 +332,7 @@ int prt_hip_gather_rccl(prt_hip_ctx* c, float* d_rgb, int root, void* stream)
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) return prt_fail(PRT_HIP_ELAUNCH, std::string("gather kernels: ") + hipGetErrorString(le));
     }
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evOut, s));
-        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
-    }
-    return PRT_HIP_OK;
+    return prt_stream_leave(c, caller);
 }
 
 int prt_hip_gather_payload_bytes(prt_hip_ctx* c, uint64_t* bytes)
@@ -365,10 +357,10 @@ int prt_hip_gather(prt_hip_ctx* const* ctxs, int n, float* rgb_host, uint32_t x0
     }
     prt_hip_ctx* root = ctxs[0];
     const uint32_t W = root->cam.width, H = root->cam.height, T = root->lastTile;
-    if (x1 < x0 || y1 < y0 || x1 >= W || y1 >= H) return prt_fail(PRT_HIP_EINVAL, "pixel rectangle outside the image");
+    int rc = prt_check_rect(root, x0, y0, x1, y1);
+    if (rc) return rc;
     const uint32_t totalTiles = ((W + T - 1) / T) * ((H + T - 1) / T);
     const size_t tileFloats = (size_t)T * T * 3;
-    int rc;
     // every other context packs its tiles; the packed tiles are copied device to device and unpacked into context 0's frame
     for (int i = 1; i < n; i++) {
         prt_hip_ctx* c = ctxs[i];

@@ -147,9 +147,28 @@ struct prt_hip_ctx {
 
 // prt_gather.hip: frees the staging buffers and an owned communicator
 void prt_gather_release(prt_hip_ctx* c);
-// prt_kernels.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
+// prt_context.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
 // stream must be idle); `clear` consumes it (prt_hip_get_stats), download / gather only report it
 int prt_sticky_error(prt_hip_ctx* c, bool clear);
+// prt_context.hip, the scaffold of an entry point.  Each returns PRT_HIP_OK or the code of the error it has recorded.
+// The rectangle lies inside the camera's image.
+int prt_check_rect(const prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
+// The work of an entry point runs on the context's own stream; a caller's stream is ordered around it with two events: work queued
+// on it before prt_stream_enter is finished before the context's stream goes on, and whatever the caller queues after
+// prt_stream_leave waits for it.  *caller = the stream to hand to prt_stream_leave, or null when there is nothing to order (no
+// stream given, or the context's own).  An error return skips the leave.
+int prt_stream_enter(prt_hip_ctx* c, void* stream, hipStream_t* caller);
+int prt_stream_leave(prt_hip_ctx* c, hipStream_t caller);
+// *d_rgb == NULL becomes the context's own framebuffer, (re)allocated at the camera's size and cleared on the context's stream.
+int prt_own_framebuffer(prt_hip_ctx* c, float** d_rgb);
+// After a kernel launch: PRT_HIP_ELAUNCH "<kernel> launch: ..." when the runtime refused it.
+int prt_launched(const char* kernel);
+// The next event pair of the timing ring (prt_hip_ctx::evT0): record ev0 before and ev1 after the launch that prt_hip_get_stats is to time.
+int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1);
+// The spill columns of the traversal stacks for a launch of `blocks` workgroups.
+int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks);
+// prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
+void prt_free_scene(prt_hip_ctx* c);
 // Progressive rendering: the accumulator holds no samples from here on (its records are zeroed before their next use).
 inline void prt_accum_forget(prt_hip_ctx* c)
 {
@@ -157,7 +176,7 @@ inline void prt_accum_forget(prt_hip_ctx* c)
     c->accMax = 0;
     c->momClear = true; // and no moments (adaptive sampling)
 }
-// prt_refit.hip: called by prt_hip_upload_scene once the scene arrays are on the device, with the wide records as uploaded (hot
+// prt_refit.hip: called by prt_hip_upload_scene (prt_upload.hip) once the scene arrays are on the device, with the wide records as uploaded (hot
 // references in place), the record of every hot slot, and per mesh its slot range, vertex count and root reference
 // (PrtRefitMesh::rootKid = DevScene::rootRef on entry); prt_refit_forget drops the state with the scene
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
@@ -167,14 +186,11 @@ void prt_refit_forget(prt_hip_ctx* c);
 void prt_denoise_forget(prt_hip_ctx* c);
 void prt_denoise_release(prt_hip_ctx* c);
 // prt_denoise.hip, for the temporal stage (prt_temporal.hip), which replaces the prepare step and then runs the same iterations:
-// the checks of prt_hip_accum_denoise; the guide planes for K jitters; the context's own framebuffer; the iterations on
-// dnPlane[0] -> d_rgb (ev, optional: one event recorded after every launch)
+// the checks of prt_hip_accum_denoise; the guide planes for K jitters; the iterations on dnPlane[0] -> d_rgb (ev, optional: one
+// event recorded after every launch)
 int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d);
 int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K);
-int prt_denoise_own_framebuffer(prt_hip_ctx* c, float** d_rgb);
 int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev);
-// prt_kernels.hip: the spill columns of the traversal stacks for a launch of `blocks` workgroups
-int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks);
 // prt_temporal.hip: the view changes to `next` (pending becomes history when the size stays, else both go; the position guide
 // goes stale); the scene changed or prt_hip_history_reset (both records go); frees the planes
 void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next);

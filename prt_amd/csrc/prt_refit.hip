@@ -168,13 +168,6 @@ int upload_array(prt_hip_ctx* c, const std::vector<T>& v, T** out)
     return PRT_HIP_OK;
 }
 
-int launch_error(const char* what)
-{
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(what) + " launch: " + hipGetErrorString(le));
-    return PRT_HIP_OK;
-}
-
 // Queues the copies of the caller's arrays, then gather, levels and finish for the named meshes on s.  ev (optional, 3 events):
 // recorded before the gathers, after them and after the finish kernel.
 int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipStream_t s, hipEvent_t* ev)
@@ -195,7 +188,7 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
         GatherArgs g{R.slotVtx, M.dPos, u[k].normals ? M.dNrm : nullptr, tris, const_cast<float4*>(c->sc.shade),
                      R.anyBump ? const_cast<float4*>(c->sc.bump) : nullptr, M.slotBase, M.slotCount, M.hasNormals ? 0u : 1u};
         hipLaunchKernelGGL(refit_gather_kernel, dim3((M.slotCount + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, g);
-        int rc = launch_error("refit_gather_kernel");
+        int rc = prt_launched("refit_gather_kernel");
         if (rc) return rc;
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
@@ -206,7 +199,7 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
             const uint32_t first = M.levels[d].first, n = M.levels[d].second;
             hipLaunchKernelGGL(refit_level_kernel, dim3((n + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, R.levelList + first, n,
                                R.kids, tris, wnodes);
-            int rc = launch_error("refit_level_kernel");
+            int rc = prt_launched("refit_level_kernel");
             if (rc) return rc;
         }
         ra.mesh[ra.count] = u[k].mesh;
@@ -216,7 +209,7 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
     const uint32_t lanes = std::max<uint32_t>(ra.count, 3u * R.hotCount);
     hipLaunchKernelGGL(refit_finish_kernel, dim3((lanes + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, ra, tris, wnodes, R.rootOut,
                        R.hotOrder, R.hotCount, const_cast<float4*>(c->sc.hotNodes));
-    int rc = launch_error("refit_finish_kernel");
+    int rc = prt_launched("refit_finish_kernel");
     if (rc) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
     return PRT_HIP_OK;
@@ -332,18 +325,10 @@ int prt_hip_update_meshes(prt_hip_ctx* c, uint32_t count, const prt_mesh_update*
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = staging_ready(c, count, updates))) return rc;
-    hipStream_t s = c->stream;
-    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evIn, caller));
-        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
-    }
-    if ((rc = queue_update(c, count, updates, s, nullptr))) return rc;
+    hipStream_t s = c->stream, caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = queue_update(c, count, updates, s, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(c->rf.rootHost, c->rf.rootOut, PRT_MAX_BVH * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evOut, s));
-        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
-    }
+    if ((rc = prt_stream_leave(c, caller))) return rc;
     HIP_TRY(hipStreamSynchronize(s)); // the root boxes are part of DevScene, which every later launch takes by value
     for (uint32_t k = 0; k < count; k++) {
         memcpy(c->sc.rootBox[updates[k].mesh], c->rf.rootHost + 6 * updates[k].mesh, 6 * sizeof(float));

@@ -227,13 +227,6 @@ __global__ __launch_bounds__(TP_TILE_X * TP_TILE_Y) void tp_merge_kernel(MergeAr
 }
 
 // ============================================================================ host side
-int launched(const char* what)
-{
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return fail(PRT_HIP_ELAUNCH, std::string(what) + " launch: " + hipGetErrorString(le));
-    return PRT_HIP_OK;
-}
-
 int check_temporal(const prt_temporal_params* t)
 {
     if (!std::isfinite(t->positionTolerance) || !(t->positionTolerance > 0.0f))
@@ -305,7 +298,7 @@ int position_ready(prt_hip_ctx* c, bool force = false)
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
     PosArgs A{c->sc, c->cam, c->tpPos, c->work, c->spill, c->spillThreads, c->counters};
     hipLaunchKernelGGL(position_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
-    if ((rc = launched("position_kernel"))) return rc;
+    if ((rc = prt_launched("position_kernel"))) return rc;
     c->timed = false;
     c->tpPosValid = true;
     return PRT_HIP_OK;
@@ -347,7 +340,7 @@ int run_merge(prt_hip_ctx* c, const prt_denoise_params* d, const prt_temporal_pa
     A.maxHistory = t->maxHistory;
     const dim3 grid((W + TP_TILE_X - 1) / TP_TILE_X, (H + TP_TILE_Y - 1) / TP_TILE_Y);
     hipLaunchKernelGGL(tp_merge_kernel, grid, dim3(TP_TILE_X * TP_TILE_Y), 0, c->stream, A);
-    int rc = launched("tp_merge_kernel");
+    int rc = prt_launched("tp_merge_kernel");
     if (rc) return rc;
     c->tpHavePend = true;
     memcpy(&c->tpPendCam, &c->cam, sizeof(prt_camera_desc));
@@ -441,21 +434,11 @@ int prt_hip_accum_denoise_temporal(prt_hip_ctx* c, const prt_denoise_params* d, 
     int rc = temporal_checks(c, d, t);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    hipStream_t caller = (stream && (hipStream_t)stream != c->stream) ? (hipStream_t)stream : nullptr;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evIn, caller));
-        HIP_TRY(hipStreamWaitEvent(s, c->evIn, 0));
-    }
-    if ((rc = temporal_inputs(c, d))) return rc;
-    if (!d_rgb && (rc = prt_denoise_own_framebuffer(c, &d_rgb))) return rc;
-    if ((rc = run_merge(c, d, t))) return rc;
-    if ((rc = prt_denoise_iterations(c, d, exposure, d_rgb, nullptr))) return rc;
-    if (caller) {
-        HIP_TRY(hipEventRecord(c->evOut, s));
-        HIP_TRY(hipStreamWaitEvent(caller, c->evOut, 0));
-    }
-    return PRT_HIP_OK;
+    hipStream_t caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = temporal_inputs(c, d)) || (rc = prt_own_framebuffer(c, &d_rgb)) ||
+        (rc = run_merge(c, d, t)) || (rc = prt_denoise_iterations(c, d, exposure, d_rgb, nullptr)))
+        return rc;
+    return prt_stream_leave(c, caller);
 }
 
 int prt_hip_history_reset(prt_hip_ctx* c)
@@ -514,7 +497,7 @@ int prt_hip_test_temporal_profile(prt_hip_ctx* c, const prt_denoise_params* d, c
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     float* rgb = nullptr;
-    if ((rc = temporal_inputs(c, d)) || (rc = prt_denoise_own_framebuffer(c, &rgb))) return rc;
+    if ((rc = temporal_inputs(c, d)) || (rc = prt_own_framebuffer(c, &rgb))) return rc;
     hipEvent_t ev[4] = {};
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
     hipStream_t s = c->stream;

@@ -1,6 +1,7 @@
 """Progressive rendering on the MI355X (include/prt_hip.h "progressive rendering"): after accumulate passes of s1, ..., sk samples
 the image is, bit for bit, the one-shot render of s1 + ... + sk samples -- so every check below compares bit patterns (tolerance
 0) with a one-shot render, the oracle, or the oracle's whole-frame digests."""
+import ctypes as C
 import hashlib
 import os
 
@@ -206,3 +207,45 @@ def test_rules(tracer, c1_scene):
     assert_bits_equal(img, tracer.render(32), "render_progressive(32)")
     _, reached = tracer.render_progressive(64, step=8, budget_ms=0.0)
     assert reached == 8  # a pass always runs; the budget is checked after it
+
+
+def test_passes_on_a_callers_stream(tracer):
+    """Accumulate, adaptive, resolve and G-buffer into an explicit target on a caller's stream: each result is there when that
+    stream gets to its copy, bit for bit the one of the same step on the context's own stream and framebuffer."""
+    W = H = 64
+    scene, camera, _ = prt_amd.setup_cornell_box(W, H)
+    upload(tracer, scene, camera)
+    tracer.seed = 12345
+    L, ctx = prt_amd.lib(), tracer._ctx
+    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
+    nbytes = H * W * 3 * 4
+    stream, target = C.c_void_p(), C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
+    got = [np.zeros((H, W, 3), np.float32) for _ in range(4)]
+
+    def copy_out(k):  # queued on the caller's stream only
+        assert hip.hipMemcpyAsync(got[k].ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
+
+    try:
+        assert hip.hipMemsetAsync(target, 0xff, C.c_size_t(nbytes), stream) == 0
+        tracer.accumulate_async(16, d_rgb=target.value, stream=stream.value, tile=16)
+        copy_out(0)
+        active = tracer.adaptive_pass_async(16, 0.0, 16, 64, d_rgb=target.value, stream=stream.value, tile=16)
+        copy_out(1)
+        assert L.prt_hip_accum_resolve(ctx, 0, 0, W - 1, H - 1, 1.0, target, stream) == 0, L.prt_hip_last_error()
+        copy_out(2)
+        assert L.prt_hip_render_gbuffer(ctx, 0, 0, W - 1, H - 1, 0, tracer.seed, 1.0, target, stream) == 0, L.prt_hip_last_error()
+        copy_out(3)
+        assert hip.hipStreamSynchronize(stream) == 0
+    finally:
+        hip.hipFree(target)
+        hip.hipStreamDestroy(stream)
+    assert active > 0  # the launch path of the adaptive pass, not the empty one
+    tracer.accum_reset()
+    want = [tracer.accumulate(16, tile=16)]
+    img, active_own = tracer.adaptive_pass(16, 0.0, 16, 64, tile=16)
+    want += [img, tracer.accum_resolve(1.0), tracer.gbuffer(0)]
+    assert active_own == active
+    for k, what in enumerate(("accumulate", "adaptive", "resolve", "gbuffer")):
+        assert not (bits(got[k]) == 0xffffffff).any(), f"{what}: the caller's buffer still holds its fill"
+        assert_bits_equal(got[k], want[k], f"{what} on a caller's stream")
