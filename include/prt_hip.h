@@ -219,7 +219,7 @@ typedef struct {
     uint32_t seed, maxDepth, rrDepth; /* the estimator the accumulated samples came from (0 when the accumulator is empty) */
 } prt_accum_info;
 /* Empties the accumulator (every count 0) and unbinds the estimator.  prt_hip_set_camera and prt_hip_upload_scene do the same, and so
- * does prt_hip_update_meshes. */
+ * does prt_hip_update_meshes.  So do prt_hip_update_lights, prt_hip_update_materials and prt_hip_update_textures ("scene edits"). */
 int prt_hip_accum_reset(prt_hip_ctx* ctx);
 /* One pass: every pixel of the rectangle (or of rank's tiles in it) renders params->samples more samples, starting from its
  * record (a pixel with count 0 is seeded as prt_hip_render seeds it), stores its state, sum and count back and writes
@@ -494,6 +494,75 @@ typedef struct {
                               * updates in one call the last non-zero one holds */
 } prt_mesh_update;
 int prt_hip_update_meshes(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, void* stream);
+
+/* ---- scene edits: the lights, single materials and the texels of single textures of the uploaded scene, replaced in place.  Everything
+ * else that changes in a look-dev session -- the sun, the environment map, a material colour, a repainted texture -- without the
+ * flattening and the copies of a whole prt_hip_upload_scene.  The contract of all three calls: after the call the context is in exactly
+ * the state prt_hip_upload_scene produces from the uploaded descriptor with these fields replaced; every device array is the same
+ * byte for byte.  Where the upload takes host-built environment tables, that is the state of the tables InfiniteAreaLight::create
+ * builds (light.cpp:30-84).  stream as in prt_hip_update_meshes: the edit is ordered after the work queued on it; host pointers are
+ * copied during the call, which SYNCHRONISES the context's stream once (an update of the directional fields alone does not).
+ * Refusals: PRT_HIP_ESTATE without a scene, PRT_HIP_EINVAL with a message otherwise.  A refused call changes nothing.
+ *
+ * Lights.  The directional fields are always applied.  envMode:
+ *     PRT_HIP_ENV_KEEP     leaves the environment light as it is, present or absent;
+ *     PRT_HIP_ENV_NONE     removes it and releases its buffers;
+ *     PRT_HIP_ENV_REPLACE  takes a new image of any size and builds the vertical table, the horizontal table and the first-step
+ *                          constants of the bisection on the DEVICE (prt_edit.hip), from the texels alone, in the reference's arithmetic:
+ *         l = sqrtf((r*r + g*g) + b*b);  hsum added in x order from 0.0f;  sinPhi = sin(kPi * (y + 0.5f) / height) (the kernels' own sine);
+ *         vert[y] = hsum * sinPhi, vsum added in y order;  invH = 1.0f / hsum, ph = accumH + invH * l running in x order;
+ *         invV = 1.0f / vsum, pv = accumV + invV * vert[y] running in y order
+ *     all f32, no FMA, correctly rounded / and sqrtf.  The additions are SEQUENTIAL along a row and along the column: float addition is
+ *     not associative, so neither a tree reduction nor a parallel scan is used for them; the parallelism is across rows, and within
+ *     a row in the loads and the lengths.  The device refuses what the upload refuses in host-built tables -- a vertical table that is
+ *     not non-decreasing, a partly NaN row, a row that is not non-decreasing (a NaN texel, a +inf texel and an all-black map end
+ *     there) -- and accepts an all-NaN row (a black row), so the accepted maps are exactly the upload's; more than 2^28 texels and a NULL
+ *     image are refused.  The tables are built into new buffers and swapped in once the flags are back, so a refused map leaves the old
+ *     light in place.
+ *
+ * Materials.  The record of (mesh, material) is rewritten by the function that wrote it at upload.  Refused: count 0, an index out of
+ * range, the same (mesh, material) twice in one call, an alphaTest other than the uploaded value, another diffuseMap for a
+ * material uploaded with alphaTest (the alpha records and the leaf flags are per triangle and fixed at upload), a map index >=
+ * textureCount, bumpMap >= 0 in a scene uploaded without any bump-mapped material (it has no bump records), reflectionType > 2.
+ *
+ * Textures.  The texels of texture `texture` are replaced; width, height and component must equal the uploaded ones.  The alpha cell
+ * classes of a texture that an alpha-tested material names are rebuilt on the device by the upload's rule.  A texture may appear only
+ * once per call.
+ *
+ * What the calls invalidate (the samples of the old radiance):
+ *   - all three empty the accumulator and the moments and unbind the estimator, as prt_hip_accum_reset does;
+ *   - all three drop the temporal history AND the pending record, as prt_hip_history_reset does: radiance changes everywhere the edit is
+ *     seen, directly or indirectly, and the position and normal tests of the merge cannot see that.  A host that prefers the biased
+ *     preview exports the history before the edit (prt_hip_history_export) and imports it afterwards;
+ *   - prt_hip_update_lights leaves the denoise guides, the position plane and planes the host had set untouched: none depends on a light;
+ *   - prt_hip_update_materials and prt_hip_update_textures treat them as prt_hip_update_meshes does: guides and position plane go stale
+ *     and are rendered again on next use, planes a host had set are dropped;
+ *   - prt_hip_render after any of the calls renders the edited scene. ---- */
+#define PRT_HIP_ENV_KEEP 0     /* leave the environment light as it is (present or absent) */
+#define PRT_HIP_ENV_NONE 1     /* remove it */
+#define PRT_HIP_ENV_REPLACE 2  /* new image, any size; tables built on the device */
+typedef struct {
+    uint32_t hasDirectionalLight; /* as in prt_scene_desc; always applied */
+    float lightDir[3];
+    float lightIntensity[3];
+    uint32_t envMode;             /* PRT_HIP_ENV_* */
+    int32_t envWidth, envHeight;  /* PRT_HIP_ENV_REPLACE only */
+    const float* envTexels;       /* host, 4*envWidth*envHeight floats, row 0 first; PRT_HIP_ENV_REPLACE only */
+} prt_light_update;
+int prt_hip_update_lights(prt_hip_ctx* ctx, const prt_light_update* update, void* stream);
+
+typedef struct {
+    uint32_t mesh, material; /* indices into prt_scene_desc.meshes and that mesh's materials */
+    prt_material value;
+} prt_material_update;
+int prt_hip_update_materials(prt_hip_ctx* ctx, uint32_t count, const prt_material_update* updates, void* stream);
+
+typedef struct {
+    uint32_t texture;                 /* index into prt_scene_desc.textures of the uploaded scene */
+    int32_t width, height, component; /* must equal the uploaded texture's */
+    const uint8_t* texels;            /* host, width*height*component bytes (the library copies) */
+} prt_texture_update;
+int prt_hip_update_textures(prt_hip_ctx* ctx, uint32_t count, const prt_texture_update* updates, void* stream);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,22 @@ int prt_hip_test_refit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_
  * prt_hip_stats.occludedTraced and raysTraced, which count the reference's rays; 0 for a render with countTraffic, which walks every
  * ray.  Synchronous. */
 int prt_hip_test_occlusion_skipped(prt_hip_ctx* ctx, uint64_t* skipped);
+/* The device arrays a scene edit ("scene edits" in prt_hip.h) can change, as they stand, to host buffers (any of them may be NULL):
+ * counts[0] material records (20 floats each), [1] alpha class words, [2] texel bytes, [3] / [4] width / height of the environment map
+ * (0 without one: envTexels 4 floats, envHorizontal 1 float per texel, envVertical and envFirstX one entry per row); the scalars of
+ * DevScene beside them.  Call it with NULL buffers for the counts first.  Synchronous. */
+int prt_hip_test_shading_arrays(prt_hip_ctx* ctx, uint64_t counts[5], float* mats, uint32_t* alphaClass, uint8_t* texels, float* envTexels,
+                                float* envVertical, float* envHorizontal, int32_t* envFirstX, int32_t* envFirstY, uint32_t* hasLight,
+                                float* lightDir, float* lightIntensity, uint32_t* hasEnv);
+/* The arithmetic the environment kernels run (prt_envcdf.h), on the HOST: the two tables, firstX[height], *firstY and the refusal flags
+ * (1 vertical table not non-decreasing, 2 partly NaN row, 4 row not non-decreasing; 0 = the map is accepted) of a width x height
+ * float RGBA image.  Takes no context and needs no device. */
+int prt_hip_test_env_tables_host(int32_t width, int32_t height, const float* rgba, float* vertical, float* horizontal, int32_t* firstX,
+                                 int32_t* firstY, uint32_t* flags);
+/* tools/scene_edit_bench.py: HIP-event times on the context's stream, medians of `reps`: ms[0] = the two kernels that build the tables of
+ * the context's own environment map again, into scratch buffers (0 without one); ms[1] = the class kernels of the named textures, whose
+ * texels are copied first (count 0: ms[1] = 0).  Ends with one real update of those textures.  Synchronous. */
+int prt_hip_test_edit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_texture_update* updates, uint32_t reps, float* ms2);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,14 @@ void prt_host_scene_bbox(const prt_host_scene* s, float lowerUpper[6]);
  * recomputed as Scene::add computes them (scene.cpp:23-26).  PRT_HIP_EINVAL for a bad index, another vertexCount, NULL positions or
  * normals for a mesh without.  The descriptor of prt_host_scene_describe afterwards is the updated scene's. */
 int prt_host_scene_update_positions(prt_host_scene* s, uint32_t mesh, uint32_t vertexCount, const float* positions, const float* normals);
+/* Scene::setMaterial / Scene::setTextureTexels (additions too): material `material` of mesh `mesh` takes the fields of *value, whose
+ * diffuseMap / bumpMap name textures by their index in the descriptor of prt_host_scene_describe as it stands (-1 = none); the bytes
+ * of texture `texture` (same numbering, unchanged size: width * height * component bytes) are replaced for every material that
+ * shares it.  PRT_HIP_EINVAL for a bad index or a NULL pointer.  A prt_hip_upload_scene of the descriptor afterwards gives the state
+ * prt_hip_update_materials / prt_hip_update_textures give in place, as long as the edit leaves the order in which the materials first
+ * name the textures alone (that order numbers them). */
+int prt_host_scene_set_material(prt_host_scene* s, uint32_t mesh, uint32_t material, const prt_material* value);
+int prt_host_scene_set_texture_texels(prt_host_scene* s, uint32_t texture, const uint8_t* texels);
 
 /* Image::saveExr (image.cpp:82-139: half-float B,G,R OpenEXR) and Image::savePpm (image.cpp:52-80: tone map, gamma, 8 bit)
  * for a float RGB image of width*height*3 values, row 0 first; 0 or -1 */

@@ -112,6 +112,22 @@ class MeshUpdate(C.Structure):
                 ("radius", C.c_float)]
 
 
+class LightUpdate(C.Structure):
+    _fields_ = [("hasDirectionalLight", C.c_uint32), ("lightDir", C.c_float * 3), ("lightIntensity", C.c_float * 3),
+                ("envMode", C.c_uint32), ("envWidth", C.c_int32), ("envHeight", C.c_int32), ("envTexels", C.POINTER(C.c_float))]
+
+    ENV_KEEP, ENV_NONE, ENV_REPLACE = 0, 1, 2
+
+
+class MaterialUpdate(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("material", C.c_uint32), ("value", Material)]
+
+
+class TextureUpdate(C.Structure):
+    _fields_ = [("texture", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("component", C.c_int32),
+                ("texels", C.POINTER(C.c_uint8))]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -133,6 +149,8 @@ EXPORTS = [
     "prt_hip_denoise_set_guides", "prt_hip_denoise_get_guides", "prt_hip_accum_denoise", "prt_hip_denoise_variance",
     "prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
     "prt_hip_history_export", "prt_hip_history_import", "prt_hip_update_meshes",
+    "prt_hip_update_lights", "prt_hip_update_materials", "prt_hip_update_textures",
+    "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
     "prt_host_mesh_calculate_bounds", "prt_host_mesh_prim_count", "prt_host_scene_create", "prt_host_scene_destroy",
@@ -143,7 +161,8 @@ EXPORTS = [
 # include/prt_hip_test.h: row-level entry points of the TEST build of the library (libprt_hip_test.so); the product does not export them
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
-                "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped"]
+                "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
+                "prt_hip_test_edit_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -232,7 +251,13 @@ def _load(path, with_test_entry_points):
     L.prt_hip_history_export.argtypes = [vp, C.c_uint32, C.POINTER(CameraDesc), vp, vp, vp]
     L.prt_hip_history_import.argtypes = [vp, C.POINTER(CameraDesc), vp, vp, vp]
     L.prt_hip_update_meshes.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), vp]
+    L.prt_hip_update_lights.argtypes = [vp, C.POINTER(LightUpdate), vp]
+    L.prt_hip_update_materials.argtypes = [vp, C.c_uint32, C.POINTER(MaterialUpdate), vp]
+    L.prt_hip_update_textures.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), vp]
     if with_test_entry_points:
+        L.prt_hip_test_shading_arrays.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 12
+        L.prt_hip_test_env_tables_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+        L.prt_hip_test_edit_profile.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), C.c_uint32, vp]
         L.prt_hip_test_scene_arrays.argtypes = [vp, C.POINTER(C.c_uint64), vp, vp, vp, vp, vp, vp, vp]
         L.prt_hip_test_refit_profile.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), C.c_uint32, vp]
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
@@ -277,6 +302,8 @@ def _load(path, with_test_entry_points):
     L.prt_host_scene_bbox.argtypes = [vp, f32p]
     L.prt_host_scene_bbox.restype = None
     L.prt_host_scene_update_positions.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.prt_host_scene_set_material.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(Material)]
+    L.prt_host_scene_set_texture_texels.argtypes = [vp, C.c_uint32, vp]
     L.prt_host_camera_create.argtypes = [f32p, f32p, C.c_uint32, C.c_uint32, C.POINTER(CameraDesc)]
     L.prt_host_camera_create.restype = None
     L.prt_host_bvh_build.argtypes = [C.c_uint32, vp, vp, C.c_int, C.POINTER(C.POINTER(BvhNode)), u32p, C.POINTER(u32p)]
@@ -388,6 +415,25 @@ class Scene:
         _check(lib().prt_host_scene_update_positions(self._h, mesh, len(p), p.ctypes.data_as(C.c_void_p),
                                                      None if n is None else n.ctypes.data_as(C.c_void_p)), "prt_host_scene_update_positions")
 
+    def set_material(self, mesh, material, value):
+        """Scene::setMaterial: material `material` of mesh `mesh` takes the fields of `value` (a Material, or one element of a
+        MATERIAL_DTYPE array); diffuseMap / bumpMap name textures in describe() order (-1 = none).  PathTracer.update_materials sends
+        it to the device without a new upload."""
+        if not isinstance(value, Material):
+            value = Material.from_buffer_copy(np.asarray(value, dtype=MATERIAL_DTYPE).tobytes())
+        _check(lib().prt_host_scene_set_material(self._h, mesh, material, C.byref(value)), "prt_host_scene_set_material")
+
+    def set_texture_texels(self, texture, texels):
+        """Scene::setTextureTexels: new bytes ((height, width, component) uint8, size unchanged) for texture `texture` in describe() order."""
+        d = self.describe().contents
+        if not 0 <= texture < d.textureCount:
+            raise PrtError(f"set_texture_texels: the scene has no texture {texture}")
+        t = d.textures[texture]
+        a = np.ascontiguousarray(texels, dtype=np.uint8)
+        if a.size != t.width * t.height * t.component:
+            raise PrtError(f"set_texture_texels: {a.size} bytes for a {t.width} x {t.height} x {t.component} texture")
+        _check(lib().prt_host_scene_set_texture_texels(self._h, texture, a.ctypes.data_as(C.c_void_p)), "prt_host_scene_set_texture_texels")
+
     def bbox(self):
         b = (C.c_float * 6)()
         lib().prt_host_scene_bbox(self._h, b)
@@ -498,6 +544,66 @@ class PathTracer:
             ups[k].radius = d.radius
         self._chk(self._L.prt_hip_update_meshes(self._ctx, len(ids), ups, stream), "prt_hip_update_meshes")
         self._scene = scene
+
+    # ---- scene edits (include/prt_hip.h "scene edits"): lights, materials and texels of the uploaded scene, replaced in place
+    def update_lights(self, scene, env=True, stream=None):
+        """prt_hip_update_lights: send the Scene's lights as describe() reports them.  env=True replaces the environment light by the
+        Scene's (tables built on the device) or removes it when the Scene has none; env=False leaves the device's as it is."""
+        d = scene.describe().contents
+        u = LightUpdate()
+        u.hasDirectionalLight = d.hasDirectionalLight
+        u.lightDir[:] = d.lightDir[:]
+        u.lightIntensity[:] = d.lightIntensity[:]
+        u.envMode = LightUpdate.ENV_KEEP
+        if env:
+            u.envMode = LightUpdate.ENV_REPLACE if d.hasInfiniteAreaLight else LightUpdate.ENV_NONE
+            if d.hasInfiniteAreaLight:
+                u.envWidth, u.envHeight, u.envTexels = d.envWidth, d.envHeight, d.envTexels
+        self._chk(self._L.prt_hip_update_lights(self._ctx, C.byref(u), stream), "prt_hip_update_lights")
+        self._scene = scene
+
+    def update_materials(self, scene, which, stream=None):
+        """prt_hip_update_materials: send the CURRENT materials `which` = [(mesh, material), ...] of the Scene (after
+        Scene.set_material) to the device."""
+        d = scene.describe().contents
+        ups = (MaterialUpdate * max(len(which), 1))()
+        for k, (m, i) in enumerate(which):
+            if not (0 <= m < d.meshCount and 0 <= i < d.meshes[m].materialCount):
+                raise PrtError(f"update_materials: the scene has no material {i} of mesh {m}")
+            ups[k].mesh, ups[k].material, ups[k].value = m, i, d.meshes[m].materials[i]
+        self._chk(self._L.prt_hip_update_materials(self._ctx, len(which), ups, stream), "prt_hip_update_materials")
+        self._scene = scene
+
+    def update_textures(self, scene, textures, stream=None):
+        """prt_hip_update_textures: send the CURRENT texels of the Scene's textures `textures` (indices in describe() order, after
+        Scene.set_texture_texels) to the device."""
+        d = scene.describe().contents
+        ups = (TextureUpdate * max(len(textures), 1))()
+        for k, t in enumerate(textures):
+            if not 0 <= t < d.textureCount:
+                raise PrtError(f"update_textures: the scene has no texture {t}")
+            td = d.textures[t]
+            ups[k].texture, ups[k].width, ups[k].height, ups[k].component, ups[k].texels = t, td.width, td.height, td.component, td.texels
+        self._chk(self._L.prt_hip_update_textures(self._ctx, len(textures), ups, stream), "prt_hip_update_textures")
+        self._scene = scene
+
+    def shading_arrays(self):
+        """Test build only: what a scene edit can change on the device, as dict(mats (M, 20) f32, alpha_class (words,) u32, texels
+        (bytes,) u8, env_texels (h, w, 4), env_vertical (h,), env_horizontal (h * w,) f32, env_first_x (h,) i32 (empty without an
+        environment light), env_first_y, has_light, has_env, light_dir (3,), light_intensity (3,))."""
+        self._need_row_level()
+        counts = (C.c_uint64 * 5)()
+        self._chk(self._L.prt_hip_test_shading_arrays(self._ctx, counts, *([None] * 12)), "prt_hip_test_shading_arrays")
+        m, cw, tb, w, h = [int(x) for x in counts]
+        out = dict(mats=np.zeros((m, 20), np.float32), alpha_class=np.zeros(cw, np.uint32), texels=np.zeros(tb, np.uint8),
+                   env_texels=np.zeros((h, w, 4), np.float32), env_vertical=np.zeros(h, np.float32), env_horizontal=np.zeros(h * w, np.float32),
+                   env_first_x=np.zeros(h, np.int32), env_first_y=np.zeros(1, np.int32), has_light=np.zeros(1, np.uint32),
+                   light_dir=np.zeros(3, np.float32), light_intensity=np.zeros(3, np.float32), has_env=np.zeros(1, np.uint32))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self._L.prt_hip_test_shading_arrays(self._ctx, counts, *[ptr(out[k]) for k in (
+            "mats", "alpha_class", "texels", "env_texels", "env_vertical", "env_horizontal", "env_first_x", "env_first_y", "has_light",
+            "light_dir", "light_intensity", "has_env")]), "prt_hip_test_shading_arrays")
+        return out
 
     def scene_arrays(self):
         """Test build only: the device scene arrays as dict(wnodes (R, 16), hot (256, 16), tris (S, 9), shade (S, 16), bump (S or 0, 12),
@@ -918,6 +1024,20 @@ class PathTracer:
         out = np.zeros(92, dtype=np.float32)
         self._chk(self._L.prt_hip_test_camera(self._ctx, x, y, state, out.ctypes.data_as(C.c_void_p)), "prt_hip_test_camera")
         return out
+
+
+def env_tables_host(env):
+    """Test build only: prt_hip_test_env_tables_host -- the arithmetic of the environment kernels on the host, for an (h, w, 4) float
+    RGBA image: (vertical (h,), horizontal (h * w,), first_x (h,) int32, first_y, flags)."""
+    e = np.ascontiguousarray(env, dtype=np.float32)
+    h, w, _ = e.shape
+    v, hor, fx = np.zeros(h, np.float32), np.zeros(h * w, np.float32), np.zeros(h, np.int32)
+    fy, flags = C.c_int32(), C.c_uint32()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rc = test_lib().prt_hip_test_env_tables_host(w, h, ptr(e), ptr(v), ptr(hor), ptr(fx), C.addressof(fy), C.addressof(flags))
+    if rc != 0:
+        raise PrtError(f"prt_hip_test_env_tables_host failed ({rc}): {test_lib().prt_hip_last_error().decode()}")
+    return v, hor, fx, fy.value, flags.value
 
 
 def device_count():

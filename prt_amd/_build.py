@@ -19,6 +19,7 @@ SOURCES = [
     "prt_denoise.hip",
     "prt_temporal.hip",
     "prt_refit.hip",
+    "prt_edit.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

@@ -215,6 +215,11 @@ public:
     // vertex count stays.  The tree keeps its shape and every node box is refitted bottom up; bounds and radius follow as in add().
     // False (nothing changed) for a bad index, or normals for a mesh without vertex normals.
     bool updatePositions(uint32_t meshIndex, const Vector3f* positions, const Vector3f* normals = nullptr);
+    // Not in the reference either: material `material` of the mesh of m_bvh[meshIndex] takes the fields of `value`; its map indices
+    // name textures in describe() order (-1 = none).  setTextureTexels replaces the bytes of texture `texture` (same order, same
+    // size) for every material that shares it.  False (nothing changed) for a bad index.
+    bool setMaterial(uint32_t meshIndex, uint32_t material, const prt_material& value);
+    bool setTextureTexels(uint32_t texture, const uint8_t* texels);
     float getRadius() const { return m_radius; }
     const BBox& getBBox() const { return m_bbox; }
     const std::vector<Bvh*>& getBvhs() const { return m_bvh; }

@@ -183,6 +183,50 @@ bool Scene::updatePositions(uint32_t meshIndex, const Vector3f* positions, const
     return true;
 }
 
+bool Scene::setMaterial(uint32_t meshIndex, uint32_t material, const prt_material& value)
+{
+    if (meshIndex >= m_bvh.size()) return false;
+    Mesh& mesh = m_bvh[meshIndex]->m_mesh;
+    if (material >= mesh.getMaterialCount()) return false;
+    prt_scene_desc desc;
+    DescStorage store;
+    describe(desc, store); // the textures in the order an upload numbers them
+    const int32_t textures = (int32_t)store.textures.size();
+    if (value.diffuseMap >= textures || value.bumpMap >= textures) return false;
+    auto textureOf = [&](int32_t index) {
+        Texture t;
+        t.init();
+        if (index >= 0) {
+            t.width = (uint16_t)store.textures[index].width;
+            t.height = (uint16_t)store.textures[index].height;
+            t.component = (uint8_t)store.textures[index].component;
+            t.texels = store.texelRefs[index];
+        }
+        return t;
+    };
+    Material& m = mesh.m_materials[material];
+    m.diffuse = Vector3f(value.diffuse[0], value.diffuse[1], value.diffuse[2]);
+    m.emissive = Vector3f(value.emissive[0], value.emissive[1], value.emissive[2]);
+    m.reflectionType = (ReflectionType)value.reflectionType;
+    m.alphaTest = value.alphaTest != 0;
+    m.diffuseMap = textureOf(value.diffuseMap);
+    m.bumpMap = textureOf(value.bumpMap);
+    m_revision = nextRevision();
+    return true;
+}
+
+bool Scene::setTextureTexels(uint32_t texture, const uint8_t* texels)
+{
+    prt_scene_desc desc;
+    DescStorage store;
+    describe(desc, store);
+    if (texture >= store.texelRefs.size() || !texels) return false;
+    std::vector<uint8_t>& bytes = *store.texelRefs[texture];
+    std::copy(texels, texels + bytes.size(), bytes.begin());
+    m_revision = nextRevision();
+    return true;
+}
+
 void Scene::setDirectionalLight(const Vector3f& dir, const Vector3f& intensity) // scene.h:30-35
 {
     m_directionalLight = {dir, intensity};

@@ -147,6 +147,18 @@ int prt_host_scene_update_positions(prt_host_scene* s, uint32_t mesh, uint32_t v
                                                                                                                                   : PRT_HIP_EINVAL;
 }
 
+int prt_host_scene_set_material(prt_host_scene* s, uint32_t mesh, uint32_t material, const prt_material* value)
+{
+    if (!s || !value) return PRT_HIP_EINVAL;
+    return s->scene.setMaterial(mesh, material, *value) ? PRT_HIP_OK : PRT_HIP_EINVAL;
+}
+
+int prt_host_scene_set_texture_texels(prt_host_scene* s, uint32_t texture, const uint8_t* texels)
+{
+    if (!s || !texels) return PRT_HIP_EINVAL;
+    return s->scene.setTextureTexels(texture, texels) ? PRT_HIP_OK : PRT_HIP_EINVAL;
+}
+
 static int saveImage(const char* path, uint32_t w, uint32_t h, const float* rgb, bool tonemap, bool exr, bool zip)
 {
     if (!path || !rgb || w == 0 || h == 0) return -1;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -57,6 +58,19 @@ struct PrtRefit {
     float* rootHost = nullptr;     // pinned host copy of it
 };
 
+// Scene edits (prt_edit.hip): what the checks of prt_hip_update_materials / prt_hip_update_textures need from the upload, kept on the host.
+struct PrtEditMesh {
+    uint32_t matBase = 0;                // first record of the mesh in DevScene::mats
+    std::vector<prt_material> materials; // as uploaded, then as last updated
+};
+struct PrtEdit {
+    std::vector<PrtEditMesh> meshes;
+    std::vector<uint4> texDesc;        // per texture: {offset in DevScene::texels, width, height, component}
+    std::vector<uint32_t> classWordOf; // per texture: first word of its alpha cell classes, 0xffffffff = none were built
+    uint64_t matRecords = 0, classWords = 0, texelBytes = 0; // sizes of DevScene::mats (records), alphaClass (words), texels (bytes)
+    bool anyBump = false;              // the scene has bump records
+};
+
 struct prt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -75,6 +89,7 @@ struct prt_hip_ctx {
     DevCamera cam{};
     std::vector<void*> sceneAllocs;
     PrtRefit rf;                // device allocations of it are in sceneAllocs
+    PrtEdit ed;
     // render resources
     float* fb = nullptr;
     size_t fbPixels = 0;
@@ -169,6 +184,25 @@ int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1);
 int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
+// The ONE place that writes a material record (prt_hip_upload_scene, prt_hip_update_materials); its size is tied to the stride the
+// kernels index with (sample_diffuse, sample_bump, shade_kernel: sc.mats + PRT_MAT_STRIDE * material).  A record count and an index
+// stride that disagree read another material's fields as texture descriptors -- a wild texel address on the device.  texDesc: per
+// texture {offset, width, height, component}; the caller has checked both map indices against it.
+inline void prt_material_record(const prt_material& mt, const std::vector<uint4>& texDesc, float4* out)
+{
+    auto ubits = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    const uint4 dd = mt.diffuseMap >= 0 ? texDesc[mt.diffuseMap] : make_uint4(0, 0, 0, 0);
+    const uint4 bd = mt.bumpMap >= 0 ? texDesc[mt.bumpMap] : make_uint4(0, 0, 0, 0);
+    const float4 record[] = {
+        make_float4(mt.diffuse[0], mt.diffuse[1], mt.diffuse[2], ubits(mt.reflectionType)),
+        make_float4(mt.emissive[0], mt.emissive[1], mt.emissive[2], ubits(mt.alphaTest)),
+        make_float4(ubits((uint32_t)mt.diffuseMap), ubits((uint32_t)mt.bumpMap), 0.0f, 0.0f),
+        make_float4(ubits(dd.x), ubits(dd.y), ubits(dd.z), ubits(dd.w)),
+        make_float4(ubits(bd.x), ubits(bd.y), ubits(bd.z), ubits(bd.w)),
+    };
+    static_assert(sizeof(record) / sizeof(record[0]) == PRT_MAT_STRIDE, "material record size and PRT_MAT_STRIDE must agree");
+    for (int k = 0; k < PRT_MAT_STRIDE; k++) out[k] = record[k];
+}
 // Progressive rendering: the accumulator holds no samples from here on (its records are zeroed before their next use).
 inline void prt_accum_forget(prt_hip_ctx* c)
 {

@@ -49,6 +49,7 @@ void prt_free_scene(prt_hip_ctx* c)
     for (void* p : c->sceneAllocs) (void)hipFree(p);
     c->sceneAllocs.clear();
     prt_refit_forget(c);
+    c->ed = PrtEdit{};
     c->haveScene = false;
 }
 
@@ -128,6 +129,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     std::vector<uint32_t> slotVtx;           // 3 vertex ids per triangle slot, for prt_hip_update_meshes (prt_refit.hip)
     std::vector<PrtRefitMesh> refitMeshes;
     std::vector<uint32_t> hotOrder;
+    PrtEdit ed;
     DevScene sc{};
     sc.bvhCount = s->meshCount;
 
@@ -179,6 +181,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
         const uint32_t triBase = (uint32_t)(tris.size() / 9);
         const uint32_t primBase = (uint32_t)(shade.size() / 4), matBase = (uint32_t)(mats.size() / PRT_MAT_STRIDE);
         sc.primBase[m] = primBase;
+        ed.meshes.push_back(PrtEditMesh{matBase, std::vector<prt_material>(md.materials, md.materials + md.materialCount)});
         sc.hasNormals[m] = md.normals ? 1u : 0u;
         auto P = [&](uint32_t v) { return HVec3{md.positions[3 * v], md.positions[3 * v + 1], md.positions[3 * v + 2]}; };
         for (uint32_t k = 0; k < md.materialCount; k++) {
@@ -186,19 +189,8 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
             if (mt.diffuseMap >= (int32_t)s->textureCount || mt.bumpMap >= (int32_t)s->textureCount)
                 return fail(PRT_HIP_EINVAL, "material texture index out of range");
             if (mt.alphaTest && mt.diffuseMap < 0) return fail(PRT_HIP_EINVAL, "alphaTest material without a diffuse map");
-            // ONE place writes a material record and its size is tied to the stride the kernels index with (sample_diffuse,
-            // sample_bump, shade_kernel: sc.mats + PRT_MAT_STRIDE * material).  A record count and an index stride that
-            // disagree read another material's fields as texture descriptors -- a wild texel address on the device.
-            const uint4 dd = mt.diffuseMap >= 0 ? texDesc[mt.diffuseMap] : make_uint4(0, 0, 0, 0);
-            const uint4 bd = mt.bumpMap >= 0 ? texDesc[mt.bumpMap] : make_uint4(0, 0, 0, 0);
-            const float4 record[] = {
-                make_float4(mt.diffuse[0], mt.diffuse[1], mt.diffuse[2], ubits(mt.reflectionType)),
-                make_float4(mt.emissive[0], mt.emissive[1], mt.emissive[2], ubits(mt.alphaTest)),
-                make_float4(ubits((uint32_t)mt.diffuseMap), ubits((uint32_t)mt.bumpMap), 0.0f, 0.0f),
-                make_float4(ubits(dd.x), ubits(dd.y), ubits(dd.z), ubits(dd.w)),
-                make_float4(ubits(bd.x), ubits(bd.y), ubits(bd.z), ubits(bd.w)),
-            };
-            static_assert(sizeof(record) / sizeof(record[0]) == PRT_MAT_STRIDE, "material record size and PRT_MAT_STRIDE must agree");
+            float4 record[PRT_MAT_STRIDE]; // (prt_internal.h: the one writer of a material record)
+            prt_material_record(mt, texDesc, record);
             mats.insert(mats.end(), record, record + PRT_MAT_STRIDE);
         }
         std::vector<uint32_t> slotOf, kOfSlot; // leaf-order index <-> slot in the device arrays (leaf_slots)
@@ -433,6 +425,13 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     c->sc = sc;
     for (uint32_t m = 0; m < sc.bvhCount; m++) refitMeshes[m].rootKid = sc.rootRef[m];
     if ((rc = prt_refit_build(c, wnodes, hotOrder, std::move(refitMeshes), slotVtx, anyBump))) return rc;
+    ed.matRecords = mats.size() / PRT_MAT_STRIDE;
+    ed.classWords = alphaClass.size();
+    ed.texelBytes = texels.size();
+    ed.anyBump = anyBump;
+    ed.texDesc = std::move(texDesc);
+    ed.classWordOf = std::move(classWordOf);
+    c->ed = std::move(ed);
     c->haveScene = true;
     return PRT_HIP_OK;
 }
