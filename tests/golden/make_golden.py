@@ -17,6 +17,8 @@ Outputs (all small, data only -- no reference source text):
   radiance_c1_crop.npz per-pixel radiance of a 64x64 crop of config C1 (512x512, 16 spp, depth cap 14) and of
                        Cornell-only 128x128x16spp, with ray counts (reference PathTracer::TraceBlock, hybrid link:
                        see oracle/ref_glue.cpp for which leaf functions are the oracle's)
+  hostile_rays.npz     the grid / twins / flat scenes of tests/prt_hostile.py for seeds 0-3: vertices, 1024 hostile rays each and the
+                       reference's Scene::intersect / Scene::occluded answers, single and packet
 """
 import os
 import struct
@@ -282,6 +284,28 @@ def dump_scene_digests():
     np.savez_compressed(os.path.join(HERE, "scene_digests.npz"), **out)
 
 
+def dump_hostile():
+    # tests/prt_hostile.py: snapped, duplicated and planar soups with rays on box planes, vertices and edges.  Vertices and rays are
+    # stored as generated, so that the tests do not depend on numpy's generator staying what it is.
+    import prt_hostile as H
+    out = {}
+    for name in H.SCENES:
+        for seed in H.SEEDS:
+            meshes, org, d, max_t = H.generate(name, seed)
+            _, _, desc = H.product_scene(meshes)
+            single, occ1, packet, occ8 = T.ref_rays(desc, org, d, max_t)
+            k = f"{name}{seed}_"
+            out.update({k + "verts": np.concatenate(meshes), k + "org": org, k + "dir": d, k + "max_t": np.float32(max_t),
+                        k + "single": single.view(np.uint8), k + "occluded_single": occ1.astype(np.uint8),
+                        k + "packet": packet.view(np.uint8), k + "occluded_packet": occ8.astype(np.uint8)})
+            print("hostile", name, seed, "single hits", int((single["t"] != -1).sum()), "packet hits", int((packet["t"] != -1).sum()),
+                  "occluded", int(occ1.sum()), int(occ8.sum()))
+    path = os.path.join(HERE, "hostile_rays.npz")
+    np.savez_compressed(path, **out)
+    # data only, and no larger than the largest fixture there is (halve the rays per scene if it ever is)
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "c5_tile_rows.npz")), os.path.getsize(path)
+
+
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", T.ORACLE_DIR])
     dump_cornell()
@@ -293,3 +317,4 @@ if __name__ == "__main__":
     dump_gbuffer()
     dump_c1_checksums()
     dump_scene_digests()
+    dump_hostile()
