@@ -1,13 +1,15 @@
 """Adaptive sampling on the MI355X (include/prt_hip.h "adaptive sampling").  An adaptive pass gives the pixels it selects exactly the
 samples an accumulate pass would give them, so every pixel holds, bit for bit, the one-shot render of its own sample count: the images,
 accumulator records and statistics below are compared with tolerance 0.  The selection is restated in numpy float32 (the build has no
-FMA) and must pick exactly the pixels the library picks; only the moment records, compared against packet sums recovered from
-accumulator differences, carry a rounding tolerance."""
+FMA, tests/prt_adaptive_ref.py) and must pick exactly the pixels the library picks; the moment records are compared word for word with
+the header's fold of exact packet sums, each exported by a pass that starts from a zeroed sum (test_gpu_adaptive_exact.py goes further:
+partly active passes, ranks, synthetic states)."""
 import numpy as np
 import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_adaptive_ref import active_set, luminance, np_error
 
 pytestmark = pytest.mark.gpu
 EXPOSURE, FLOOR = 1.0, 0.01
@@ -22,29 +24,6 @@ def assert_bits_equal(a, b, what=""):
     assert a.shape == b.shape, (what, a.shape, b.shape)
     bad = np.nonzero(a != b)
     assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
-
-
-def luminance(res):
-    """The packet-mean luminance of the header, in float32 and in its order."""
-    res = np.asarray(res, dtype=np.float32)
-    return (np.float32(0.2126) * res[..., 0] + np.float32(0.7152) * res[..., 1] + np.float32(0.0722) * res[..., 2]) * np.float32(0.125)
-
-
-def np_error(count, mom, exposure=EXPOSURE, floor=FLOOR):
-    """err of the header from an accumulator export's counts and a moment export, in float32."""
-    n = np.asarray(count, dtype=np.uint32)
-    mean, m2, m = mom[..., 0], mom[..., 1], mom[..., 2].view(np.uint32)
-    e, f = np.float32(exposure), np.float32(floor)
-    with np.errstate(all="ignore"):
-        var = m2 / (np.maximum(m, np.uint32(1)) - np.uint32(1)).astype(np.float32)
-        se = np.sqrt(var / (n >> 3).astype(np.float32))
-        err = (e * se) / (f + e * mean)
-    return np.where(m < 2, np.float32(np.inf), err).astype(np.float32)
-
-
-def active_set(count, err, samples, threshold, min_spp, max_spp):
-    n = count.astype(np.uint64)
-    return (n + samples <= max_spp) & ((n < min_spp) | (err > np.float32(threshold)))
 
 
 @pytest.fixture(scope="module")
@@ -191,22 +170,23 @@ def test_moments(tracer, c1_scene):
     for s in (8, 16, 8):
         tracer.adaptive_pass(s, 0.0, 64, 64, FLOOR, *rect, exposure=EXPOSURE)
     mom = tracer.accum_export_moments()[y0:y1 + 1, x0:x1 + 1]
-    # the same 40 samples in packets: an accumulate run of 8-spp passes, exported after each
+    # the same 40 samples in packets: an accumulate run of 8-spp passes, each from a sum set to +0 (state and count kept), so that the
+    # exported sum is the packet's own sum exactly
     tracer.accum_reset()
-    prev = np.zeros((y1 - y0 + 1, x1 - x0 + 1, 3), dtype=np.float32)
-    mean = np.zeros(prev.shape[:2], dtype=np.float32)
+    mean = np.zeros((y1 - y0 + 1, x1 - x0 + 1), dtype=np.float32)
     m2 = np.zeros_like(mean)
     for m in range(1, 6):
         tracer.accumulate(8, *rect, exposure=EXPOSURE)
-        cur = tracer.accum_export()["sum"][y0:y1 + 1, x0:x1 + 1]
-        L = luminance(cur - prev)
+        st = tracer.accum_export()
+        L = luminance(st["sum"][y0:y1 + 1, x0:x1 + 1])
         d = L - mean
         mean = mean + d / np.float32(m)
         m2 = m2 + d * (L - mean)
-        prev = cur
+        st["sum"] = np.zeros_like(st["sum"])
+        tracer.accum_import(st)
     assert (mom[..., 2].view(np.uint32) == 5).all()
-    np.testing.assert_allclose(mom[..., 0], mean, rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(mom[..., 1], m2, rtol=1e-3, atol=1e-6)
+    assert_bits_equal(mom[..., 0], mean, "mean over five packets vs the header's fold")
+    assert_bits_equal(mom[..., 1], m2, "M2 over five packets vs the header's fold")
     # plain accumulate passes neither read nor change the moments
     tracer.accum_reset()
     tracer.adaptive_pass(16, 0.0, 64, 64, FLOOR, *rect, exposure=EXPOSURE)
