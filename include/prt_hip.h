@@ -564,6 +564,81 @@ typedef struct {
 } prt_texture_update;
 int prt_hip_update_textures(prt_hip_ctx* ctx, uint32_t count, const prt_texture_update* updates, void* stream);
 
+/* ---- display transform: 8-bit display-referred pixels and auto exposure on the device.  Every stage above ends in a camera-sized float
+ * RGB image in device memory; a viewer shows bytes.  This stage turns such an image -- the context's framebuffer or a caller's -- into
+ * RGB8 / RGBA8 / BGRA8 on the device, under a manual gain or under an exposure METERED from the image's own luminance histogram and
+ * adapted over the frames.  It needs a camera (for the image size) and no scene, and it changes nothing else in the context: the
+ * accumulator, the moments, the guides, the history and the statistics are untouched, it is not a render for prt_hip_get_stats and
+ * takes no slot of the timing ring.  The only path to bytes without it is prt_hip_download (12 bytes per pixel) and the host loop of
+ * Image::savePpm (image.cpp:52-80); with meter 0, gain 1.0f, transfer 0 and format 0 the bytes here ARE the pixel block
+ * prt_host_save_ppm writes for the same floats.
+ *
+ * It is specified exactly, as the denoiser is: all arithmetic is f32, no FMA, correctly rounded /, subnormals kept, in the order
+ * written (prt_amd/csrc/prt_display.h is that text for the device and for the host check).
+ *     lum(c) = 0.2126f*c.x + 0.7152f*c.y + 0.0722f*c.z                                  (left to right)
+ * Metering (meter 1), over the rectangle of the INPUT image:
+ *     a pixel is counted iff lum > 0.0f (false for NaN, +-0 and negatives); every other pixel of the rectangle is `ignored`
+ *     bin k = min(max((int32)(bits(lum) >> 20) - 888, 0), 255): 8 bins per octave from 2^-16, from the exponent and the top three
+ *     mantissa bits -- a piecewise-linear log2 without a transcendental; +inf and everything from 1.875 * 2^15 falls in bin 255.
+ *     The counts are integers: the histogram is exact whatever the order of the atomics.
+ * Resolve, on the device:
+ *     N = sum of hist; with N == 0 the whole state record stays as it is.  Otherwise, in u64:
+ *     rlo = lowPermille*N/1000; rhi = (highPermille*N + 999)/1000
+ *     bins upward with cum: bin k gives n = |[cum, cum + hist[k]) intersected with [rlo, rhi)| to Nb += n and S += n*(2k + 1)
+ *     m = (float)S / (float)Nb                        (both conversions round to nearest even; Nb >= 1 follows from low < high)
+ *     octaves = m*0.0625f - 16.0f
+ *     i = floorf(octaves); f = octaves - i; two = the float with bits ((int32)i + 127) << 23; L = (1.0f + f) * two
+ *     target = fminf(fmaxf(key / L, minGain), maxGain)
+ *     gain = (valid && adaptRate < 1.0f) ? gain + (target - gain)*adaptRate : target;  valid = 1
+ * Transform, of every pixel of the rectangle:
+ *     g = meter ? params.gain * state.gain : params.gain      (once; with meter 1 read on the device after this call's resolve)
+ *     per channel x = g * in;  tonemap 1: x = x / (x + 1.0f);  x = fminf(fmaxf(x, 0.0f), 1.0f)
+ *         (NaN becomes 0, and +inf through the tone map -- inf / inf -- becomes 0 too: the reference's own behaviour)
+ *     transfer 0: byte = (uint8_t)(powf(x, 1/2.2f) * 255.0f)
+ *     transfer 1: s = x <= 0.0031308f ? 12.92f*x : 1.055f*powf(x, 1/2.4f) - 0.055f;  byte = (uint8_t)(s*255.0f + 0.5f)
+ *     powf is glibc's algorithm (prt_devmath.h restates it; checked against libm over every float of [2^-24, 1] for both exponents).
+ *
+ * d_rgb: a device image of the camera's size (pixel (x,y) at (x + y*width)*3 floats), NULL = the context's framebuffer (PRT_HIP_ESTATE
+ * when it holds no image of the camera's size).  d_out: a device buffer of width*height*bytesPerPixel, pixel (x,y) at
+ * (x + y*width)*bpp, NULL = a display buffer the context owns, reallocated (and zeroed) when size or format make it grow.  Only the
+ * bytes of the rectangle (inclusive) are written.  stream rules of prt_hip_accum_resolve; the call is asynchronous and never
+ * synchronises the host, with meter 1 as well: the gain goes from the resolve to the transform through device memory.  Pointers that
+ * are 16-byte aligned take the wide path (four pixels per thread); any 4-byte aligned d_rgb, and any d_out aligned to its format's
+ * 1 or 4 bytes, is accepted.
+ * Refusals: PRT_HIP_ESTATE without a camera; PRT_HIP_EINVAL with a message naming the field for every field out of range or not
+ * finite (the meter's fields are only read with meter 1).  A refused call changes nothing.
+ * The adaptation state survives prt_hip_set_camera, scene edits and uploads -- that is its purpose; only prt_hip_display_reset and
+ * prt_hip_destroy end it. ---- */
+typedef struct {
+    uint32_t tonemap;   /* 0 none, 1 c/(c+1) per channel (Image::m_tonemap, image.cpp:64) */
+    uint32_t transfer;  /* 0 the reference's: powf(c, 1/2.2f) * 255, truncated (image.cpp:65); 1 sRGB, rounded to nearest */
+    uint32_t format;    /* 0 RGB8 (3 B/pixel: the body of the PPM), 1 RGBA8 (a = 255), 2 BGRA8 (a = 255) */
+    uint32_t meter;     /* 0 manual gain only, 1 auto exposure */
+    float gain;         /* finite, >= 0: manual multiplier; 1.0f with meter 0 gives savePpm's bytes */
+    float key;          /* meter 1: finite, > 0: where the metered luminance lands (0.18) */
+    uint32_t lowPermille, highPermille; /* meter 1: band of the lit pixels that is averaged, 0 <= low < high <= 1000 (500, 950) */
+    float minGain, maxGain;             /* meter 1: finite, 0 < minGain <= maxGain */
+    float adaptRate;    /* meter 1: in (0, 1]; 1 = jump to the target */
+} prt_display_params;
+typedef struct {
+    float gain; uint32_t valid;     /* the adaptation state */
+    float octaves, target;          /* of the last metering (0 before any) */
+    uint64_t metered, ignored;      /* pixels of the last metering inside / outside the histogram */
+    uint32_t hist[256];             /* its histogram */
+} prt_display_state;
+int prt_hip_display(prt_hip_ctx* ctx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_display_params* params,
+                    const float* d_rgb, uint8_t* d_out, void* stream);
+/* Copies the rectangle (inclusive) of the context's display buffer into a host image of the camera's size in the format of the last
+ * display into that buffer.  Synchronises; like prt_hip_download it reports a sticky launch error without clearing it. */
+int prt_hip_download_display(prt_hip_ctx* ctx, uint8_t* out_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
+/* The state record as it stands once the context's stream is idle (all zero before the first display).  Synchronous. */
+int prt_hip_display_get_state(prt_hip_ctx* ctx, prt_display_state* state);
+/* valid = 0, ordered behind the displays queued so far: the next metering jumps to its target. */
+int prt_hip_display_reset(prt_hip_ctx* ctx);
+/* The mirror of prt_hip_download: the rectangle (inclusive) of a host image of the camera's size goes into the context's framebuffer
+ * (allocated and zeroed at the camera's size when there is none), behind the work queued on the context's stream.  Synchronous. */
+int prt_hip_upload(prt_hip_ctx* ctx, const float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
+
 #ifdef __cplusplus
 }
 #endif

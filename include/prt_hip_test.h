@@ -78,6 +78,15 @@ int prt_hip_test_env_tables_host(int32_t width, int32_t height, const float* rgb
  * the context's own environment map again, into scratch buffers (0 without one); ms[1] = the class kernels of the named textures, whose
  * texels are copied first (count 0: ms[1] = 0).  Ends with one real update of those textures.  Synchronous. */
 int prt_hip_test_edit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_texture_update* updates, uint32_t reps, float* ms2);
+/* The arithmetic of the display kernels (prt_display.h) on the HOST: metering over the rectangle (meter 1; *state is the adaptation
+ * state going in and coming out) and the transform of the rectangle of a width x height float RGB image into `out` (width * height *
+ * bytesPerPixel bytes; only the rectangle's are written).  Takes no context and needs no device; the refusals of the device call. */
+int prt_hip_test_display_host(uint32_t width, uint32_t height, const float* rgb, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                              const prt_display_params* params, prt_display_state* state, uint8_t* out);
+/* tools/display_bench.py: HIP-event times on the context's stream, medians of `reps` displays (after one warm-up) of the whole
+ * framebuffer into the context's display buffer: ms[0] = the histogram kernel with its memset, ms[1] = the resolve kernel (both 0 with
+ * meter 0), ms[2] = the transform kernel.  The adaptation state advances as by that many displays.  Synchronous. */
+int prt_hip_test_display_profile(prt_hip_ctx* ctx, const prt_display_params* params, uint32_t reps, float* ms3);
 
 #ifdef __cplusplus
 }

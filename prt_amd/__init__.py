@@ -128,6 +128,35 @@ class TextureUpdate(C.Structure):
                 ("texels", C.POINTER(C.c_uint8))]
 
 
+class DisplayParams(C.Structure):
+    """prt_display_params (include/prt_hip.h "display transform")."""
+    _fields_ = [("tonemap", C.c_uint32), ("transfer", C.c_uint32), ("format", C.c_uint32), ("meter", C.c_uint32), ("gain", C.c_float),
+                ("key", C.c_float), ("lowPermille", C.c_uint32), ("highPermille", C.c_uint32), ("minGain", C.c_float), ("maxGain", C.c_float),
+                ("adaptRate", C.c_float)]
+
+    RGB8, RGBA8, BGRA8 = 0, 1, 2
+    GAMMA22, SRGB = 0, 1
+
+    @classmethod
+    def make(cls, tonemap=True, transfer=0, format=0, meter=False, gain=1.0, key=0.18, low_permille=500, high_permille=950,
+             min_gain=2.0 ** -10, max_gain=2.0 ** 10, adapt_rate=1.0):
+        return cls(int(tonemap), transfer, format, int(meter), gain, key, low_permille, high_permille, min_gain, max_gain, adapt_rate)
+
+    @property
+    def bpp(self):
+        return 3 if self.format == 0 else 4
+
+
+class DisplayState(C.Structure):
+    """prt_display_state: the adaptation state and the figures of the last metering."""
+    _fields_ = [("gain", C.c_float), ("valid", C.c_uint32), ("octaves", C.c_float), ("target", C.c_float), ("metered", C.c_uint64),
+                ("ignored", C.c_uint64), ("hist", C.c_uint32 * 256)]
+
+    def as_dict(self):
+        return dict(gain=np.float32(self.gain), valid=int(self.valid), octaves=np.float32(self.octaves), target=np.float32(self.target),
+                    metered=int(self.metered), ignored=int(self.ignored), hist=np.array(self.hist[:], dtype=np.uint32))
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("i", C.c_float), ("j", C.c_float), ("k", C.c_float), ("primId", C.c_uint32),
                 ("meshId", C.c_uint32)]
@@ -150,6 +179,7 @@ EXPORTS = [
     "prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
     "prt_hip_history_export", "prt_hip_history_import", "prt_hip_update_meshes",
     "prt_hip_update_lights", "prt_hip_update_materials", "prt_hip_update_textures",
+    "prt_hip_display", "prt_hip_download_display", "prt_hip_display_get_state", "prt_hip_display_reset", "prt_hip_upload",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -162,7 +192,7 @@ EXPORTS = [
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
                 "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
-                "prt_hip_test_edit_profile"]
+                "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -254,7 +284,15 @@ def _load(path, with_test_entry_points):
     L.prt_hip_update_lights.argtypes = [vp, C.POINTER(LightUpdate), vp]
     L.prt_hip_update_materials.argtypes = [vp, C.c_uint32, C.POINTER(MaterialUpdate), vp]
     L.prt_hip_update_textures.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), vp]
+    L.prt_hip_display.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams), vp, vp, vp]
+    L.prt_hip_download_display.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.prt_hip_display_get_state.argtypes = [vp, C.POINTER(DisplayState)]
+    L.prt_hip_display_reset.argtypes = [vp]
+    L.prt_hip_upload.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
     if with_test_entry_points:
+        L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
+                                                C.POINTER(DisplayState), vp]
+        L.prt_hip_test_display_profile.argtypes = [vp, C.POINTER(DisplayParams), C.c_uint32, vp]
         L.prt_hip_test_shading_arrays.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 12
         L.prt_hip_test_env_tables_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
         L.prt_hip_test_edit_profile.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), C.c_uint32, vp]
@@ -943,6 +981,44 @@ class PathTracer:
         self._chk(self._L.prt_hip_history_import(self._ctx, C.byref(cam), *[p.ctypes.data_as(C.c_void_p) for p in planes]),
                   "prt_hip_history_import")
 
+    # ---- display transform (include/prt_hip.h "display transform"): the float image as 8-bit display pixels, under a manual gain or a
+    # metered exposure that adapts over the frames; it reads the image and changes nothing else in the context
+    def upload_image(self, rgb, x0=0, y0=0, x1=None, y1=None):
+        """prt_hip_upload: the rectangle of a host image ((H, W, 3) float32 of the camera's size) into the context's framebuffer."""
+        W, H = self._camera.width, self._camera.height
+        a = np.ascontiguousarray(rgb, dtype=np.float32)
+        if a.shape != (H, W, 3):
+            raise PrtError(f"upload_image: an image of shape {a.shape} does not match the camera's ({H}, {W}, 3)")
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        self._chk(self._L.prt_hip_upload(self._ctx, a.ctypes.data_as(C.c_void_p), x0, y0, x1, y1), "prt_hip_upload")
+
+    def display_async(self, params=None, x0=0, y0=0, x1=None, y1=None, d_rgb=None, d_out=None, stream=None):
+        """Queue prt_hip_display over the inclusive rectangle: d_rgb / d_out = device pointers (int) or None for the context's
+        framebuffer / display buffer; params = a DisplayParams (None: DisplayParams.make())."""
+        p = DisplayParams.make() if params is None else params
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        self._chk(self._L.prt_hip_display(self._ctx, x0, y0, x1, y1, C.byref(p), d_rgb, d_out, stream), "prt_hip_display")
+
+    def display(self, params=None, x0=0, y0=0, x1=None, y1=None):
+        """The rectangle of the context's framebuffer as display pixels: (h, w, bpp) uint8."""
+        p = DisplayParams.make() if params is None else params
+        x0, y0, x1, y1 = self._rect(x0, y0, x1, y1)
+        self.display_async(p, x0, y0, x1, y1)
+        W, H = self._camera.width, self._camera.height
+        out = np.zeros((H, W, p.bpp), dtype=np.uint8)
+        self._chk(self._L.prt_hip_download_display(self._ctx, out.ctypes.data_as(C.c_void_p), x0, y0, x1, y1), "prt_hip_download_display")
+        return out[y0:y1 + 1, x0:x1 + 1].copy()
+
+    def display_state(self):
+        """The adaptation state and the last metering's figures (DisplayState.as_dict)."""
+        st = DisplayState()
+        self._chk(self._L.prt_hip_display_get_state(self._ctx, C.byref(st)), "prt_hip_display_get_state")
+        return st.as_dict()
+
+    def display_reset(self):
+        """The next metered display jumps to its target."""
+        self._chk(self._L.prt_hip_display_reset(self._ctx), "prt_hip_display_reset")
+
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""
         idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
@@ -1038,6 +1114,24 @@ def env_tables_host(env):
     if rc != 0:
         raise PrtError(f"prt_hip_test_env_tables_host failed ({rc}): {test_lib().prt_hip_last_error().decode()}")
     return v, hor, fx, fy.value, flags.value
+
+
+def display_host(rgb, params=None, state=None, x0=0, y0=0, x1=None, y1=None, out=None):
+    """Test build only: prt_hip_test_display_host -- the arithmetic of the display kernels on the host, for an (h, w, 3) float image.
+    Returns (the whole (h, w, bpp) uint8 image, of which only the rectangle is written -- into `out` when given -- and the DisplayState
+    after the call); `state` (a DisplayState) is the adaptation state going in and is not modified."""
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w, _ = a.shape
+    p = DisplayParams.make() if params is None else params
+    st = DisplayState()
+    if state is not None:
+        C.memmove(C.byref(st), C.byref(state), C.sizeof(DisplayState))
+    o = np.zeros((h, w, p.bpp), dtype=np.uint8) if out is None else out
+    rc = test_lib().prt_hip_test_display_host(w, h, a.ctypes.data_as(C.c_void_p), x0, y0, w - 1 if x1 is None else x1, h - 1 if y1 is None else y1,
+                                              C.byref(p), C.byref(st), o.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PrtError(f"prt_hip_test_display_host failed ({rc}): {test_lib().prt_hip_last_error().decode()}")
+    return o, st
 
 
 def device_count():

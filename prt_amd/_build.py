@@ -20,6 +20,7 @@ SOURCES = [
     "prt_temporal.hip",
     "prt_refit.hip",
     "prt_edit.hip",
+    "prt_display.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

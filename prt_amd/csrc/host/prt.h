@@ -340,6 +340,10 @@ public:
     explicit PathTracer(const Options& o) : m_options(o) { m_stats.clear(); }
     void TraceBlock(Image& image, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const Scene& scene, const Camera& camera,
                     uint32_t samples);
+    // The image as 8-bit display pixels (C-ABI prt_hip_display, "display transform" in prt_hip.h): uploaded to the device's context,
+    // transformed there -- with params.meter under the context's adapting exposure -- and copied into `out` (width * height * 3 or 4
+    // bytes).  With meter 0, gain 1, transfer 0 and format 0 these are the bytes image.savePpm() writes.
+    void display(const Image& image, const prt_display_params& params, std::vector<uint8_t>& out);
     Stats getStats() const { return m_stats; }
     double getKernelMs() const { return m_kernelMs; }
     static void releaseDevice(); // frees the per-device context cache

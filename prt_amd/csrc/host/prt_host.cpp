@@ -1129,4 +1129,25 @@ void PathTracer::TraceBlock(Image& image, uint32_t x0, uint32_t y0, uint32_t x1,
     m_kernelMs += st.kernelMs;
 }
 
+void PathTracer::display(const Image& image, const prt_display_params& params, std::vector<uint8_t>& out)
+{
+    std::lock_guard<std::mutex> g(g_deviceMutex);
+    DeviceSlot& slot = g_devices[m_options.device];
+    if (!slot.ctx && prt_hip_create(m_options.device, &slot.ctx) != PRT_HIP_OK) die("prt_hip_create");
+    const uint32_t W = image.getWidth(), H = image.getHeigit();
+    if (!slot.haveCamera || slot.camera.width != W || slot.camera.height != H) { // the display needs the image's size and nothing else of a view
+        prt_camera_desc cd{};
+        cd.width = W;
+        cd.height = H;
+        if (prt_hip_set_camera(slot.ctx, &cd) != PRT_HIP_OK) die("prt_hip_set_camera");
+        slot.haveCamera = false; // the next TraceBlock sets its own
+    }
+    slot.frameValid = false; // the context's framebuffer no longer holds a path-traced frame
+    slot.haveFrameParams = false;
+    out.assign((size_t)W * H * (params.format == 0 ? 3 : 4), 0);
+    if (prt_hip_upload(slot.ctx, image.getPixels(), 0, 0, W - 1, H - 1) != PRT_HIP_OK) die("prt_hip_upload");
+    if (prt_hip_display(slot.ctx, 0, 0, W - 1, H - 1, &params, nullptr, nullptr, nullptr) != PRT_HIP_OK) die("prt_hip_display");
+    if (prt_hip_download_display(slot.ctx, out.data(), 0, 0, W - 1, H - 1) != PRT_HIP_OK) die("prt_hip_download_display");
+}
+
 } // namespace prt

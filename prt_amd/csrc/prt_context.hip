@@ -212,6 +212,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->adCountHost) (void)hipHostFree(c->adCountHost);
     prt_denoise_release(c);
     prt_temporal_release(c);
+    prt_display_release(c);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -263,6 +264,25 @@ int prt_hip_download(prt_hip_ctx* c, float* rgb_host, uint32_t x0, uint32_t y0, 
     HIP_TRY(hipMemcpy2D(rgb_host + off, (size_t)W * 3 * sizeof(float), c->fb + off, (size_t)W * 3 * sizeof(float), rowBytes,
                         y1 - y0 + 1, hipMemcpyDeviceToHost));
     return prt_sticky_error(c, false); // the pixels are delivered, but a caller must learn that a launch behind them was cut short
+}
+
+// The mirror of prt_hip_download; ordered on the context's stream behind the work queued there.
+int prt_hip_upload(prt_hip_ctx* c, const float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
+{
+    if (!c || !rgb_host) return fail(PRT_HIP_EINVAL, "NULL argument");
+    if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
+    const uint32_t W = c->cam.width;
+    int rc = prt_check_rect(c, x0, y0, x1, y1);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    float* fb = nullptr;
+    if ((rc = prt_own_framebuffer(c, &fb))) return rc;
+    size_t rowBytes = (size_t)(x1 - x0 + 1) * 3 * sizeof(float);
+    size_t off = ((size_t)y0 * W + x0) * 3;
+    HIP_TRY(hipMemcpy2DAsync(fb + off, (size_t)W * 3 * sizeof(float), rgb_host + off, (size_t)W * 3 * sizeof(float), rowBytes, y1 - y0 + 1,
+                             hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream)); // the caller's array is free again on return
+    return PRT_HIP_OK;
 }
 
 int prt_hip_get_stats(prt_hip_ctx* c, prt_hip_stats* st)

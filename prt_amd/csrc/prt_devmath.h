@@ -191,13 +191,14 @@ PRT_HD void prt_powf_log2_tab(int i, double* invc, double* logc)
     }
 }
 
-PRT_HD float prt_powf_2p2(float x)
+// powf(x, e) for x >= 0 and a finite e > 0 that is no integer: the exponent only enters where glibc multiplies it into log2(x).
+PRT_HD float prt_powf_pos(float x, float e)
 {
     uint32_t ix = prt_f2u(x);
     if (ix == 0x3f800000u) return 1.0f; // x == 1
     if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {
         // zero, subnormal, negative, inf or nan
-        if ((ix << 1) == 0) return 0.0f;                 // pow(+-0, 2.2) = +0
+        if ((ix << 1) == 0) return 0.0f;                 // pow(+-0, e) = +0
         if (ix == 0x7f800000u) return x;                 // +inf
         if (ix > 0x7f800000u) return prt_u2f(0x7fc00000u); // negative or nan -> nan (never on the path)
         // subnormal: normalise as glibc does (x * 2^23, exponent - 23)
@@ -226,9 +227,9 @@ PRT_HD float prt_powf_2p2(float x)
     double q = prt_mad(A4, r, y0);
     q = prt_mad(p, r2, q);
     y = prt_mad(y, r4, q);
-    double ylogx = (double)2.2f * y;
-    // (overflow/underflow of the result cannot happen for x in [0,1], y = 2.2: 2.2*log2(x) > -330 only matters
-    //  below 2^-57; such inputs underflow to the correctly signed 0/denormal through the scaling below)
+    double ylogx = (double)e * y;
+    // (overflow of the result cannot happen for x in [0,1]: e*log2(x) <= 0; underflow as glibc answers it: e = 2.2 reaches
+    //  -150 only below 2^-68, the display exponents 1/2.2 and 1/2.4 never do)
     if (ylogx <= -150.0) return 0.0f;
     // exp2_inline, N = 32, no sign bias
     const double SHIFT = 0x1.8p+52 / 32.0;
@@ -258,3 +259,5 @@ PRT_HD float prt_powf_2p2(float x)
     yy = yy * s;
     return (float)yy;
 }
+
+PRT_HD float prt_powf_2p2(float x) { return prt_powf_pos(x, 2.2f); }

@@ -157,6 +157,12 @@ struct prt_hip_ctx {
     size_t tpPixels = 0;         // pixels each of the six planes holds
     bool tpHaveHist = false, tpHavePend = false;
     prt_camera_desc tpHistCam{}, tpPendCam{};
+    // display transform (prt_display.hip): allocated on first use; neither the camera nor the scene touches any of it
+    prt_display_state* dpState = nullptr; // device: the adaptation state and the figures of the last metering
+    uint32_t* dpHist = nullptr;           // device: the histogram of the metering under way, then the ignored count (64 bits)
+    uint8_t* dpOut = nullptr;             // the context's display buffer
+    size_t dpOutBytes = 0;                // bytes allocated
+    uint32_t dpOutW = 0, dpOutH = 0, dpOutFormat = 0; // image it last held (prt_hip_download_display)
 };
 
 
@@ -230,6 +236,8 @@ int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float ex
 void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next);
 void prt_temporal_forget(prt_hip_ctx* c);
 void prt_temporal_release(prt_hip_ctx* c);
+// prt_display.hip: frees the state, the histogram and the display buffer
+void prt_display_release(prt_hip_ctx* c);
 // prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
 // temp == nullptr it only sets tempBytes
 hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,
