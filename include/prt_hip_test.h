@@ -87,6 +87,20 @@ int prt_hip_test_display_host(uint32_t width, uint32_t height, const float* rgb,
  * framebuffer into the context's display buffer: ms[0] = the histogram kernel with its memset, ms[1] = the resolve kernel (both 0 with
  * meter 0), ms[2] = the transform kernel.  The adaptation state advances as by that many displays.  Synchronous. */
 int prt_hip_test_display_profile(prt_hip_ctx* ctx, const prt_display_params* params, uint32_t reps, float* ms3);
+/* Texture taps on the uploaded scene's own arrays (texture.cpp:31-183, material.cpp:87-96).  records: n x 4 words {material (global
+ * index: the scene's materials in mesh order), f32 u, f32 v, flags}; flags 1: the single-ray flavours (uv must be finite; the material
+ * needs both maps), 2: the alpha tests (the material is alpha-tested, its diffuse map has 4 components).  out: n x 12 words:
+ * [0..2] tex_sample3 of the diffuse map, [3] tex_sample1 of the bump map, [4] the alpha decision of a leaf round for a single ray
+ * (class word, then the blend -- alpha_decide, prt_device.h), [5] the same for a packet, [6..8] sample_diffuse, [9] taps counted
+ * (counting form), [10..11] 0.  counting != 0 runs the kernels' counting form (prt_render_params.countTraffic).  blocks = workgroups of
+ * 256 threads to launch (the kernel strides over the records), 0 = one thread per record.  Refuses what would read outside the scene's
+ * arrays.  Synchronous. */
+int prt_hip_test_taps(prt_hip_ctx* ctx, uint32_t n, const uint32_t* records, int counting, uint32_t blocks, uint32_t* out);
+/* Mesh::getSurfaceProperties and Material::sampleBump (mesh.cpp:311-364, material.cpp:98-114) on the uploaded scene's own records.
+ * records: n x 5 words {mesh, primId in mesh order, f32 i, j, k}; out: n x 20 words: [0..2] normal, [3..4] uv, [5] material (index within
+ * the mesh), [6..9] duv01, duv02 and [10..15] dp01, dp02 as the bump record of the triangle holds them (0 in a scene without a bump
+ * map), [16..18] sample_bump's normal, [19] taps counted (counting form).  counting, blocks: as above.  Synchronous. */
+int prt_hip_test_surface(prt_hip_ctx* ctx, uint32_t n, const uint32_t* records, int counting, uint32_t blocks, uint32_t* out);
 
 #ifdef __cplusplus
 }

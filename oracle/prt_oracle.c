@@ -858,6 +858,19 @@ int orc_x_tex_test_alpha(int32_t w, int32_t h, int32_t comp, const uint8_t* texe
     return tex_test_alpha(&t, V2(u, v), soa, NULL);
 }
 
+/* Texture::sample<Vector3f> / sample<float> on an 8-bit map (texture.cpp:106-139); `texels` needs 2 readable bytes past a 1-component map */
+void orc_x_tex_sample3(int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u, float v, float out[3])
+{
+    texture_t t = {w, h, comp, (uint8_t*)texels};
+    st3(out, tex_sample3(&t, V2(u, v), NULL));
+}
+
+float orc_x_tex_sample1(int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u, float v)
+{
+    texture_t t = {w, h, comp, (uint8_t*)texels};
+    return tex_sample1(&t, V2(u, v), NULL);
+}
+
 void orc_x_sample_diffuse(const float diffuse[3], int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u,
                           float v, float out[3])
 {

@@ -163,6 +163,8 @@ void orc_set_rr_depth(uint32_t rrDepth); /* default 4 = the reference (path_trac
 void orc_x_get_surface(const orc_mesh* m, uint32_t primId, float i, float j, float k, float normal[3], uint32_t* matIndex,
                        float uv[2], float duv01[2], float duv02[2], float dp01[3], float dp02[3]);
 int orc_x_tex_test_alpha(int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u, float v, int soa);
+void orc_x_tex_sample3(int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u, float v, float out[3]);
+float orc_x_tex_sample1(int32_t w, int32_t h, int32_t comp, const uint8_t* texels, float u, float v);
 void orc_x_sample_diffuse(const float diffuse[3], int32_t w, int32_t h, int32_t comp, const uint8_t* texels /*nullable*/,
                           float u, float v, float out[3]);
 void orc_x_sample_bump(const float normal[3], int32_t w, int32_t h, int32_t comp, const uint8_t* texels /*nullable*/,

@@ -1,14 +1,13 @@
-// ref_glue.cpp -- lets the compiled reference's path_tracer.cpp / scene.cpp / bvh.cpp run end to
-// end although four of its translation units cannot be built in this image.
+// ref_glue.cpp -- lets the compiled reference's path_tracer.cpp / scene.cpp / bvh.cpp run end to end WITHOUT its texture.cpp,
+// material.cpp, mesh.cpp and image.cpp (ref_path, ref_path_stats), and hands scenes and images over in both builds.
 //
-// TEST INFRASTRUCTURE ONLY.  mesh.cpp, material.cpp, texture.cpp and image.cpp include the
-// un-vendored tinyobjloader / stb / tinyexr headers (empty submodules), so the reference objects
-// that DO build (oracle/Makefile) reference a handful of member functions nobody defines.  This
-// file defines exactly those members, with the reference's declarations, by forwarding to the
-// ORACLE's restatement (prt_oracle.c) -- it contains no reference code.  Consequence, stated in
-// a `ref_path render` result pins the oracle's bounce loop, traversal, camera and RNG
-// against the reference's compiled code, but the surface fetch and material/texture sampling in
-// that run are the oracle's own (rows a12/a14 stay "restatement only").
+// TEST INFRASTRUCTURE ONLY.  The members below "forwarding members" have the reference's declarations and forward to the ORACLE's
+// restatement (prt_oracle.c) -- this file contains no reference code.  A `ref_path render` therefore pins the oracle's bounce loop,
+// traversal, camera and RNG against the reference's compiled code while surface fetch and material / texture sampling in that run are
+// the oracle's own.  With -DREF_REAL_TUS (ref_path_real, oracle/Makefile) those members are compiled out and the reference's own four
+// objects -- built against the stand-in declarations of oracle/shim/ext/ -- serve the render: rows a12 / a14 are then the reference's
+// too, and tests/test_hostile_taps_cpu.py checks that the committed fixtures come out the same.  The bookkeeping above the switch
+// (the hand-made Image, the mesh registry the forwarding getSurfaceProperties looks its oracle mesh up in) stays in both.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -63,6 +62,7 @@ prt::Image* refGlueMakeImage(uint32_t width, uint32_t height, float exposure)
 
 const float* refGlueImagePixels(const prt::Image* image) { return image->m_pixels; }
 
+#ifndef REF_REAL_TUS // ---- the forwarding members; compiled out where the reference's own four TUs are linked (ref_path_real)
 namespace prt {
 
 // image.cpp:44-50
@@ -204,3 +204,4 @@ void Mesh::calculateBounds()
 }
 
 } // namespace prt
+#endif // REF_REAL_TUS

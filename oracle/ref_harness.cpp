@@ -15,6 +15,9 @@
 //   ref_path  -- additionally links path_tracer.o, sample_models.o and oracle/ref_glue.cpp, which
 //                supplies the missing leaf functions by forwarding to the oracle's restatement.
 //                Commands: + render, cornell.  (-DREF_WITH_GLUE)
+//   ref_path_real -- ref_path with those forwarding members compiled out (-DREF_REAL_TUS) and the reference's own texture.o,
+//                material.o, mesh.o, image.o (built against oracle/shim/ext/) in their place.
+//   (ref_shade.cpp includes this file for the scene reader and fillMesh, with REF_HARNESS_NO_MAIN.)
 //
 // Scene file format ("PRTS", little endian) -- written by tests/prt_testlib.py:
 //   char magic[4]="PRTS"; u32 version=1; u32 meshCount;
@@ -44,6 +47,7 @@
 #include <chrono>
 #include <type_traits>
 #include <immintrin.h>
+#include <new>
 
 #define private public
 #define protected public
@@ -159,7 +163,9 @@ static void fillMesh(Mesh* m, const FMesh& fm, const FScene& fs)
     memcpy(m->m_primMaterial, fm.primMaterial.data(), (size_t)fm.primCount * 4);
     m->m_materials = (Material*)calloc(fm.materialCount, sizeof(Material));
     for (uint32_t i = 0; i < fm.materialCount; i++) {
-        Material& d = m->m_materials[i];
+        // Texture's threshold and alpha offset are per-object constants with initialisers (texture.h:44-45): the reference's own
+        // testAlpha (ref_path_real, ref_shade) reads them, so the objects are constructed, not just zeroed
+        Material& d = *new (&m->m_materials[i]) Material();
         const orc_material& sm = fm.materials[i];
         d.diffuse = Vector3f(sm.diffuse[0], sm.diffuse[1], sm.diffuse[2]);
         d.emissive = Vector3f(sm.emissive[0], sm.emissive[1], sm.emissive[2]);
@@ -602,6 +608,7 @@ static int cmdCornell(const char* out)
 }
 #endif
 
+#ifndef REF_HARNESS_NO_MAIN // (ref_shade.cpp includes this file for the scene reader and brings its own main)
 int main(int argc, char** argv)
 {
     if (argc >= 4 && !strcmp(argv[1], "leaf")) return cmdLeaf(argv[2], argv[3]);
@@ -627,3 +634,4 @@ int main(int argc, char** argv)
             "\n", argv[0]);
     return 1;
 }
+#endif

@@ -192,7 +192,8 @@ EXPORTS = [
 TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos", "prt_hip_test_powf", "prt_hip_test_camera",
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
                 "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
-                "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile"]
+                "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile", "prt_hip_test_taps",
+                "prt_hip_test_surface"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -307,6 +308,8 @@ def _load(path, with_test_entry_points):
         L.prt_hip_test_copy_yardstick.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.prt_hip_test_temporal_profile.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_float, vp]
         L.prt_hip_test_occlusion_skipped.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.prt_hip_test_taps.argtypes = [vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp]
+        L.prt_hip_test_surface.argtypes = [vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp]
     for n in ("prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
               "prt_host_mesh_atrium", "prt_host_scene_create"):
         getattr(L, n).restype = vp
@@ -1094,6 +1097,24 @@ class PathTracer:
         y = np.zeros_like(x)
         self._chk(self._L.prt_hip_test_powf(self._ctx, len(x), x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p)), "prt_hip_test_powf")
         return y
+
+    def test_taps(self, records, counting=False, blocks=0):
+        """prt_hip_test_taps: (n, 4) uint32 records {material, u bits, v bits, flags} -> (n, 12) uint32 words."""
+        self._need_row_level()
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 4)
+        out = np.zeros((len(rec), 12), dtype=np.uint32)
+        self._chk(self._L.prt_hip_test_taps(self._ctx, len(rec), rec.ctypes.data_as(C.c_void_p), int(counting), blocks,
+                                            out.ctypes.data_as(C.c_void_p)), "prt_hip_test_taps")
+        return out
+
+    def test_surface(self, records, counting=False, blocks=0):
+        """prt_hip_test_surface: (n, 5) uint32 records {mesh, primId, i bits, j bits, k bits} -> (n, 20) uint32 words."""
+        self._need_row_level()
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 5)
+        out = np.zeros((len(rec), 20), dtype=np.uint32)
+        self._chk(self._L.prt_hip_test_surface(self._ctx, len(rec), rec.ctypes.data_as(C.c_void_p), int(counting), blocks,
+                                               out.ctypes.data_as(C.c_void_p)), "prt_hip_test_surface")
+        return out
 
     def test_camera(self, x, y, state):
         self._need_row_level()

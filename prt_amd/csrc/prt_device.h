@@ -411,6 +411,27 @@ __device__ __forceinline__ bool tex_test_alpha(const DevScene& sc, uint4 d, Vec2
     return alpha > 127.0f;
 }
 
+// The alpha test of a leaf candidate at uv (bvh.cpp:336-338, 407-409) as the leaf round decides it: the class of the tap's cell -- one
+// word of a map that stays in the L2, built at upload (prt_upload.hip classWord) -- answers for a cell whose four bytes lie on one side
+// of the threshold; a cell with bytes on both sides (or a byte of 127), or a non-finite uv, takes the blend.  d = the texture's
+// descriptor, classBits = the first class word of that texture as the alpha record holds it (an index in a float's bits).  The test
+// build's taps kernel calls this too.
+template <bool SOA>
+__device__ __forceinline__ bool alpha_decide(const DevScene& sc, const uint4& d, const float& classBits, const Vec2& uv, Traffic& tr)
+{
+    int32_t x0, y0;
+    float xt, yt;
+    uint32_t cls = 0u;
+    if (bilinear_cell(uv, (int32_t)d.y, (int32_t)d.z, SOA, x0, y0, xt, yt)) {
+        const uint32_t cell = (uint32_t)x0 + (uint32_t)y0 * d.y;
+        cls = (gld(sc.alphaClass + asu(classBits) + (cell >> 4)) >> ((cell & 15u) * 2u)) & 3u;
+    }
+    bool pass;
+    if (cls == 0u) pass = tex_test_alpha<false>(sc, d, uv, SOA, tr); // a cell with texels on both sides of the threshold, or a non-finite uv
+    else pass = cls == 1u;
+    return pass;
+}
+
 template <bool COUNT>
 __device__ __forceinline__ Vec3 tex_sample3(const DevScene& sc, uint4 d, Vec2 uv, Traffic& tr)
 {
@@ -993,15 +1014,7 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
             const float4 u0 = gld4(ap), u1 = gld4(ap + 1), u2 = gld4(ap + 2);
             const Vec2 uv = Vec2{bi * u0.x + bj * u0.z + bk * u1.x, bi * u0.y + bj * u0.w + bk * u1.y}; // bvh.cpp:336, 407
             const uint4 d = make_uint4(asu(u2.x), asu(u2.y), asu(u2.z), asu(u2.w));
-            int32_t x0, y0;
-            float xt, yt;
-            uint32_t cls = 0u;
-            if (bilinear_cell(uv, (int32_t)d.y, (int32_t)d.z, PACKET, x0, y0, xt, yt)) {
-                const uint32_t cell = (uint32_t)x0 + (uint32_t)y0 * d.y;
-                cls = (gld(sc.alphaClass + asu(u1.w) + (cell >> 4)) >> ((cell & 15u) * 2u)) & 3u;
-            }
-            if (cls == 0u) cand = tex_test_alpha<false>(sc, d, uv, PACKET, tr); // a cell with texels on both sides of the threshold, or a non-finite uv
-            else cand = cls == 1u;
+            cand = alpha_decide<PACKET>(sc, d, u1.w, uv, tr);
         }
 #ifdef PRT_PROFILE
         if (__ballot(cand && (flags & 4u)) != 0ull) { // (ballot of the lanes inside `if (pair)`: some candidate lies in a leaf with alpha-tested triangles)

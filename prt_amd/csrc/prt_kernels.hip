@@ -223,6 +223,69 @@ __global__ void camera_kernel(DevCamera cam, uint32_t x, uint32_t y, uint32_t st
     }
 }
 
+// Texture taps on the uploaded scene's own arrays (texture.cpp:31-183, material.cpp:87-96).  rec: {material (global), u, v, flags};
+// out: 12 words per record (include/prt_hip_test.h).  classOf = per texture its first alpha class word (PrtEdit::classWordOf); the
+// host has checked every record's material, maps and class words.  A grid-stride loop: any grid covers any n.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void taps_kernel(DevScene sc, const uint32_t* classOf, uint32_t n, const uint32_t* rec, uint32_t* out)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+        const uint32_t* p = rec + 4 * (size_t)r;
+        uint32_t* q = out + 12 * (size_t)r;
+        const uint32_t mat = p[0], flags = p[3];
+        const Vec2 uv = Vec2{asf(p[1]), asf(p[2])};
+        Traffic tr{};
+        const float4* mp = sc.mats + PRT_MAT_STRIDE * (size_t)mat;
+        const float4 m2 = gld4(mp + 2), m3 = gld4(mp + 3), m4 = gld4(mp + 4);
+        const uint4 dd = make_uint4(asu(m3.x), asu(m3.y), asu(m3.z), asu(m3.w)), bd = make_uint4(asu(m4.x), asu(m4.y), asu(m4.z), asu(m4.w));
+        for (int k = 0; k < 12; k++) q[k] = 0u;
+        if (flags & 1u) {
+            const Vec3 c = tex_sample3<COUNT>(sc, dd, uv, tr);
+            q[0] = asu(c.x); q[1] = asu(c.y); q[2] = asu(c.z);
+            q[3] = asu(tex_sample1<COUNT>(sc, bd, uv, tr));
+            const Vec3 s = sample_diffuse<COUNT>(sc, mat, uv, tr);
+            q[6] = asu(s.x); q[7] = asu(s.y); q[8] = asu(s.z);
+        }
+        if (flags & 2u) {
+            const float base = asf(classOf[asu(m2.x)]);
+            if (flags & 1u) q[4] = alpha_decide<false>(sc, dd, base, uv, tr) ? 1u : 0u;
+            q[5] = alpha_decide<true>(sc, dd, base, uv, tr) ? 1u : 0u;
+        }
+        q[9] = COUNT ? tr.nTap : 0u;
+    }
+}
+
+// Mesh::getSurfaceProperties + Material::sampleBump (mesh.cpp:311-364, material.cpp:98-114) on the uploaded scene's own records.
+// rec: {mesh, triangle slot, i, j, k} (the host has turned the mesh-order primId into the slot and checked both); out: 20 words.
+template <bool COUNT>
+__global__ __launch_bounds__(256) void surface_kernel(DevScene sc, uint32_t anyBump, uint32_t n, const uint32_t* rec, uint32_t* out)
+{
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
+        const uint32_t* p = rec + 5 * (size_t)r;
+        uint32_t* q = out + 20 * (size_t)r;
+        Traffic tr{};
+        DevHit h;
+        h.t = 1.0f; h.i = asf(p[2]); h.j = asf(p[3]); h.k = asf(p[4]);
+        h.primId = p[1]; h.meshId = p[0];
+        Surface s;
+        get_surface<COUNT>(sc, h, s, tr);
+        for (int k = 0; k < 20; k++) q[k] = 0u;
+        q[0] = asu(s.normal.x); q[1] = asu(s.normal.y); q[2] = asu(s.normal.z);
+        q[3] = asu(s.uv.x); q[4] = asu(s.uv.y);
+        q[5] = s.mat;
+        if (anyBump) { // the bump record of the slot: dp01.xyz duv01.x | dp02.xyz duv01.y | duv02.xy (prt_upload.hip)
+            const float4* bp = sc.bump + 3 * (size_t)s.prim;
+            const float4 b0 = gld4(bp), b1 = gld4(bp + 1), b2 = gld4(bp + 2);
+            q[6] = asu(b0.w); q[7] = asu(b1.w); q[8] = asu(b2.x); q[9] = asu(b2.y);
+            q[10] = asu(b0.x); q[11] = asu(b0.y); q[12] = asu(b0.z);
+            q[13] = asu(b1.x); q[14] = asu(b1.y); q[15] = asu(b1.z);
+        }
+        const Vec3 bn = sample_bump<COUNT>(sc, s.mat, s, tr);
+        q[16] = asu(bn.x); q[17] = asu(bn.y); q[18] = asu(bn.z);
+        q[19] = COUNT ? tr.nTap : 0u;
+    }
+}
+
 #endif // PRT_TEST_ENTRY_POINTS
 
 // ============================================================================ host side of the C-ABI
@@ -889,6 +952,95 @@ int prt_hip_test_camera(prt_hip_ctx* c, uint32_t x, uint32_t y, uint32_t state, 
     hipLaunchKernelGGL(camera_kernel, dim3(1), dim3(64), 0, c->stream, c->cam, x, y, state, d.as<float>());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out92, d.p, 92 * 4, hipMemcpyDeviceToHost));
+    return PRT_HIP_OK;
+}
+
+// blocks of a row-level launch: the caller's, or one thread per record; at most 65535
+static uint32_t row_blocks(uint32_t n, uint32_t blocks)
+{
+    if (blocks == 0) blocks = (n + 255u) / 256u;
+    return std::min<uint32_t>(blocks, 65535u);
+}
+
+int prt_hip_test_taps(prt_hip_ctx* c, uint32_t n, const uint32_t* records, int counting, uint32_t blocks, uint32_t* out)
+{
+    if (!c || !records || !out || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
+    if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
+    // every address the kernel forms is checked here: the material exists, the flavours asked for have their maps and class words
+    std::vector<const prt_material*> matOf(c->ed.matRecords, nullptr);
+    for (const PrtEditMesh& m : c->ed.meshes)
+        for (size_t k = 0; k < m.materials.size(); k++)
+            if (m.matBase + k < matOf.size()) matOf[m.matBase + k] = &m.materials[k];
+    for (uint32_t r = 0; r < n; r++) {
+        const uint32_t mat = records[4 * (size_t)r], flags = records[4 * (size_t)r + 3];
+        if (mat >= matOf.size() || !matOf[mat] || (flags & ~3u)) return fail(PRT_HIP_EINVAL, "taps: bad material index or flags");
+        const prt_material& mt = *matOf[mat];
+        if ((flags & 1u) && (mt.diffuseMap < 0 || mt.bumpMap < 0)) return fail(PRT_HIP_EINVAL, "taps: the material lacks a diffuse or a bump map");
+        if (flags & 2u) {
+            if (mt.diffuseMap < 0 || (size_t)mt.diffuseMap >= c->ed.classWordOf.size() || c->ed.classWordOf[mt.diffuseMap] == 0xffffffffu ||
+                c->ed.texDesc[mt.diffuseMap].w != 4u)
+                return fail(PRT_HIP_EINVAL, "taps: alpha test asked of a material without a 4-component map whose cell classes were built");
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf din, dout, dcls;
+    HIP_TRY(din.alloc((size_t)n * 16));
+    HIP_TRY(dout.alloc((size_t)n * 48));
+    HIP_TRY(dcls.alloc(c->ed.classWordOf.size() * 4));
+    HIP_TRY(hipMemcpy(din.p, records, (size_t)n * 16, hipMemcpyHostToDevice));
+    if (!c->ed.classWordOf.empty()) HIP_TRY(hipMemcpy(dcls.p, c->ed.classWordOf.data(), c->ed.classWordOf.size() * 4, hipMemcpyHostToDevice));
+    blocks = row_blocks(n, blocks);
+    if (counting) hipLaunchKernelGGL(taps_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls.as<uint32_t>(), n, din.as<uint32_t>(), dout.as<uint32_t>());
+    else hipLaunchKernelGGL(taps_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls.as<uint32_t>(), n, din.as<uint32_t>(), dout.as<uint32_t>());
+    int rc = prt_launched("taps_kernel");
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    return PRT_HIP_OK;
+}
+
+int prt_hip_test_surface(prt_hip_ctx* c, uint32_t n, const uint32_t* records, int counting, uint32_t blocks, uint32_t* out)
+{
+    if (!c || !records || !out || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
+    if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // mesh-order primId -> triangle slot, from the arrays the upload left on the device (a pad slot names no vertices)
+    const size_t slots = (size_t)c->rf.slots;
+    std::vector<uint32_t> triPrim(slots), slotVtx(3 * slots);
+    if (slots) {
+        HIP_TRY(hipMemcpy(triPrim.data(), c->sc.triPrim, slots * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(slotVtx.data(), c->rf.slotVtx, slots * 12, hipMemcpyDeviceToHost));
+    }
+    std::vector<std::vector<uint32_t>> slotOf(c->rf.meshes.size());
+    for (size_t m = 0; m < c->rf.meshes.size(); m++) {
+        const PrtRefitMesh& rm = c->rf.meshes[m];
+        if ((size_t)rm.slotBase + rm.slotCount > slots) return fail(PRT_HIP_ESTATE, "surface: slot range outside the scene");
+        slotOf[m].assign(rm.slotCount, 0xffffffffu); // (primCount <= slotCount)
+        for (uint32_t s = rm.slotBase; s < rm.slotBase + rm.slotCount; s++)
+            if (slotVtx[3 * (size_t)s] != 0xffffffffu && triPrim[s] < rm.slotCount) slotOf[m][triPrim[s]] = s;
+    }
+    std::vector<uint32_t> rec(records, records + 5 * (size_t)n);
+    for (uint32_t r = 0; r < n; r++) {
+        const uint32_t mesh = rec[5 * (size_t)r], prim = rec[5 * (size_t)r + 1];
+        if (mesh >= slotOf.size() || mesh >= c->sc.bvhCount || prim >= slotOf[mesh].size() || slotOf[mesh][prim] == 0xffffffffu)
+            return fail(PRT_HIP_EINVAL, "surface: bad mesh or primitive index");
+        rec[5 * (size_t)r + 1] = slotOf[mesh][prim];
+    }
+    DevBuf din, dout;
+    HIP_TRY(din.alloc((size_t)n * 20));
+    HIP_TRY(dout.alloc((size_t)n * 80));
+    HIP_TRY(hipMemcpy(din.p, rec.data(), (size_t)n * 20, hipMemcpyHostToDevice));
+    blocks = row_blocks(n, blocks);
+    const uint32_t anyBump = c->ed.anyBump ? 1u : 0u;
+    if (counting) hipLaunchKernelGGL(surface_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din.as<uint32_t>(), dout.as<uint32_t>());
+    else hipLaunchKernelGGL(surface_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din.as<uint32_t>(), dout.as<uint32_t>());
+    int rc = prt_launched("surface_kernel");
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 80, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < n; r++) // the material as the reference names it: its index within the mesh
+        out[20 * (size_t)r + 5] -= c->ed.meshes[records[5 * (size_t)r]].matBase;
     return PRT_HIP_OK;
 }
 #endif // PRT_TEST_ENTRY_POINTS

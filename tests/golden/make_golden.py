@@ -19,6 +19,11 @@ Outputs (all small, data only -- no reference source text):
                        see oracle/ref_glue.cpp for which leaf functions are the oracle's)
   hostile_rays.npz     the grid / twins / flat scenes of tests/prt_hostile.py for seeds 0-3: vertices, 1024 hostile rays each and the
                        reference's Scene::intersect / Scene::occluded answers, single and packet
+  hostile_taps.npz     the maps, meshes and records of tests/prt_hostile_taps.py and the answers of the reference's own texture.cpp /
+                       material.cpp / mesh.cpp to them (oracle/_ref/ref_shade)
+
+radiance_c1_crop, gbuffer and scene_digests were rendered through ref_path (surface fetch and texture taps forwarded to the oracle);
+tests/test_hostile_taps_cpu.py renders them again through ref_path_real (the reference's own) and requires the committed bytes.
 """
 import os
 import struct
@@ -306,6 +311,21 @@ def dump_hostile():
     assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "c5_tile_rows.npz")), os.path.getsize(path)
 
 
+def dump_hostile_taps():
+    # tests/prt_hostile_taps.py: hostile uv on small maps, direct bump records and surface fetches, answered by the reference's OWN
+    # texture.cpp / material.cpp / mesh.cpp (oracle/_ref/ref_shade: no member is forwarded to the oracle).  Inputs are stored as generated.
+    import prt_hostile_taps as H
+    z = H.generate()
+    desc = H.scene_desc(H.maps())
+    taps = H.ref_shade(desc, "taps", z["taps"], 12)
+    f, a = H.pack_taps(taps)
+    z.update(ref_taps_f=f, ref_taps_a=a, ref_bump=H.ref_shade(desc, "bump", z["bump"], 3), ref_surface=H.ref_shade(desc, "surface", z["surface"], 20))
+    path = os.path.join(HERE, "hostile_taps.npz")
+    np.savez_compressed(path, **z)
+    print("hostile taps:", len(z["taps"]), "taps,", len(z["bump"]), "bump,", len(z["surface"]), "surface records;", os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "hostile_rays.npz")), os.path.getsize(path)
+
+
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", T.ORACLE_DIR])
     dump_cornell()
@@ -318,3 +338,4 @@ if __name__ == "__main__":
     dump_c1_checksums()
     dump_scene_digests()
     dump_hostile()
+    dump_hostile_taps()

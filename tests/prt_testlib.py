@@ -430,13 +430,14 @@ def ref_bvh(desc, threaded=False):
     return out, sbox, radius
 
 
-def ref_gbuffer(desc, kind, rect, seed=12345):
-    """GbufferVisualizer::TraceBlock of the compiled reference (kind 0 diffuse, 1 mesh normal, 2 normal), per-pixel states."""
+def ref_gbuffer(desc, kind, rect, seed=12345, binary="ref_path"):
+    """GbufferVisualizer::TraceBlock of the compiled reference (kind 0 diffuse, 1 mesh normal, 2 normal), per-pixel states.
+    binary="ref_path_real": the reference's own surface fetch and texture taps instead of the oracle's (oracle/Makefile)."""
     x0, y0, x1, y1 = rect
     with tempfile.TemporaryDirectory() as td:
         sp, op = os.path.join(td, "s.prts"), os.path.join(td, "out.bin")
         desc.write_prts(sp)
-        run_ref("ref_path", "gbuffer", sp, kind, x0, y0, x1, y1, seed, op)
+        run_ref(binary, "gbuffer", sp, kind, x0, y0, x1, y1, seed, op)
         return np.fromfile(op, dtype="<f4").reshape(y1 - y0 + 1, x1 - x0 + 1, 3).copy()
 
 
@@ -456,7 +457,9 @@ def ref_envlight(desc, u):
     return vp, hp, rec[:, :3].copy(), rec[:, 3:].copy()
 
 
-def ref_render(desc, spp, rect, seed=12345, threads=0, stats=True):
+def ref_render(desc, spp, rect, seed=12345, threads=0, stats=True, binary=None):
+    """binary: None = ref_path_stats / ref_path; "ref_path_real" = the build whose surface fetch and texture taps are the reference's own
+    (no ray counts)."""
     x0, y0, x1, y1 = rect
     with tempfile.TemporaryDirectory() as td:
         sp, op = os.path.join(td, "s.prts"), os.path.join(td, "out.bin")
@@ -466,7 +469,7 @@ def ref_render(desc, spp, rect, seed=12345, threads=0, stats=True):
             ep = os.path.join(td, "e.prte")
             desc.write_env(ep)
             extra = [ep]
-        run_ref("ref_path_stats" if stats else "ref_path", "render", sp, spp, x0, y0, x1, y1, seed, threads, op, *extra)
+        run_ref(binary or ("ref_path_stats" if stats else "ref_path"), "render", sp, spp, x0, y0, x1, y1, seed, threads, op, *extra)
         raw = open(op, "rb").read()
     n = (x1 - x0 + 1) * (y1 - y0 + 1) * 3
     rgb = np.frombuffer(raw, dtype="<f4", count=n).reshape(y1 - y0 + 1, x1 - x0 + 1, 3).copy()
