@@ -639,6 +639,60 @@ int prt_hip_display_reset(prt_hip_ctx* ctx);
  * (allocated and zeroed at the camera's size when there is none), behind the work queued on the context's stream.  Synchronous. */
 int prt_hip_upload(prt_hip_ctx* ctx, const float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 
+/* ---- ray queries: nearest hit, any hit and surface records for batches of the caller's own rays.  Everything above answers "what
+ * colour is this pixel"; these answer what else a ray tracer is asked: which mesh, triangle and material lies under the cursor, whether
+ * two points see each other, what a probe or a lightmap texel sees, what a collision ray meets among the meshes prt_hip_update_meshes
+ * moves.  The traversals are the frame kernel's own (prt_device.h trace_loop) behind a ray source that reads the caller's array; a
+ * query reads the scene and changes nothing else: the accumulator, the moments, the guides, the history and the display state are
+ * untouched.  It needs a scene and no camera (PRT_HIP_ESTATE without a scene).
+ *
+ * A ray is {org, tMax, dir}: 32 bytes, read as two 16-byte loads.  dir need not be normalised; t is in units of dir.  There is no
+ * tMin: as in the reference, offsetting the origin is the caller's business.  pad is ignored.
+ *
+ * nearest: Scene::intersect<SingleRayHitPacket, SingleRayPacket> (scene.cpp:47-64) per ray with the ray's own tMax: the single-ray
+ * nearest traversal of the G-buffer kernel, alpha tests included.  hits[r] is the reference's RayHitT: t, the barycentrics i, j, k,
+ * primId = the triangle's index in its mesh, meshId = the mesh's index in the scene; a miss is {-1, 0, 0, 0, 0, 0}.
+ * any: Scene::occluded<bool, SingleRayPacket> (scene.cpp:66-84): occluded[r] = 1 when any triangle is accepted below tMax, else 0.
+ * A ray with a NaN in org, dir or tMax is answered as a miss / not occluded without a walk (under the reference's min / max such a ray
+ * passes every box test and misses every triangle: the same answer after a walk of the whole tree).  The library never stores a NaN t.
+ *
+ * surfaces (nearest: may be NULL): the surface record of each ray's own hit, fetched by the same kernel:
+ *     P = org + t*dir per component (the product is rounded, then the sum); t
+ *     normal = Mesh::getSurfaceProperties' normal (mesh.cpp:311-364); material = the GLOBAL material index (the meshes' materials in order)
+ *     shadingNormal = Material::sampleBump's normal (material.cpp:98-114); meshMaterial = the material's index within its mesh
+ *     uv; primId, meshId as in the hit;  diffuse = Material::sampleDiffuse at uv (material.cpp:87-96)
+ * A miss is the all-zero record with t = -1.
+ * prt_hip_query_surface fetches the same records for hits the caller supplies (primId in mesh order, as nearest reports it), with
+ * rays[r] giving org and dir of P.  Every index read from caller memory is range-checked on the device before it is used as an
+ * address: meshId < the scene's mesh count, primId < that mesh's primitive count; the barycentrics are taken as they are.  A record
+ * that fails the check, a record with t == -1 and a record with a NaN t all give the miss record, and nothing of the scene is read for
+ * them; the records that failed the check are counted (prt_hip_query_get_counts, synchronous: those of the last query_surface).  The
+ * call needs the inverse of the upload's triangle order, one word per triangle slot, built on the device by its first use after
+ * prt_hip_upload_scene and kept until the next upload (prt_hip_update_meshes and the scene edits keep the topology, hence the table).
+ *
+ * n: 1 .. 2^30 rays, any count (PRT_HIP_EINVAL otherwise).  Pointers: DEVICE pointers by default; rays and surfaces must be 16-byte
+ * aligned, hits 4-byte aligned, occluded any; anything else is refused with PRT_HIP_EINVAL and a message before anything is launched.
+ * stream as in prt_hip_render: the query is ordered after the work queued on it and before what is queued next; asynchronous.  With
+ * PRT_HIP_QUERY_HOST in flags all array pointers are HOST pointers: the arrays are staged through buffers the context owns (grown on
+ * demand, freed with the context) and the call returns when the answers are in host memory.  Other flag bits are refused.
+ * For prt_hip_get_stats nearest and any are launches like the position pass, timed as a render: kernelMs, raysTraced = n
+ * (occludedTraced = n too for any), and a stack overflow is reported there.  query_surface is not a launch for the statistics.
+ * One persistent launch per call, a few workgroups per compute unit whatever n is. ---- */
+typedef struct { float org[3]; float tMax; float dir[3]; uint32_t pad; } prt_ray;      /* 32 bytes, 16-byte aligned */
+typedef struct { float P[3]; float t;                /* org + t*dir per component (product rounded, then the sum); t = -1: miss */
+                 float normal[3]; uint32_t material; /* Mesh::getSurfaceProperties' normal; GLOBAL material index (meshes in order) */
+                 float shadingNormal[3]; uint32_t meshMaterial; /* Material::sampleBump's normal; index within the mesh */
+                 float uv[2]; uint32_t primId, meshId;
+                 float diffuse[3]; uint32_t pad; } prt_surface;                        /* 80 bytes */
+#define PRT_HIP_QUERY_HOST 1u  /* all array pointers are HOST pointers: staged through context-owned buffers, the call is synchronous */
+
+int prt_hip_query_nearest(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces /* may be NULL */,
+                          uint32_t flags, void* stream);
+int prt_hip_query_any(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, uint8_t* occluded, uint32_t flags, void* stream);
+int prt_hip_query_surface(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surfaces,
+                          uint32_t flags, void* stream);
+int prt_hip_query_get_counts(prt_hip_ctx* ctx, uint64_t* invalidHits); /* synchronous: records of the last prt_hip_query_surface refused on the device */
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,12 @@ class Hit(C.Structure):
 
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("i", "<f4"), ("j", "<f4"), ("k", "<f4"), ("primId", "<u4"), ("meshId", "<u4")])
+# prt_ray / prt_surface (include/prt_hip.h "ray queries")
+RAY_DTYPE = np.dtype([("org", "<f4", 3), ("tMax", "<f4"), ("dir", "<f4", 3), ("pad", "<u4")])
+SURFACE_DTYPE = np.dtype([("P", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("material", "<u4"), ("shadingNormal", "<f4", 3),
+                          ("meshMaterial", "<u4"), ("uv", "<f4", 2), ("primId", "<u4"), ("meshId", "<u4"), ("diffuse", "<f4", 3),
+                          ("pad", "<u4")])
+QUERY_HOST = 1  # PRT_HIP_QUERY_HOST
 NODE_DTYPE = np.dtype([("lower", "<f4", 3), ("upper", "<f4", 3), ("primOrSecondNodeIndex", "<u4"),
                        ("triVectorIndex", "<u4"), ("primCount", "<u4"), ("splitAxis", "<u4")])
 MATERIAL_DTYPE = np.dtype([("diffuse", "<f4", 3), ("emissive", "<f4", 3), ("reflectionType", "<u4"),
@@ -180,6 +186,7 @@ EXPORTS = [
     "prt_hip_history_export", "prt_hip_history_import", "prt_hip_update_meshes",
     "prt_hip_update_lights", "prt_hip_update_materials", "prt_hip_update_textures",
     "prt_hip_display", "prt_hip_download_display", "prt_hip_display_get_state", "prt_hip_display_reset", "prt_hip_upload",
+    "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -290,6 +297,10 @@ def _load(path, with_test_entry_points):
     L.prt_hip_display_get_state.argtypes = [vp, C.POINTER(DisplayState)]
     L.prt_hip_display_reset.argtypes = [vp]
     L.prt_hip_upload.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.prt_hip_query_nearest.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    L.prt_hip_query_any.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.prt_hip_query_surface.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    L.prt_hip_query_get_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
@@ -1022,6 +1033,69 @@ class PathTracer:
         """The next metered display jumps to its target."""
         self._chk(self._L.prt_hip_display_reset(self._ctx), "prt_hip_display_reset")
 
+    # ---- ray queries (include/prt_hip.h "ray queries"): nearest hit, any hit and surface records for batches of the caller's own rays;
+    # they read the scene and change nothing else in the context
+    def query_nearest_async(self, n, d_rays, d_hits, d_surfaces=None, stream=None):
+        """Queue prt_hip_query_nearest on device arrays: d_rays (n prt_ray, 16-byte aligned), d_hits (n prt_hit), d_surfaces (n
+        prt_surface, 16-byte aligned, or None) are device pointers (int)."""
+        self._chk(self._L.prt_hip_query_nearest(self._ctx, n, d_rays, d_hits, d_surfaces, 0, stream), "prt_hip_query_nearest")
+
+    def query_any_async(self, n, d_rays, d_occluded, stream=None):
+        """Queue prt_hip_query_any on device arrays: d_occluded gets one byte 0 / 1 per ray."""
+        self._chk(self._L.prt_hip_query_any(self._ctx, n, d_rays, d_occluded, 0, stream), "prt_hip_query_any")
+
+    def query_surface_async(self, n, d_rays, d_hits, d_surfaces, stream=None):
+        """Queue prt_hip_query_surface on device arrays: the surface records of the caller's hits (primId in mesh order)."""
+        self._chk(self._L.prt_hip_query_surface(self._ctx, n, d_rays, d_hits, d_surfaces, 0, stream), "prt_hip_query_surface")
+
+    def query_nearest(self, org, dir, t_max, surface=False):
+        """The nearest hit of every ray: org, dir (n, 3) float32, t_max a scalar or (n,).  Returns hits (n,) HIT_DTYPE (t = -1 for a
+        miss; primId in mesh order), and with surface=True (hits, surfaces (n,) SURFACE_DTYPE)."""
+        rays = make_rays(org, dir, t_max)
+        hits = np.zeros(len(rays), dtype=HIT_DTYPE)
+        surf = np.zeros(len(rays), dtype=SURFACE_DTYPE) if surface else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._chk(self._L.prt_hip_query_nearest(self._ctx, len(rays), ptr(rays), ptr(hits), ptr(surf), QUERY_HOST, None), "prt_hip_query_nearest")
+        return (hits, surf) if surface else hits
+
+    def query_any(self, org, dir, t_max):
+        """(n,) uint8: 1 where anything lies on the ray below t_max."""
+        rays = make_rays(org, dir, t_max)
+        occ = np.zeros(len(rays), dtype=np.uint8)
+        self._chk(self._L.prt_hip_query_any(self._ctx, len(rays), rays.ctypes.data_as(C.c_void_p), occ.ctypes.data_as(C.c_void_p), QUERY_HOST, None),
+                  "prt_hip_query_any")
+        return occ
+
+    def query_surface(self, org, dir, hits):
+        """(n,) SURFACE_DTYPE: the surface records of the given hits ((n,) HIT_DTYPE, primId in mesh order) on rays org, dir.  A hit
+        with t = -1 or NaN, or with an index outside the scene, gives the miss record (query_get_counts counts the latter)."""
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+        rays = make_rays(org, dir, 0.0)
+        if len(h) != len(rays):
+            raise PrtError(f"query_surface: {len(h)} hits for {len(rays)} rays")
+        surf = np.zeros(len(rays), dtype=SURFACE_DTYPE)
+        self._chk(self._L.prt_hip_query_surface(self._ctx, len(rays), rays.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p),
+                                                surf.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_query_surface")
+        return surf
+
+    def query_get_counts(self):
+        """Records of the last query_surface that failed the range check on the device."""
+        n = C.c_uint64()
+        self._chk(self._L.prt_hip_query_get_counts(self._ctx, C.byref(n)), "prt_hip_query_get_counts")
+        return int(n.value)
+
+    def pick(self, x, y):
+        """What lies under pixel (x, y) of the current camera: the ray through the pixel's centre (the position guide's ray) ->
+        (hit, surface), one element of HIT_DTYPE and of SURFACE_DTYPE; hit["t"] == -1 for the background."""
+        if self._camera is None:
+            raise PrtError("pick: set a camera first")
+        W, H = self._camera.width, self._camera.height
+        if not (0 <= x < W and 0 <= y < H):
+            raise PrtError(f"pick: pixel ({x}, {y}) outside the {W} x {H} image")
+        rays = pixel_centre_rays(self._camera.desc, [x], [y])
+        hits, surf = self.query_nearest(rays["org"], rays["dir"], rays["tMax"], surface=True)
+        return hits[0], surf[0]
+
     def build_bvh(self, indices, positions):
         """Bvh::build on the GPU (prt_hip_build_bvh): returns (nodes as NODE_DTYPE array, primRemapping, device ms)."""
         idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
@@ -1157,6 +1231,38 @@ def display_host(rgb, params=None, state=None, x0=0, y0=0, x1=None, y1=None, out
 
 def device_count():
     return lib().prt_hip_device_count()
+
+
+# ----------------------------------------------------------------------------- ray queries
+def make_rays(org, dir, t_max):
+    """(n,) RAY_DTYPE from org, dir (n, 3) and t_max (a scalar or (n,)), all taken as float32."""
+    o = np.ascontiguousarray(org, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dir, dtype=np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise PrtError(f"{len(o)} origins for {len(d)} directions")
+    rays = np.zeros(len(o), dtype=RAY_DTYPE)
+    rays["org"], rays["dir"] = o, d
+    rays["tMax"] = np.asarray(t_max, dtype=np.float32)
+    return rays
+
+
+def pixel_centre_rays(cam, xs, ys):
+    """(n,) RAY_DTYPE: the rays through the centres of pixels (xs[k], ys[k]) of camera `cam` (a CameraDesc) -- the position guide's rays
+    (include/prt_hip.h "temporal reprojection": camera_dir with both jitter terms 0.0f, tMax = 100000), operation by operation in float32."""
+    F = np.float32
+    x = np.asarray(xs, dtype=np.uint32).astype(F)
+    y = np.asarray(ys, dtype=np.uint32).astype(F)
+    right, up, fwd, pos = (np.array(list(getattr(cam, k)), dtype=F) for k in ("right", "up", "dir", "pos"))
+    k_aspect = F(cam.width) / F(cam.height)
+    nx = F(2.0) * (x * F(cam.invWidth) - F(0.5) + F(0.0)) * F(0.6) * k_aspect
+    ny = F(-2.0) * (y * F(cam.invHeight) - F(0.5) + F(0.0)) * F(0.6)
+    v = ((nx[:, None] * right + ny[:, None] * up) + fwd).astype(F)
+    inv = F(1.0) / np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+    rays = np.zeros(len(x), dtype=RAY_DTYPE)
+    rays["org"] = pos
+    rays["dir"] = (inv[:, None] * v).astype(F)
+    rays["tMax"] = F(100000.0)
+    return rays
 
 
 # ----------------------------------------------------------------------------- the reference's scene setups (main.cpp:22-105)

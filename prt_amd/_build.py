@@ -21,6 +21,7 @@ SOURCES = [
     "prt_refit.hip",
     "prt_edit.hip",
     "prt_display.hip",
+    "prt_query.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

@@ -213,6 +213,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     prt_denoise_release(c);
     prt_temporal_release(c);
     prt_display_release(c);
+    prt_query_release(c);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);

@@ -39,6 +39,7 @@ const std::string& prt_last_error_string();
 struct PrtRefitMesh {
     uint32_t slotBase = 0, slotCount = 0; // the mesh's triangle slots in tris / shade / bump
     uint32_t vertexCount = 0, hasNormals = 0;
+    uint32_t primCount = 0;               // triangles of the mesh (slotCount minus the pad slots): the range of a caller's primId (prt_query.hip)
     uint32_t rootKid = 0;                 // the root as a kid word (see PrtRefit::kids)
     std::vector<std::pair<uint32_t, uint32_t>> levels; // per depth (root's record first): {first entry in levelList, entries}
     float* dPos = nullptr;                // staging of the caller's positions / normals (3 * vertexCount floats), allocated by the first update
@@ -163,6 +164,11 @@ struct prt_hip_ctx {
     uint8_t* dpOut = nullptr;             // the context's display buffer
     size_t dpOutBytes = 0;                // bytes allocated
     uint32_t dpOutW = 0, dpOutH = 0, dpOutFormat = 0; // image it last held (prt_hip_download_display)
+    // ray queries (prt_query.hip): allocated on first use
+    uint32_t* qInv = nullptr;             // with the scene: slot base of the mesh + mesh-order primId -> triangle slot (0xffffffff: none)
+    unsigned long long* qCounts = nullptr; // device: records the last prt_hip_query_surface refused
+    void* qStage[4] = {nullptr, nullptr, nullptr, nullptr}; // PRT_HIP_QUERY_HOST: rays, hits, surfaces, occlusion bytes on the device
+    size_t qStageBytes[4] = {0, 0, 0, 0};
 };
 
 
@@ -238,6 +244,9 @@ void prt_temporal_forget(prt_hip_ctx* c);
 void prt_temporal_release(prt_hip_ctx* c);
 // prt_display.hip: frees the state, the histogram and the display buffer
 void prt_display_release(prt_hip_ctx* c);
+// prt_query.hip: drops the inverse triangle table with the scene (prt_free_scene); frees the staging buffers (prt_hip_destroy)
+void prt_query_forget(prt_hip_ctx* c);
+void prt_query_release(prt_hip_ctx* c);
 // prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
 // temp == nullptr it only sets tempBytes
 hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,

@@ -1,0 +1,418 @@
+// prt_query.hip -- ray queries (include/prt_hip.h "ray queries"): nearest hit, any hit and surface records for batches of the caller's
+// own rays.  The traversal is trace_loop of prt_device.h, unchanged, behind a ray source that reads prt_ray records and a sink that
+// writes prt_hit / prt_surface / one byte; the surface fetch is get_surface, sample_bump and sample_diffuse, unchanged.  In a
+// translation unit of its own, as prt_temporal.hip and prt_display.hip are, so that the code objects of every other kernel -- the
+// frame kernel's above all -- do not move.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "prt_internal.h"
+
+namespace {
+
+int fail(int code, const std::string& msg) { return prt_fail(code, msg); }
+
+#define PRT_QUERY_MAX_RAYS (1u << 30)
+#define PRT_QUERY_BLOCKS_PER_CU 2 // a workgroup is 16 waves and a CU holds 32: two are resident, more would only queue behind them
+
+static_assert(sizeof(prt_ray) == 32 && sizeof(prt_surface) == 80 && sizeof(prt_hit) == 24, "record sizes of the ray queries");
+
+// What a query needs of the scene beside DevScene: per mesh the first global material and the number of triangles.
+struct QueryMeshes {
+    uint32_t matBase[PRT_MAX_BVH];
+    uint32_t primCount[PRT_MAX_BVH];
+};
+
+struct QueryArgs {
+    DevScene sc;
+    QueryMeshes qm;
+    uint32_t n;
+    const float4* rays; // 2 x float4 per ray: {org, tMax} {dir, pad}
+    prt_hit* hits;
+    float4* surf;       // 5 x float4 per record, or nullptr
+    uint8_t* occ;
+    uint32_t* cursor;
+    uint32_t* spill;
+    uint32_t spillStride;
+    unsigned long long* counters;
+};
+
+__device__ __forceinline__ void store_miss(float4* q)
+{
+    gst4(q, make_float4(0.0f, 0.0f, 0.0f, -1.0f));
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    gst4(q + 1, z);
+    gst4(q + 2, z);
+    gst4(q + 3, z);
+    gst4(q + 4, z);
+}
+
+// The record of hit h (primId = the triangle SLOT, as the traversal reports it) of the ray (org, dir); prim = its primId in its mesh.
+__device__ __forceinline__ void store_surface(const DevScene& sc, const QueryMeshes& qm, Vec3 org, Vec3 dir, const DevHit& h, uint32_t prim, float4* q)
+{
+    Traffic tr{};
+    Surface s;
+    get_surface<false>(sc, h, s, tr);
+    const Vec3 bn = sample_bump<false>(sc, s.mat, s, tr);
+    const Vec3 kd = sample_diffuse<false>(sc, s.mat, s.uv, tr);
+    gst4(q, make_float4(org.x + h.t * dir.x, org.y + h.t * dir.y, org.z + h.t * dir.z, h.t));
+    gst4(q + 1, make_float4(s.normal.x, s.normal.y, s.normal.z, asf(s.mat)));
+    gst4(q + 2, make_float4(bn.x, bn.y, bn.z, asf(s.mat - qm.matBase[h.meshId])));
+    gst4(q + 3, make_float4(s.uv.x, s.uv.y, asf(prim), asf(h.meshId)));
+    gst4(q + 4, make_float4(kd.x, kd.y, kd.z, 0.0f));
+}
+
+template <bool SURFACE>
+struct QuerySrc {
+    const QueryArgs* A;
+    __device__ __forceinline__ uint32_t count() const { return A->n; }
+    __device__ __forceinline__ uint32_t* cursor() const { return A->cursor; }
+    __device__ __forceinline__ void load(uint32_t i, Vec3& org, Vec3& dir, float& maxT, uint32_t& rev) const
+    {
+        const float4 a = gld4(A->rays + 2 * (size_t)i), b = gld4(A->rays + 2 * (size_t)i + 1);
+        org = mk3(a.x, a.y, a.z);
+        dir = mk3(b.x, b.y, b.z);
+        maxT = a.w;
+        rev = 0;
+        // trace_loop answers a ray with a NaN in org or dir without a walk; a NaN limit gets the same answer the same way (every
+        // t < NaN is false, so the walk of the whole tree it would otherwise take records nothing)
+        if (!(maxT == maxT)) org.x = maxT;
+    }
+    __device__ __forceinline__ void store_hit(uint32_t i, const DevHit& h) const
+    {
+        const bool hit = h.t != -1.0f && h.t == h.t; // (a NaN limit leaves hit.t NaN: never stored)
+        prt_hit o;
+        o.t = hit ? h.t : -1.0f; o.i = h.i; o.j = h.j; o.k = h.k;
+        // the device names a hit triangle by its slot; the reference's primId is that triangle's index in its mesh
+        o.primId = hit ? gld(A->sc.triPrim + h.primId) : h.primId;
+        o.meshId = h.meshId;
+        A->hits[i] = o;
+        if (SURFACE) {
+            float4* q = A->surf + 5 * (size_t)i;
+            if (hit) {
+                const float4 a = gld4(A->rays + 2 * (size_t)i), b = gld4(A->rays + 2 * (size_t)i + 1);
+                store_surface(A->sc, A->qm, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), h, o.primId, q);
+            } else {
+                store_miss(q);
+            }
+        }
+    }
+    __device__ __forceinline__ void store_occ(uint32_t i, bool occ) const { A->occ[i] = occ ? 1 : 0; }
+};
+
+template <bool SURFACE>
+__global__ __launch_bounds__(PRT_BLOCK) void query_nearest_kernel(QueryArgs A)
+{
+    __shared__ uint32_t ldsRef[PRT_STACK_LDS * PRT_BLOCK];
+    __shared__ float ldsT[PRT_BLOCK];
+    const uint32_t tid = threadIdx.x;
+    __shared__ uint32_t coopTbl[(PRT_BLOCK / 64) * PRT_COOP_STRIDE];
+    const StackT<PRT_STACK_LDS> st{(lds_u32*)&ldsRef[tid], (lds_f32*)&ldsT[tid], A.spill, A.spillStride, nullptr,
+                                   (lds_u32*)&coopTbl[(tid >> 6) * PRT_COOP_STRIDE]};
+    QuerySrc<SURFACE> src{&A};
+    Traffic tr{};
+    uint32_t overflow = 0;
+    trace_loop<PRT_MODE_SINGLE, false>(A.sc, src, st, tr, overflow);
+    if (overflow) atomicAdd(&A.counters[7], 1ull);
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.counters[0], (unsigned long long)A.n); // raysTraced
+}
+
+__global__ __launch_bounds__(PRT_BLOCK) void query_any_kernel(QueryArgs A)
+{
+    __shared__ uint32_t ldsRef[PRT_STACK_LDS * PRT_BLOCK];
+    __shared__ float ldsT[PRT_BLOCK];
+    const uint32_t tid = threadIdx.x;
+    __shared__ uint32_t coopTbl[(PRT_BLOCK / 64) * PRT_COOP_STRIDE];
+    const StackT<PRT_STACK_LDS> st{(lds_u32*)&ldsRef[tid], (lds_f32*)&ldsT[tid], A.spill, A.spillStride, nullptr,
+                                   (lds_u32*)&coopTbl[(tid >> 6) * PRT_COOP_STRIDE]};
+    QuerySrc<false> src{&A};
+    Traffic tr{};
+    uint32_t overflow = 0;
+    trace_loop<PRT_MODE_OCC_SINGLE, false>(A.sc, src, st, tr, overflow);
+    if (overflow) atomicAdd(&A.counters[7], 1ull);
+    if (blockIdx.x == 0 && tid == 0) {
+        atomicAdd(&A.counters[0], (unsigned long long)A.n); // raysTraced
+        atomicAdd(&A.counters[1], (unsigned long long)A.n); // occludedTraced
+    }
+}
+
+// ============================================================================ the inverse of triPrim
+// inv[slotBase of the mesh + primId] = slot, for every slot that holds a triangle (a pad slot names no vertices: prt_upload.hip);
+// the host has filled inv with 0xffffffff.  A triPrim beyond the mesh's slots cannot come from an accepted upload and is skipped.
+struct IndexArgs {
+    const uint32_t* triPrim;
+    const uint32_t* slotVtx;
+    uint32_t* inv;
+    uint32_t slots, meshes;
+    uint32_t slotBase[PRT_MAX_BVH], slotCount[PRT_MAX_BVH];
+};
+
+__global__ __launch_bounds__(256) void query_index_kernel(IndexArgs a)
+{
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < a.slots; s += gridDim.x * blockDim.x) {
+        if (a.slotVtx[3 * (size_t)s] == 0xffffffffu) continue;
+        const uint32_t prim = a.triPrim[s];
+        for (uint32_t m = 0; m < a.meshes; m++)
+            if (s - a.slotBase[m] < a.slotCount[m] && prim < a.slotCount[m]) a.inv[a.slotBase[m] + prim] = s; // (s < slotBase wraps: false)
+    }
+}
+
+// ============================================================================ surface records of the caller's hits
+struct SurfaceArgs {
+    DevScene sc;
+    QueryMeshes qm;
+    uint32_t n;
+    const float4* rays;
+    const prt_hit* hits;
+    float4* surf;
+    const uint32_t* inv;
+    unsigned long long* invalid;
+};
+
+__global__ __launch_bounds__(256) void query_surface_kernel(SurfaceArgs A)
+{
+    uint32_t bad = 0;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < A.n; r += gridDim.x * blockDim.x) {
+        const prt_hit in = A.hits[r];
+        float4* q = A.surf + 5 * (size_t)r;
+        uint32_t slot = 0xffffffffu;
+        // every index from caller memory is checked before it becomes an address
+        if (in.meshId < A.sc.bvhCount && in.primId < A.qm.primCount[in.meshId]) slot = A.inv[A.sc.primBase[in.meshId] + in.primId];
+        if (slot == 0xffffffffu) {
+            bad++;
+            store_miss(q);
+        } else if (in.t == -1.0f || !(in.t == in.t)) {
+            store_miss(q);
+        } else {
+            const float4 a = gld4(A.rays + 2 * (size_t)r), b = gld4(A.rays + 2 * (size_t)r + 1);
+            DevHit h;
+            h.t = in.t; h.i = in.i; h.j = in.j; h.k = in.k;
+            h.primId = slot;
+            h.meshId = in.meshId;
+            store_surface(A.sc, A.qm, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), h, in.primId, q);
+        }
+    }
+    if (bad) atomicAdd(A.invalid, (unsigned long long)bad);
+}
+
+// ============================================================================ host side
+QueryMeshes query_meshes(const prt_hip_ctx* c)
+{
+    QueryMeshes qm{};
+    for (uint32_t m = 0; m < c->sc.bvhCount && m < PRT_MAX_BVH; m++) {
+        qm.matBase[m] = m < c->ed.meshes.size() ? c->ed.meshes[m].matBase : 0u;
+        qm.primCount[m] = m < c->rf.meshes.size() ? std::min(c->rf.meshes[m].primCount, c->rf.meshes[m].slotCount) : 0u;
+    }
+    return qm;
+}
+
+bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int check_batch(prt_hip_ctx* c, uint32_t n, uint32_t flags, const char* what)
+{
+    if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
+    if (n == 0 || n > PRT_QUERY_MAX_RAYS) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^30");
+    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    return PRT_HIP_OK;
+}
+
+// ENODEVICE on a machine without a device (where no context can exist), EINVAL otherwise
+int null_argument(const char* what)
+{
+    if (prt_hip_device_count() == 0) return fail(PRT_HIP_ENODEVICE, "no HIP device: libprt_hip has no CPU path (the GPU kernels are the product)");
+    return fail(PRT_HIP_EINVAL, std::string(what) + ": NULL argument");
+}
+
+// staging buffer `k` of the HOST flavour, at least `bytes` large
+int stage(prt_hip_ctx* c, int k, size_t bytes)
+{
+    if (c->qStageBytes[k] >= bytes) return PRT_HIP_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream)); // an earlier query may still use the old one
+    if (c->qStage[k]) (void)hipFree(c->qStage[k]);
+    c->qStage[k] = nullptr;
+    c->qStageBytes[k] = 0;
+    HIP_TRY(hipMalloc(&c->qStage[k], bytes));
+    c->qStageBytes[k] = bytes;
+    return PRT_HIP_OK;
+}
+
+int counts_ready(prt_hip_ctx* c)
+{
+    if (!c->qCounts) HIP_TRY(hipMalloc(&c->qCounts, sizeof(unsigned long long)));
+    return PRT_HIP_OK;
+}
+
+// One launch of a traversal kernel over the batch on the context's stream, timed as a render.
+int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surf, uint8_t* occ, bool any)
+{
+    hipStream_t s = c->stream;
+    const uint32_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
+    const uint32_t resident = (uint32_t)(c->computeUnits * PRT_QUERY_BLOCKS_PER_CU);
+    const uint32_t blocks = std::min<uint32_t>(want, resident);
+    int rc = prt_launch_resources(c, resident);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
+    QueryArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, occ, c->work, c->spill, c->spillThreads, c->counters};
+    hipEvent_t ev0, ev1;
+    if ((rc = prt_timing_pair(c, &ev0, &ev1))) return rc;
+    HIP_TRY(hipEventRecord(ev0, s));
+    const char* name = any ? "query_any_kernel" : "query_nearest_kernel";
+    if (any) hipLaunchKernelGGL(query_any_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
+    else if (surf) hipLaunchKernelGGL(query_nearest_kernel<true>, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL(query_nearest_kernel<false>, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
+    if ((rc = prt_launched(name))) return rc;
+    HIP_TRY(hipEventRecord(ev1, s));
+    c->timed = false;
+    return PRT_HIP_OK;
+}
+
+// The inverse table of the uploaded scene on the context's stream (first use after an upload).
+int inverse_ready(prt_hip_ctx* c)
+{
+    if (c->qInv) return PRT_HIP_OK;
+    const PrtRefit& R = c->rf;
+    if (R.slots == 0 || R.slots > 0xffffffffull || !R.slotVtx || R.meshes.size() != c->sc.bvhCount)
+        return fail(PRT_HIP_ESTATE, "query_surface: the scene holds no triangle slots");
+    IndexArgs a{};
+    a.triPrim = c->sc.triPrim;
+    a.slotVtx = R.slotVtx;
+    a.slots = (uint32_t)R.slots;
+    a.meshes = c->sc.bvhCount;
+    for (uint32_t m = 0; m < a.meshes; m++) {
+        const PrtRefitMesh& rm = R.meshes[m];
+        if ((uint64_t)rm.slotBase + rm.slotCount > R.slots || rm.slotBase != c->sc.primBase[m])
+            return fail(PRT_HIP_ESTATE, "query_surface: slot range outside the scene");
+        a.slotBase[m] = rm.slotBase;
+        a.slotCount[m] = rm.slotCount;
+    }
+    HIP_TRY(hipMalloc(&c->qInv, R.slots * sizeof(uint32_t)));
+    a.inv = c->qInv;
+    HIP_TRY(hipMemsetAsync(c->qInv, 0xff, R.slots * sizeof(uint32_t), c->stream));
+    const uint32_t blocks = std::min<uint32_t>((a.slots + 255u) / 256u, 65535u);
+    hipLaunchKernelGGL(query_index_kernel, dim3(blocks), dim3(256), 0, c->stream, a);
+    return prt_launched("query_index_kernel");
+}
+
+int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surf)
+{
+    int rc;
+    if ((rc = inverse_ready(c)) || (rc = counts_ready(c))) return rc;
+    HIP_TRY(hipMemsetAsync(c->qCounts, 0, sizeof(unsigned long long), c->stream));
+    SurfaceArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, c->qInv, c->qCounts};
+    const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)c->computeUnits * 8u);
+    hipLaunchKernelGGL(query_surface_kernel, dim3(blocks), dim3(256), 0, c->stream, A);
+    return prt_launched("query_surface_kernel");
+}
+
+} // namespace
+
+void prt_query_forget(prt_hip_ctx* c)
+{
+    if (c->qInv) (void)hipFree(c->qInv);
+    c->qInv = nullptr;
+}
+
+void prt_query_release(prt_hip_ctx* c)
+{
+    prt_query_forget(c);
+    if (c->qCounts) (void)hipFree(c->qCounts);
+    c->qCounts = nullptr;
+    for (int k = 0; k < 4; k++) {
+        if (c->qStage[k]) (void)hipFree(c->qStage[k]);
+        c->qStage[k] = nullptr;
+        c->qStageBytes[k] = 0;
+    }
+}
+
+extern "C" {
+
+int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
+{
+    if (!c || !rays || !hits) return null_argument("query_nearest");
+    int rc = check_batch(c, n, flags, "query_nearest");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (flags & PRT_HIP_QUERY_HOST) {
+        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 1, (size_t)n * sizeof(prt_hit))) ||
+            (surfaces && (rc = stage(c, 2, (size_t)n * sizeof(prt_surface)))))
+            return rc;
+        hipStream_t s = c->stream;
+        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        if ((rc = launch_trace(c, n, (const prt_ray*)c->qStage[0], (prt_hit*)c->qStage[1], surfaces ? (prt_surface*)c->qStage[2] : nullptr, nullptr, false)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(hits, c->qStage[1], (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
+        if (surfaces) HIP_TRY(hipMemcpyAsync(surfaces, c->qStage[2], (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return PRT_HIP_OK;
+    }
+    if (!aligned(rays, 16) || !aligned(hits, 4) || (surfaces && !aligned(surfaces, 16)))
+        return fail(PRT_HIP_EINVAL, "query_nearest: rays and surfaces must be 16-byte aligned, hits 4-byte aligned");
+    hipStream_t caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_trace(c, n, rays, hits, surfaces, nullptr, false))) return rc;
+    return prt_stream_leave(c, caller);
+}
+
+int prt_hip_query_any(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, uint8_t* occluded, uint32_t flags, void* stream)
+{
+    if (!c || !rays || !occluded) return null_argument("query_any");
+    int rc = check_batch(c, n, flags, "query_any");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (flags & PRT_HIP_QUERY_HOST) {
+        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 3, (size_t)n))) return rc;
+        hipStream_t s = c->stream;
+        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        if ((rc = launch_trace(c, n, (const prt_ray*)c->qStage[0], nullptr, nullptr, (uint8_t*)c->qStage[3], true))) return rc;
+        HIP_TRY(hipMemcpyAsync(occluded, c->qStage[3], (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return PRT_HIP_OK;
+    }
+    if (!aligned(rays, 16)) return fail(PRT_HIP_EINVAL, "query_any: rays must be 16-byte aligned");
+    hipStream_t caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_trace(c, n, rays, nullptr, nullptr, occluded, true))) return rc;
+    return prt_stream_leave(c, caller);
+}
+
+int prt_hip_query_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
+{
+    if (!c || !rays || !hits || !surfaces) return null_argument("query_surface");
+    int rc = check_batch(c, n, flags, "query_surface");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (flags & PRT_HIP_QUERY_HOST) {
+        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 1, (size_t)n * sizeof(prt_hit))) ||
+            (rc = stage(c, 2, (size_t)n * sizeof(prt_surface))))
+            return rc;
+        hipStream_t s = c->stream;
+        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->qStage[1], hits, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
+        if ((rc = launch_surface(c, n, (const prt_ray*)c->qStage[0], (const prt_hit*)c->qStage[1], (prt_surface*)c->qStage[2]))) return rc;
+        HIP_TRY(hipMemcpyAsync(surfaces, c->qStage[2], (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return PRT_HIP_OK;
+    }
+    if (!aligned(rays, 16) || !aligned(hits, 4) || !aligned(surfaces, 16))
+        return fail(PRT_HIP_EINVAL, "query_surface: rays and surfaces must be 16-byte aligned, hits 4-byte aligned");
+    hipStream_t caller;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_surface(c, n, rays, hits, surfaces))) return rc;
+    return prt_stream_leave(c, caller);
+}
+
+int prt_hip_query_get_counts(prt_hip_ctx* c, uint64_t* invalidHits)
+{
+    if (!c || !invalidHits) return null_argument("query_get_counts");
+    *invalidHits = 0;
+    if (!c->qCounts) return PRT_HIP_OK; // no query_surface yet
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, c->qCounts, sizeof(v), hipMemcpyDeviceToHost));
+    *invalidHits = v;
+    return PRT_HIP_OK;
+}
+
+} // extern "C"

@@ -49,6 +49,7 @@ void prt_free_scene(prt_hip_ctx* c)
     for (void* p : c->sceneAllocs) (void)hipFree(p);
     c->sceneAllocs.clear();
     prt_refit_forget(c);
+    prt_query_forget(c);
     c->ed = PrtEdit{};
     c->haveScene = false;
 }
@@ -280,6 +281,7 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
             rm.slotBase = triBase;
             rm.slotCount = slotCount;
             rm.vertexCount = md.vertexCount;
+            rm.primCount = md.primCount;
             rm.hasNormals = md.normals ? 1u : 0u;
             refitMeshes.push_back(std::move(rm));
         }
