@@ -53,13 +53,9 @@ int prt_own_framebuffer(prt_hip_ctx* c, float** d_rgb)
 {
     if (*d_rgb) return PRT_HIP_OK;
     const size_t n = (size_t)c->cam.width * c->cam.height;
-    if (c->fbPixels != n) {
-        if (c->fb) (void)hipFree(c->fb);
-        c->fb = nullptr;
-        HIP_TRY(hipMalloc(&c->fb, n * 3 * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(c->fb, 0, n * 3 * sizeof(float), c->stream));
-        c->fbPixels = n;
-    }
+    bool fresh = false;
+    HIP_TRY(c->fb.fit(n * 3, c->stream, &fresh));
+    if (fresh) HIP_TRY(hipMemsetAsync(c->fb, 0, n * 3 * sizeof(float), c->stream));
     *d_rgb = c->fb;
     return PRT_HIP_OK;
 }
@@ -74,13 +70,7 @@ int prt_launched(const char* kernel)
 // Per-thread spill columns of the traversal stacks (entries beyond those kept in LDS): [entry][thread], two words per entry.
 int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks)
 {
-    uint32_t threads = blocks * PRT_BLOCK;
-    if (threads > c->spillThreads) {
-        if (c->spill) (void)hipFree(c->spill);
-        c->spill = nullptr;
-        HIP_TRY(hipMalloc(&c->spill, (size_t)threads * 2 * (PRT_STACK_MAX - PRT_STACK_LDS_PACKET) * sizeof(uint32_t)));
-        c->spillThreads = threads;
-    }
+    HIP_TRY(c->spill.grow((size_t)blocks * PRT_BLOCK * 2 * (PRT_STACK_MAX - PRT_STACK_LDS_PACKET), c->stream));
     return PRT_HIP_OK;
 }
 
@@ -158,9 +148,9 @@ static int create_resources(prt_hip_ctx* c)
     HIP_TRY(hipStreamCreate(&c->stream));
     HIP_TRY(hipEventCreateWithFlags(&c->evIn, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->evOut, hipEventDisableTiming));
-    HIP_TRY(hipMalloc(&c->work, (PRT_WORK_WORDS + PRT_STICKY_WORDS) * sizeof(uint32_t)));
+    HIP_TRY(c->work.fit(PRT_WORK_WORDS + PRT_STICKY_WORDS, c->stream));
     HIP_TRY(hipMemset(c->work, 0, (PRT_WORK_WORDS + PRT_STICKY_WORDS) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->counters, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long)));
+    HIP_TRY(c->counters.fit(PRT_STAT_SHARDS * PRT_STAT_STRIDE, c->stream));
     HIP_TRY(hipMemset(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long)));
     return PRT_HIP_OK;
 }
@@ -194,26 +184,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     prt_free_scene(c);
-    if (c->fb) (void)hipFree(c->fb);
-    if (c->work) (void)hipFree(c->work);
-    if (c->counters) (void)hipFree(c->counters);
-    if (c->spill) (void)hipFree(c->spill);
-    if (c->wfBuffer) (void)hipFree(c->wfBuffer);
-    if (c->frameArgs) (void)hipFree(c->frameArgs);
-    if (c->accRng) (void)hipFree(c->accRng);
-    if (c->accSum) (void)hipFree(c->accSum);
-    if (c->accMom) (void)hipFree(c->accMom);
-    if (c->adCode) (void)hipFree(c->adCode);
-    if (c->adList) (void)hipFree(c->adList);
-    if (c->adFlag) (void)hipFree(c->adFlag);
-    if (c->adTemp) (void)hipFree(c->adTemp);
-    if (c->adCount) (void)hipFree(c->adCount);
-    if (c->adErr) (void)hipFree(c->adErr);
     if (c->adCountHost) (void)hipHostFree(c->adCountHost);
-    prt_denoise_release(c);
-    prt_temporal_release(c);
-    prt_display_release(c);
-    prt_query_release(c);
     prt_gather_release(c);
     for (int k = 0; k < PRT_TIMING_RING; k++) {
         if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
@@ -222,7 +193,7 @@ void prt_hip_destroy(prt_hip_ctx* c)
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->evOut) (void)hipEventDestroy(c->evOut);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // frees the context's buffers (DevBuf)
 }
 
 int prt_hip_device_info(prt_hip_ctx* c, char* name, size_t cap, int* computeUnits)
@@ -249,13 +220,13 @@ int prt_hip_set_camera(prt_hip_ctx* c, const prt_camera_desc* cam)
     return PRT_HIP_OK;
 }
 
-float* prt_hip_framebuffer(prt_hip_ctx* c) { return c ? c->fb : nullptr; }
+float* prt_hip_framebuffer(prt_hip_ctx* c) { return c ? (float*)c->fb : nullptr; }
 
 int prt_hip_download(prt_hip_ctx* c, float* rgb_host, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1)
 {
     if (!c || !rgb_host) return fail(PRT_HIP_EINVAL, "NULL argument");
-    if (!c->fb) return fail(PRT_HIP_ESTATE, "nothing rendered into the context framebuffer");
     const uint32_t W = c->cam.width;
+    if (!c->fb || c->fb.size() != (size_t)W * c->cam.height * 3) return fail(PRT_HIP_ESTATE, "nothing rendered into the context framebuffer");
     int rc = prt_check_rect(c, x0, y0, x1, y1);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));

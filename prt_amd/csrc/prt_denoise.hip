@@ -213,21 +213,18 @@ int check_guide_samples(uint32_t k)
     return PRT_HIP_OK;
 }
 
-// The planes at the camera's size (the context's stream must not be using the old ones: it is synchronised before they go).
+// The planes at the camera's size; new planes hold neither guides nor a filtered image.
 int planes_ready(prt_hip_ctx* c)
 {
     const size_t n = (size_t)c->cam.width * c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->dnPixels == n) return PRT_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    prt_denoise_release(c);
-    HIP_TRY(hipMalloc(&c->dnAlbedo, n * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->dnNormal, n * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->dnGuideA, n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&c->dnGuideN, n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&c->dnPlane[0], n * sizeof(float4)));
-    HIP_TRY(hipMalloc(&c->dnPlane[1], n * sizeof(float4)));
-    c->dnPixels = n;
+    bool fresh = false;
+    hipError_t e = c->dnAlbedo.fit(n * 3, c->stream, &fresh);
+    if (e == hipSuccess) e = c->dnNormal.fit(n * 3, c->stream, &fresh);
+    for (auto* b : {&c->dnGuideA, &c->dnGuideN, &c->dnPlane[0], &c->dnPlane[1]})
+        if (e == hipSuccess) e = b->fit(n, c->stream, &fresh);
+    if (fresh) prt_denoise_forget(c);
+    HIP_TRY(e);
     return PRT_HIP_OK;
 }
 
@@ -249,7 +246,7 @@ int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K)
     c->dnGuidesValid = false;
     const uint32_t W = c->cam.width, H = c->cam.height;
     const size_t nf = (size_t)W * H * 3;
-    float* tmp = (float*)c->dnPlane[1];
+    float* tmp = (float*)(float4*)c->dnPlane[1];
     for (int plane = 0; plane < 2; plane++) {
         float* g = plane == 0 ? c->dnAlbedo : c->dnNormal;
         for (uint32_t k = 0; k < K; k++) {
@@ -275,7 +272,7 @@ int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, floa
     const uint32_t W = c->cam.width, H = c->cam.height;
     const size_t n = (size_t)W * H;
     hipStream_t s = c->stream;
-    const float4* mom = (c->accMom && c->momPixels == n && !c->momClear) ? c->accMom : nullptr;
+    const float4* mom = (c->accMom.size() == n && !c->momClear) ? c->accMom : nullptr;
     int rc;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     hipLaunchKernelGGL(dn_prepare_kernel, dim3(grid1d(c, n)), dim3(256), 0, s, (const float4*)c->accSum, mom, (const float*)c->dnAlbedo,
@@ -317,7 +314,7 @@ int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
     if (rc) return rc;
     if ((rc = check_guide_samples(d->guideSamples))) return rc;
     if (!c->haveScene || !c->haveCamera) return fail(PRT_HIP_ESTATE, "upload a scene and set a camera first");
-    if (c->accMax == 0 || c->accClear || !c->accSum || c->accPixels != (size_t)c->cam.width * c->cam.height)
+    if (c->accMax == 0 || c->accClear || !c->accSum || c->accSum.size() != (size_t)c->cam.width * c->cam.height)
         return fail(PRT_HIP_ESTATE, "denoise: the accumulator is empty (render or import samples first)");
     if (c->cam.width > 65535 || c->cam.height > 65535) return fail(PRT_HIP_EINVAL, "image too large");
     return PRT_HIP_OK;
@@ -325,23 +322,6 @@ int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d)
 
 void prt_denoise_forget(prt_hip_ctx* c)
 {
-    c->dnGuidesValid = false;
-    c->dnHostGuides = false;
-    c->dnLast = -1;
-}
-
-void prt_denoise_release(prt_hip_ctx* c)
-{
-    if (c->dnAlbedo) (void)hipFree(c->dnAlbedo);
-    if (c->dnNormal) (void)hipFree(c->dnNormal);
-    if (c->dnGuideA) (void)hipFree(c->dnGuideA);
-    if (c->dnGuideN) (void)hipFree(c->dnGuideN);
-    if (c->dnPlane[0]) (void)hipFree(c->dnPlane[0]);
-    if (c->dnPlane[1]) (void)hipFree(c->dnPlane[1]);
-    c->dnAlbedo = c->dnNormal = nullptr;
-    c->dnGuideA = c->dnGuideN = nullptr;
-    c->dnPlane[0] = c->dnPlane[1] = nullptr;
-    c->dnPixels = 0;
     c->dnGuidesValid = false;
     c->dnHostGuides = false;
     c->dnLast = -1;
@@ -361,7 +341,7 @@ int prt_hip_denoise_set_guides(prt_hip_ctx* c, const float* albedo, const float*
     if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
     int rc = planes_ready(c);
     if (rc) return rc;
-    const size_t bytes = c->dnPixels * 3 * sizeof(float);
+    const size_t bytes = c->dnAlbedo.size() * sizeof(float);
     HIP_TRY(hipStreamSynchronize(c->stream)); // a denoise may still be reading the old planes
     HIP_TRY(hipMemcpy(c->dnAlbedo, albedo, bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->dnNormal, normal, bytes, hipMemcpyHostToDevice));
@@ -376,7 +356,7 @@ int prt_hip_denoise_get_guides(prt_hip_ctx* c, uint32_t guideSamples, float* alb
     int rc = check_guide_samples(guideSamples);
     if (rc) return rc;
     if ((rc = prt_denoise_guides_ready(c, guideSamples))) return rc;
-    const size_t bytes = c->dnPixels * 3 * sizeof(float);
+    const size_t bytes = c->dnAlbedo.size() * sizeof(float);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(albedo, c->dnAlbedo, bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(normal, c->dnNormal, bytes, hipMemcpyDeviceToHost));
@@ -400,7 +380,7 @@ int prt_hip_denoise_variance(prt_hip_ctx* c, float* var)
     if (!c || !var) return fail(PRT_HIP_EINVAL, "NULL argument");
     if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
     const size_t n = (size_t)c->cam.width * c->cam.height;
-    if (c->dnLast < 0 || c->dnPixels != n) return fail(PRT_HIP_ESTATE, "denoise_variance: no denoise of this view yet");
+    if (c->dnLast < 0 || c->dnPlane[0].size() != n) return fail(PRT_HIP_ESTATE, "denoise_variance: no denoise of this view yet");
     HIP_TRY(hipSetDevice(c->device));
     std::vector<float4> h(n);
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -479,8 +459,8 @@ int prt_hip_test_copy_yardstick(prt_hip_ctx* c, uint64_t pixels, int read16, int
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)pixels;
     const size_t bytes = n * (size_t)(16 * (read16 + write16) + 12 * (read12 + write12));
-    char* buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, bytes));
+    DevBuf<char> buf;
+    HIP_TRY(buf.fit(bytes, c->stream));
     HIP_TRY(hipMemsetAsync(buf, 0, bytes, c->stream));
     CopyArgs A{};
     char* q = buf;
@@ -500,7 +480,6 @@ int prt_hip_test_copy_yardstick(prt_hip_ctx* c, uint64_t pixels, int read16, int
     HIP_TRY(hipEventElapsedTime(ms, e0, e1));
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
     return prt_launched("dn_copy_kernel");
 }
 

@@ -138,10 +138,10 @@ int dp_check(const prt_hip_ctx* c, const prt_display_params* p, uint32_t x0, uin
 // state and histogram, zeroed (valid = 0) on the context's stream when they are first needed
 int dp_state_ready(prt_hip_ctx* c)
 {
-    if (c->dpState) return PRT_HIP_OK;
-    if (!c->dpHist) HIP_TRY(hipMalloc(&c->dpHist, DP_HIST_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->dpState, sizeof(prt_display_state)));
-    HIP_TRY(hipMemsetAsync(c->dpState, 0, sizeof(prt_display_state), c->stream));
+    bool fresh = false;
+    HIP_TRY(c->dpHist.fit(DP_HIST_WORDS, c->stream));
+    HIP_TRY(c->dpState.fit(1, c->stream, &fresh));
+    if (fresh) HIP_TRY(hipMemsetAsync(c->dpState, 0, sizeof(prt_display_state), c->stream));
     return PRT_HIP_OK;
 }
 
@@ -149,15 +149,9 @@ int dp_state_ready(prt_hip_ctx* c)
 int dp_own_buffer(prt_hip_ctx* c, uint32_t format, uint8_t** d_out)
 {
     const size_t bytes = (size_t)c->cam.width * c->cam.height * prt_display_bpp(format);
-    if (bytes > c->dpOutBytes) {
-        if (c->dpOut) (void)hipFree(c->dpOut);
-        c->dpOut = nullptr;
-        c->dpOutBytes = 0;
-        c->dpOutW = c->dpOutH = 0;
-        HIP_TRY(hipMalloc(&c->dpOut, bytes));
-        HIP_TRY(hipMemsetAsync(c->dpOut, 0, bytes, c->stream));
-        c->dpOutBytes = bytes;
-    }
+    bool fresh = false;
+    HIP_TRY(c->dpOut.grow(bytes, c->stream, &fresh));
+    if (fresh) HIP_TRY(hipMemsetAsync(c->dpOut, 0, bytes, c->stream));
     c->dpOutW = c->cam.width;
     c->dpOutH = c->cam.height;
     c->dpOutFormat = format;
@@ -197,17 +191,6 @@ int dp_queue(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
 }
 } // namespace
 
-void prt_display_release(prt_hip_ctx* c)
-{
-    if (c->dpState) (void)hipFree(c->dpState);
-    if (c->dpHist) (void)hipFree(c->dpHist);
-    if (c->dpOut) (void)hipFree(c->dpOut);
-    c->dpState = nullptr;
-    c->dpHist = nullptr;
-    c->dpOut = nullptr;
-    c->dpOutBytes = 0;
-}
-
 extern "C" {
 
 int prt_hip_display(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_display_params* p, const float* d_rgb,
@@ -218,7 +201,7 @@ int prt_hip_display(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint3
     if (d_out && p->format != 0 && (uintptr_t)d_out % 4 != 0) return fail(PRT_HIP_EINVAL, "display: d_out of a 4-byte format must be 4-byte aligned");
     if (d_rgb && (uintptr_t)d_rgb % 4 != 0) return fail(PRT_HIP_EINVAL, "display: d_rgb must be 4-byte aligned");
     if (!d_rgb && !c->fb) return fail(PRT_HIP_ESTATE, "display: nothing rendered or uploaded into the context framebuffer");
-    if (!d_rgb && c->fbPixels != (size_t)c->cam.width * c->cam.height)
+    if (!d_rgb && c->fb.size() != (size_t)c->cam.width * c->cam.height * 3)
         return fail(PRT_HIP_ESTATE, "display: the context framebuffer holds an image of another camera's size");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t caller;
@@ -303,7 +286,7 @@ int prt_hip_test_display_profile(prt_hip_ctx* c, const prt_display_params* p, ui
     if (!ms3 || reps == 0) return fail(PRT_HIP_EINVAL, "NULL argument");
     int rc = dp_check(c, p, 0, 0, 0, 0);
     if (rc) return rc;
-    if (!c->fb || c->fbPixels != (size_t)c->cam.width * c->cam.height) return fail(PRT_HIP_ESTATE, "display profile: render or upload an image first");
+    if (!c->fb || c->fb.size() != (size_t)c->cam.width * c->cam.height * 3) return fail(PRT_HIP_ESTATE, "display profile: render or upload an image first");
     HIP_TRY(hipSetDevice(c->device));
     uint8_t* d_out = nullptr;
     if ((rc = dp_state_ready(c)) || (rc = dp_own_buffer(c, p->format, &d_out))) return rc;

@@ -67,17 +67,6 @@ uint32_t tiles_owned(uint32_t totalTiles, uint32_t rank, uint32_t nranks)
     return rank < totalTiles ? (totalTiles - rank + nranks - 1) / nranks : 0;
 }
 
-int ensure_floats(float** buf, size_t* have, size_t need)
-{
-    if (need <= *have) return PRT_HIP_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc((void**)buf, std::max<size_t>(need, 64) * sizeof(float)));
-    *have = need;
-    return PRT_HIP_OK;
-}
-
 void launch_pack(bool unpack, float* frame, float* packed, uint32_t W, uint32_t H, uint32_t T, uint32_t rank, uint32_t nranks, uint32_t tiles,
                  hipStream_t s)
 {
@@ -199,10 +188,6 @@ int need_rccl(Rccl** out)
 
 void prt_gather_release(prt_hip_ctx* c)
 {
-    if (c->packBuf) (void)hipFree(c->packBuf);
-    if (c->stageBuf) (void)hipFree(c->stageBuf);
-    c->packBuf = c->stageBuf = nullptr;
-    c->packFloats = c->stageFloats = 0;
     if (c->comm) drop_comm(rccl(), c);
 }
 
@@ -310,7 +295,7 @@ int prt_hip_gather_rccl(prt_hip_ctx* c, float* d_rgb, int root, void* stream)
     if (n > 1) {
         if (me != (uint32_t)root) {
             const uint32_t mine = tiles_owned(totalTiles, me, n);
-            if ((rc = ensure_floats(&c->packBuf, &c->packFloats, mine * tileFloats))) return rc;
+            HIP_TRY(c->packBuf.grow(std::max<size_t>(mine * tileFloats, 64), c->stream));
             launch_pack(false, d_rgb, c->packBuf, W, H, T, me, n, mine, s);
             RCCL_TRY(*R, R->GroupStart());
             if (mine) RCCL_TRY_IN_GROUP(*R, c, R->Send(c->packBuf, mine * tileFloats, kNcclFloat, root, c->comm, s));
@@ -319,7 +304,7 @@ int prt_hip_gather_rccl(prt_hip_ctx* c, float* d_rgb, int root, void* stream)
             // staged tiles of rank r start at off[r]; the root's own tiles are already where they belong
             std::vector<size_t> off(n + 1, 0);
             for (uint32_t r = 0; r < n; r++) off[r + 1] = off[r] + (r == me ? 0 : (size_t)tiles_owned(totalTiles, r, n) * tileFloats);
-            if ((rc = ensure_floats(&c->stageBuf, &c->stageFloats, off[n]))) return rc;
+            HIP_TRY(c->stageBuf.grow(std::max<size_t>(off[n], 64), c->stream));
             RCCL_TRY(*R, R->GroupStart());
             for (uint32_t r = 0; r < n; r++) {
                 const size_t cnt = off[r + 1] - off[r];
@@ -367,11 +352,11 @@ int prt_hip_gather(prt_hip_ctx* const* ctxs, int n, float* rgb_host, uint32_t x0
         const uint32_t mine = tiles_owned(totalTiles, (uint32_t)i, (uint32_t)n);
         if (mine == 0) continue;
         HIP_TRY(hipSetDevice(c->device));
-        if ((rc = ensure_floats(&c->packBuf, &c->packFloats, mine * tileFloats))) return rc;
+        HIP_TRY(c->packBuf.grow(std::max<size_t>(mine * tileFloats, 64), c->stream));
         launch_pack(false, c->fb, c->packBuf, W, H, T, (uint32_t)i, (uint32_t)n, mine, c->stream);
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipSetDevice(root->device));
-        if ((rc = ensure_floats(&root->stageBuf, &root->stageFloats, mine * tileFloats))) return rc;
+        HIP_TRY(root->stageBuf.grow(std::max<size_t>(mine * tileFloats, 64), root->stream));
         HIP_TRY(hipStreamSynchronize(root->stream)); // the previous unpack has consumed the staging buffer
         if (c->device == root->device) HIP_TRY(hipMemcpy(root->stageBuf, c->packBuf, mine * tileFloats * sizeof(float), hipMemcpyDeviceToDevice));
         else HIP_TRY(hipMemcpyPeer(root->stageBuf, root->device, c->packBuf, c->device, mine * tileFloats * sizeof(float)));

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/prt_hip.h"
+#include "prt_devbuf.h"
 #include "prt_device.h"
 
 #define PRT_WORK_WORDS 512 // control words of a launch (frame kernel: prt_frame.h PRT_CTRL_CURSORS; claim cursor of the G-buffer kernel)
@@ -91,88 +92,73 @@ struct prt_hip_ctx {
     std::vector<void*> sceneAllocs;
     PrtRefit rf;                // device allocations of it are in sceneAllocs
     PrtEdit ed;
-    // render resources
-    float* fb = nullptr;
-    size_t fbPixels = 0;
-    uint32_t* work = nullptr; // Q_COUNT queue counters
-    unsigned long long* counters = nullptr;
+    // render resources.  Every device buffer of the context is a DevBuf (prt_devbuf.h): it is freed with the context, and a (re)allocation
+    // synchronises the context's stream before the old memory goes.
+    DevBuf<float> fb;           // the context's own framebuffer, at the size of the camera it was last rendered or uploaded for
+    DevBuf<uint32_t> work;      // PRT_WORK_WORDS control words of a launch + PRT_STICKY_WORDS
+    DevBuf<unsigned long long> counters;
     hipEvent_t evIn = nullptr, evOut = nullptr; // order the pipeline against a caller's stream
-    void* wfBuffer = nullptr; // the frame kernel's pool state and ray queues
-    size_t wfBytes = 0;
-    uint32_t* spill = nullptr;
-    uint32_t spillThreads = 0;
+    DevBuf<char> wfBuffer;      // the frame kernel's pool state and ray queues
+    DevBuf<uint32_t> spill;     // spill columns of the traversal stacks: [entry][thread], two words per entry (prt_launch_resources)
+    uint32_t spillThreads() const { return (uint32_t)(spill.size() / (2 * (PRT_STACK_MAX - PRT_STACK_LDS_PACKET))); }
     uint32_t lastRank = 0, lastNranks = 0, lastTile = 0; // of the last render (prt_hip_gather*)
-    float* lastTarget = nullptr;                         // framebuffer of the last render (device)
     // image gather (prt_gather.hip): tile-major staging buffers and the RCCL communicator
     void* comm = nullptr;       // ncclComm_t
     bool commOwned = false;     // created by prt_hip_comm_init (destroyed with the context) or adopted from the host
     bool commBroken = false;    // a send / receive failed: the communicator is refused until it is replaced (prt_gather.hip)
     int commRank = 0, commSize = 0;
-    float* packBuf = nullptr;   // this rank's tiles, tile-major
-    size_t packFloats = 0;
-    float* stageBuf = nullptr;  // root: the other ranks' tiles as received
-    size_t stageFloats = 0;
-    int frameBlocksPerCU = 0;  // resident blocks per CU of the frame kernel
-    bool frameLaunched = false;
-    void* frameArgs = nullptr;  // device copies of the frame kernel's argument block (ring)
-    uint32_t frameArgSlot = 0;
-    bool timed = false;
+    DevBuf<float> packBuf;      // this rank's tiles, tile-major
+    DevBuf<float> stageBuf;     // root: the other ranks' tiles as received
+    int frameBlocksPerCU = 0;   // resident blocks per CU of the frame kernel
     // progressive rendering (prt_hip_render_accumulate): one record per camera pixel, allocated on first use
-    uint32_t* accRng = nullptr;  // generator state
-    float4* accSum = nullptr;    // colour sum, bits(count)
-    size_t accPixels = 0;        // records allocated
+    DevBuf<uint32_t> accRng;     // generator state
+    DevBuf<float4> accSum;       // colour sum, bits(count)
     bool accClear = true;        // the records must be zeroed before the next use (a reset since the last pass)
     uint32_t accMax = 0;         // upper bound of any pixel's count; 0 = empty, the estimator is not bound yet
     uint32_t accSeed = 0, accMaxDepth = 0, accRrDepth = 0; // the estimator the accumulated samples came from (accMax > 0)
     // adaptive sampling (prt_hip_render_adaptive): allocated on first use
-    float4* accMom = nullptr;    // per camera pixel: {mean, M2, bits(m), 0}
-    size_t momPixels = 0;        // records allocated
+    DevBuf<float4> accMom;       // per camera pixel: {mean, M2, bits(m), 0}
     bool momClear = true;        // the moment records must be zeroed before their next use
-    uint32_t* adCode = nullptr;  // per work item of a pass: its pixel code (the selection's output)
-    uint32_t* adList = nullptr;  // the compacted codes of the active pixels, padded to a multiple of 64 (the frame kernel's input)
-    uint8_t* adFlag = nullptr;   // per work item: 1 = active
-    size_t adItems = 0;          // work items the three buffers hold
-    void* adTemp = nullptr;      // hipcub scratch of the compaction
-    size_t adTempBytes = 0;
-    uint32_t* adCount = nullptr;     // device: active pixels of the last selection
+    DevBuf<uint32_t> adCode;     // per work item of a pass: its pixel code (the selection's output)
+    DevBuf<uint32_t> adList;     // the compacted codes of the active pixels, padded to a multiple of 64 (the frame kernel's input)
+    DevBuf<uint8_t> adFlag;      // per work item: 1 = active
+    DevBuf<char> adTemp;         // hipcub scratch of the compaction
+    DevBuf<uint32_t> adCount;    // active pixels of the last selection
     uint32_t* adCountHost = nullptr; // pinned host copy of it
-    float* adErr = nullptr;          // prt_hip_accum_error: the rectangle's errors (device)
-    size_t adErrItems = 0;
+    DevBuf<float> adErr;         // prt_hip_accum_error: the rectangle's errors
     // denoised previews (prt_denoise.hip): guide and scratch planes at the camera's size, allocated on first use
-    float* dnAlbedo = nullptr;   // guide planes, 3 floats per pixel: the average of dnGuideK G-buffer launches, or the host's own
-    float* dnNormal = nullptr;
-    float4* dnGuideA = nullptr;  // packed for the taps: {A.xyz, valid ? 1 : 0}
-    float4* dnGuideN = nullptr;  // {N.xyz, 0}
-    float4* dnPlane[2] = {nullptr, nullptr}; // ping-pong {C.xyz, V}
-    size_t dnPixels = 0;         // pixels all of them hold
+    DevBuf<float> dnAlbedo;      // guide planes, 3 floats per pixel: the average of dnGuideK G-buffer launches, or the host's own
+    DevBuf<float> dnNormal;
+    DevBuf<float4> dnGuideA;     // packed for the taps: {A.xyz, valid ? 1 : 0}
+    DevBuf<float4> dnGuideN;     // {N.xyz, 0}
+    DevBuf<float4> dnPlane[2];   // ping-pong {C.xyz, V}
     bool dnGuidesValid = false;  // dnAlbedo / dnNormal hold the library's guides for (dnGuideSeed, dnGuideK) and the current view
     bool dnHostGuides = false;   // dnAlbedo / dnNormal hold planes the host supplied (prt_hip_denoise_set_guides)
     uint32_t dnGuideSeed = 0, dnGuideK = 0;
     int dnLast = -1;             // dnPlane[dnLast].w is V_final of the last denoise (-1: none yet)
     // temporal reprojection (prt_temporal.hip): the position guide and the history / pending records, allocated on first use
-    float4* tpPos = nullptr;     // {X.xyz, t} per camera pixel: the library's (tpPosValid) or the host's own (tpHostPos)
-    size_t tpPosPixels = 0;
+    DevBuf<float4> tpPos;        // {X.xyz, t} per camera pixel: the library's (tpPosValid) or the host's own (tpHostPos)
     bool tpPosValid = false, tpHostPos = false;
-    float4* tpHist[3] = {nullptr, nullptr, nullptr}; // {hC.xyz, hV}, {hX.xyz, hLen}, {hN.xyz, 0}
-    float4* tpPend[3] = {nullptr, nullptr, nullptr};
-    size_t tpPixels = 0;         // pixels each of the six planes holds
+    DevBuf<float4> tpHist[3];    // {hC.xyz, hV}, {hX.xyz, hLen}, {hN.xyz, 0}
+    DevBuf<float4> tpPend[3];
     bool tpHaveHist = false, tpHavePend = false;
     prt_camera_desc tpHistCam{}, tpPendCam{};
     // display transform (prt_display.hip): allocated on first use; neither the camera nor the scene touches any of it
-    prt_display_state* dpState = nullptr; // device: the adaptation state and the figures of the last metering
-    uint32_t* dpHist = nullptr;           // device: the histogram of the metering under way, then the ignored count (64 bits)
-    uint8_t* dpOut = nullptr;             // the context's display buffer
-    size_t dpOutBytes = 0;                // bytes allocated
+    DevBuf<prt_display_state> dpState; // the adaptation state and the figures of the last metering
+    DevBuf<uint32_t> dpHist;           // the histogram of the metering under way, then the ignored count (64 bits)
+    DevBuf<uint8_t> dpOut;             // the context's display buffer
     uint32_t dpOutW = 0, dpOutH = 0, dpOutFormat = 0; // image it last held (prt_hip_download_display)
     // ray queries (prt_query.hip): allocated on first use
-    uint32_t* qInv = nullptr;             // with the scene: slot base of the mesh + mesh-order primId -> triangle slot (0xffffffff: none)
-    unsigned long long* qCounts = nullptr; // device: records the last prt_hip_query_surface refused
-    void* qStage[4] = {nullptr, nullptr, nullptr, nullptr}; // PRT_HIP_QUERY_HOST: rays, hits, surfaces, occlusion bytes on the device
-    size_t qStageBytes[4] = {0, 0, 0, 0};
+    DevBuf<uint32_t> qInv;             // with the scene: slot base of the mesh + mesh-order primId -> triangle slot (0xffffffff: none)
+    DevBuf<unsigned long long> qCounts; // records the last prt_hip_query_surface refused
+    DevBuf<prt_ray> qRays;             // PRT_HIP_QUERY_HOST: the caller's rays and the answers, staged on the device
+    DevBuf<prt_hit> qHits;
+    DevBuf<prt_surface> qSurf;
+    DevBuf<uint8_t> qOccl;
 };
 
 
-// prt_gather.hip: frees the staging buffers and an owned communicator
+// prt_gather.hip: ends an owned communicator
 void prt_gather_release(prt_hip_ctx* c);
 // prt_context.hip: 0, or the error code of a launch since the last prt_hip_get_stats whose image must not be trusted (the context's
 // stream must be idle); `clear` consumes it (prt_hip_get_stats), download / gather only report it
@@ -228,9 +214,8 @@ inline void prt_accum_forget(prt_hip_ctx* c)
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
                     const std::vector<uint32_t>& slotVtx, bool anyBump);
 void prt_refit_forget(prt_hip_ctx* c);
-// prt_denoise.hip: the view or the scene changed (guides of either origin are dropped); frees the planes
+// prt_denoise.hip: the view or the scene changed, or the planes are new (guides of either origin are dropped)
 void prt_denoise_forget(prt_hip_ctx* c);
-void prt_denoise_release(prt_hip_ctx* c);
 // prt_denoise.hip, for the temporal stage (prt_temporal.hip), which replaces the prepare step and then runs the same iterations:
 // the checks of prt_hip_accum_denoise; the guide planes for K jitters; the iterations on dnPlane[0] -> d_rgb (ev, optional: one
 // event recorded after every launch)
@@ -238,15 +223,9 @@ int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d);
 int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K);
 int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev);
 // prt_temporal.hip: the view changes to `next` (pending becomes history when the size stays, else both go; the position guide
-// goes stale); the scene changed or prt_hip_history_reset (both records go); frees the planes
+// goes stale); the scene changed or prt_hip_history_reset (both records go)
 void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next);
 void prt_temporal_forget(prt_hip_ctx* c);
-void prt_temporal_release(prt_hip_ctx* c);
-// prt_display.hip: frees the state, the histogram and the display buffer
-void prt_display_release(prt_hip_ctx* c);
-// prt_query.hip: drops the inverse triangle table with the scene (prt_free_scene); frees the staging buffers (prt_hip_destroy)
-void prt_query_forget(prt_hip_ctx* c);
-void prt_query_release(prt_hip_ctx* c);
 // prt_select.hip: hipcub::DeviceSelect::Flagged of n pixel codes on stream s (stable: the selected codes keep their order); with
 // temp == nullptr it only sets tempBytes
 hipError_t prt_select_flagged(void* temp, size_t& tempBytes, const uint32_t* in, const uint8_t* flags, uint32_t* out, uint32_t* count,

@@ -318,14 +318,8 @@ static int frame_layout(prt_hip_ctx* c, uint32_t blocks, bool env, FrameArgs& A)
     need += (env ? 7 : 5) * al(slots * sizeof(float4));
     need += al(slots * sizeof(float4)) + al(slots * sizeof(uint2)) + al(slots * sizeof(uint32_t));
     need += al((size_t)blocks * Q_COUNT * PRT_POOL_SLOTS * sizeof(uint32_t));
-    if (need > c->wfBytes) {
-        if (c->wfBuffer) (void)hipFree(c->wfBuffer);
-        c->wfBuffer = nullptr;
-        c->wfBytes = 0;
-        HIP_TRY(hipMalloc(&c->wfBuffer, need));
-        c->wfBytes = need;
-    }
-    char* p = (char*)c->wfBuffer;
+    HIP_TRY(c->wfBuffer.grow(need, c->stream));
+    char* p = c->wfBuffer;
     auto take = [&](size_t bytes) { char* r = p; p += al(bytes); return r; };
     A.gRng = (uint32_t*)take(groups * sizeof(uint32_t));
     A.gInfo = (uint32_t*)take(groups * sizeof(uint32_t));
@@ -368,7 +362,7 @@ static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork,
     int rc = prt_launch_resources(c, resident);
     if (rc) return rc;
     A.spill = c->spill;
-    A.spillStride = c->spillThreads;
+    A.spillStride = c->spillThreads();
     if ((rc = frame_layout(c, resident, c->sc.hasEnv != 0, A))) return rc;
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
     if (A.totalChunks == 0) return PRT_HIP_OK;
@@ -451,7 +445,6 @@ static int frame_finish(prt_hip_ctx* c, const FrameLaunch& F)
     c->lastRank = F.A.p.rank;
     c->lastNranks = F.A.p.nranks;
     c->lastTile = F.A.p.tileSize;
-    c->lastTarget = F.A.rgb;
     return prt_stream_leave(c, F.caller);
 }
 
@@ -466,10 +459,7 @@ static int frame_launch(prt_hip_ctx* c, FrameLaunch& F, uint64_t totalWork, Fram
     HIP_TRY(hipEventRecord(ev0, s));
     if ((rc = render_frame_kernel(c, F.A, totalWork, s, kind)) || (rc = prt_launched(kFrameKernelName[kind]))) return rc;
     HIP_TRY(hipEventRecord(ev1, s));
-    if ((rc = frame_finish(c, F))) return rc;
-    c->timed = true;
-    c->frameLaunched = true;
-    return PRT_HIP_OK;
+    return frame_finish(c, F);
 }
 
 // One launch of the frame kernel over a checked rectangle (prt_hip_render, prt_hip_render_accumulate).
@@ -514,10 +504,9 @@ int prt_hip_render_gbuffer(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1
     if ((rc = prt_launch_resources(c, resident))) return rc;
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
-    GbufArgs A{c->sc, c->cam, x0, y0, rw, rh, type, seed, exposure, d_rgb, c->work, c->spill, c->spillThreads, c->counters};
+    GbufArgs A{c->sc, c->cam, x0, y0, rw, rh, type, seed, exposure, d_rgb, c->work, c->spill, c->spillThreads(), c->counters};
     hipLaunchKernelGGL(gbuffer_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
     if ((rc = prt_launched("gbuffer_kernel")) || (rc = prt_stream_leave(c, caller))) return rc;
-    c->timed = false;
     return PRT_HIP_OK;
 }
 
@@ -530,18 +519,8 @@ static int accum_ready(prt_hip_ctx* c)
 {
     const size_t n = (size_t)c->cam.width * c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->accPixels != n) {
-        HIP_TRY(hipStreamSynchronize(c->stream)); // the old records may still be in use
-        if (c->accRng) (void)hipFree(c->accRng);
-        if (c->accSum) (void)hipFree(c->accSum);
-        c->accRng = nullptr;
-        c->accSum = nullptr;
-        c->accPixels = 0;
-        HIP_TRY(hipMalloc(&c->accRng, n * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->accSum, n * sizeof(float4)));
-        c->accPixels = n;
-        c->accClear = true;
-    }
+    HIP_TRY(c->accRng.fit(n, c->stream, &c->accClear));
+    HIP_TRY(c->accSum.fit(n, c->stream, &c->accClear));
     if (c->accClear) {
         HIP_TRY(hipMemsetAsync(c->accRng, 0, n * sizeof(uint32_t), c->stream));
         HIP_TRY(hipMemsetAsync(c->accSum, 0, n * sizeof(float4), c->stream));
@@ -623,7 +602,7 @@ int prt_hip_accum_export(prt_hip_ctx* c, prt_accum_info* info, uint32_t* rng, fl
     if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
     int rc = accum_ready(c);
     if (rc) return rc;
-    const size_t n = c->accPixels;
+    const size_t n = c->accSum.size();
     std::vector<float4> rec(n);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(rng, c->accRng, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -676,16 +655,8 @@ static int moments_ready(prt_hip_ctx* c)
 {
     int rc = accum_ready(c);
     if (rc) return rc;
-    const size_t n = c->accPixels;
-    if (c->momPixels != n) {
-        HIP_TRY(hipStreamSynchronize(c->stream)); // the old records may still be in use
-        if (c->accMom) (void)hipFree(c->accMom);
-        c->accMom = nullptr;
-        c->momPixels = 0;
-        HIP_TRY(hipMalloc(&c->accMom, n * sizeof(float4)));
-        c->momPixels = n;
-        c->momClear = true;
-    }
+    const size_t n = c->accSum.size();
+    HIP_TRY(c->accMom.fit(n, c->stream, &c->momClear));
     if (c->momClear) {
         HIP_TRY(hipMemsetAsync(c->accMom, 0, n * sizeof(float4), c->stream));
         c->momClear = false;
@@ -697,31 +668,15 @@ static int moments_ready(prt_hip_ctx* c)
 // the active count with its pinned host copy.
 static int adapt_buffers(prt_hip_ctx* c, uint64_t items)
 {
-    if (!c->adCount) HIP_TRY(hipMalloc(&c->adCount, sizeof(uint32_t)));
+    HIP_TRY(c->adCount.fit(1, c->stream));
     if (!c->adCountHost) HIP_TRY(hipHostMalloc((void**)&c->adCountHost, sizeof(uint32_t), hipHostMallocDefault));
     const size_t padded = (size_t)((items + PRT_CHUNK - 1) / PRT_CHUNK * PRT_CHUNK);
-    if (padded > c->adItems) {
-        HIP_TRY(hipStreamSynchronize(c->stream)); // the old buffers may still be in use
-        for (void* q : {(void*)c->adCode, (void*)c->adList, (void*)c->adFlag})
-            if (q) (void)hipFree(q);
-        c->adCode = c->adList = nullptr;
-        c->adFlag = nullptr;
-        c->adItems = 0;
-        HIP_TRY(hipMalloc(&c->adCode, padded * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->adList, padded * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&c->adFlag, padded * sizeof(uint8_t)));
-        c->adItems = padded;
-    }
+    HIP_TRY(c->adCode.grow(padded, c->stream));
+    HIP_TRY(c->adList.grow(padded, c->stream));
+    HIP_TRY(c->adFlag.grow(padded, c->stream));
     size_t bytes = 0;
     HIP_TRY(prt_select_flagged(nullptr, bytes, c->adCode, c->adFlag, c->adList, c->adCount, items, c->stream));
-    if (bytes > c->adTempBytes) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->adTemp) (void)hipFree(c->adTemp);
-        c->adTemp = nullptr;
-        c->adTempBytes = 0;
-        HIP_TRY(hipMalloc(&c->adTemp, bytes));
-        c->adTempBytes = bytes;
-    }
+    HIP_TRY(c->adTemp.grow(bytes, c->stream));
     return PRT_HIP_OK;
 }
 
@@ -757,7 +712,7 @@ int prt_hip_render_adaptive(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x
         hipLaunchKernelGGL(adapt_select_kernel, dim3(blocks), dim3(256), 0, s, F.A, (const float4*)c->accSum, (const float4*)c->accMom, *a,
                            c->adCode, c->adFlag);
         if ((rc = prt_launched("adapt_select_kernel"))) return rc;
-        size_t bytes = c->adTempBytes;
+        size_t bytes = c->adTemp.size();
         HIP_TRY(prt_select_flagged(c->adTemp, bytes, c->adCode, c->adFlag, c->adList, c->adCount, F.totalWork, s));
         HIP_TRY(hipMemcpyAsync(c->adCountHost, c->adCount, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s)); // the pass's one synchronisation: the launch is sized by the active count
@@ -788,14 +743,7 @@ int prt_hip_accum_error(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, u
     const uint32_t rw = x1 - x0 + 1, rh = y1 - y0 + 1;
     const size_t n = (size_t)rw * rh;
     if (n > 0xffffffffull) return fail(PRT_HIP_EINVAL, "rectangle too large");
-    if (n > c->adErrItems) { // the context keeps the buffer: a viewer may ask once per pass
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->adErr) (void)hipFree(c->adErr);
-        c->adErr = nullptr;
-        c->adErrItems = 0;
-        HIP_TRY(hipMalloc(&c->adErr, n * sizeof(float)));
-        c->adErrItems = n;
-    }
+    HIP_TRY(c->adErr.grow(n, c->stream)); // the context keeps the buffer: a viewer may ask once per pass
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->computeUnits * 8);
     hipLaunchKernelGGL(accum_error_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float4*)c->accSum, (const float4*)c->accMom, W, x0, y0,
                        rw, rh, exposure, floor, c->adErr);
@@ -814,7 +762,7 @@ int prt_hip_accum_export_moments(prt_hip_ctx* c, float* mom)
     int rc = moments_ready(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(mom, c->accMom, c->momPixels * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mom, c->accMom, c->accMom.size() * sizeof(float4), hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -838,17 +786,7 @@ int prt_hip_accum_import_moments(prt_hip_ctx* c, const float* mom)
 }
 
 #ifdef PRT_TEST_ENTRY_POINTS
-} // extern "C"
-namespace {
-// device scratch of one test call: freed on every return path
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T* as() const { return (T*)p; }
-};
-} // namespace
-extern "C" {
+// (the device scratch of a test call is a DevBuf of its own: freed on every return path)
 
 int prt_hip_test_occlusion_skipped(prt_hip_ctx* c, uint64_t* skipped)
 {
@@ -872,16 +810,17 @@ int prt_hip_trace_rays(prt_hip_ctx* c, int mode, uint32_t n, const float* org, c
     uint32_t blocks = (n + PRT_BLOCK - 1) / PRT_BLOCK;
     int rc = prt_launch_resources(c, blocks);
     if (rc) return rc;
-    DevBuf dorg, ddir, dh;
-    HIP_TRY(dorg.alloc((size_t)n * 12));
-    HIP_TRY(ddir.alloc((size_t)n * 12));
-    HIP_TRY(dh.alloc((size_t)n * sizeof(prt_hit)));
-    HIP_TRY(hipMemcpy(dorg.p, org, (size_t)n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ddir.p, dir, (size_t)n * 12, hipMemcpyHostToDevice));
+    DevBuf<float> dorg, ddir;
+    DevBuf<prt_hit> dh;
+    HIP_TRY(dorg.fit((size_t)n * 3, c->stream));
+    HIP_TRY(ddir.fit((size_t)n * 3, c->stream));
+    HIP_TRY(dh.fit(n, c->stream));
+    HIP_TRY(hipMemcpy(dorg, org, (size_t)n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ddir, dir, (size_t)n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), c->stream));
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), c->stream));
-    RaysArgs A{c->sc, n, dorg.as<float>(), ddir.as<float>(), maxT, dh.as<prt_hit>(), c->work, c->spill, c->spillThreads, c->counters};
-    blocks = std::min<uint32_t>(blocks, (uint32_t)c->spillThreads / PRT_BLOCK);
+    RaysArgs A{c->sc, n, dorg, ddir, maxT, dh, c->work, c->spill, c->spillThreads(), c->counters};
+    blocks = std::min<uint32_t>(blocks, c->spillThreads() / PRT_BLOCK);
     // timed like a render (prt_hip_get_stats reports it as kernelMs): tools/ray_order_experiment.py compares orders of one batch
     hipEvent_t ev0, ev1;
     if ((rc = prt_timing_pair(c, &ev0, &ev1))) return rc;
@@ -893,8 +832,7 @@ int prt_hip_trace_rays(prt_hip_ctx* c, int mode, uint32_t n, const float* org, c
     if ((rc = prt_launched("rays_kernel"))) return rc;
     HIP_TRY(hipEventRecord(ev1, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(hits, dh.p, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost));
-    c->timed = false;
+    HIP_TRY(hipMemcpy(hits, dh, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -902,13 +840,13 @@ int prt_hip_test_leaf(prt_hip_ctx* c, uint32_t n, const float* records, float* o
 {
     if (!c || !records || !out || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf din, dout;
-    HIP_TRY(din.alloc((size_t)n * 22 * 4));
-    HIP_TRY(dout.alloc((size_t)n * 24 * 4));
-    HIP_TRY(hipMemcpy(din.p, records, (size_t)n * 22 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(leaf_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, din.as<float>(), dout.as<float>());
+    DevBuf<float> din, dout;
+    HIP_TRY(din.fit((size_t)n * 22, c->stream));
+    HIP_TRY(dout.fit((size_t)n * 24, c->stream));
+    HIP_TRY(hipMemcpy(din, records, (size_t)n * 22 * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(leaf_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, din, dout);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 24 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 24 * 4, hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -916,15 +854,15 @@ int prt_hip_test_sincos(prt_hip_ctx* c, uint32_t n, const float* theta, float* s
 {
     if (!c || !theta || !s || !cs || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf dt, ds, dc;
-    HIP_TRY(dt.alloc((size_t)n * 4));
-    HIP_TRY(ds.alloc((size_t)n * 4));
-    HIP_TRY(dc.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(dt.p, theta, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(sincos_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dt.as<float>(), ds.as<float>(), dc.as<float>());
+    DevBuf<float> dt, ds, dc;
+    HIP_TRY(dt.fit(n, c->stream));
+    HIP_TRY(ds.fit(n, c->stream));
+    HIP_TRY(dc.fit(n, c->stream));
+    HIP_TRY(hipMemcpy(dt, theta, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sincos_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dt, ds, dc);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(s, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cs, dc.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s, ds, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cs, dc, (size_t)n * 4, hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -932,13 +870,13 @@ int prt_hip_test_powf(prt_hip_ctx* c, uint32_t n, const float* x, float* y)
 {
     if (!c || !x || !y || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf dx, dy;
-    HIP_TRY(dx.alloc((size_t)n * 4));
-    HIP_TRY(dy.alloc((size_t)n * 4));
-    HIP_TRY(hipMemcpy(dx.p, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(powf_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx.as<float>(), dy.as<float>());
+    DevBuf<float> dx, dy;
+    HIP_TRY(dx.fit(n, c->stream));
+    HIP_TRY(dy.fit(n, c->stream));
+    HIP_TRY(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(powf_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, dx, dy);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(y, dy.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(y, dy, (size_t)n * 4, hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -947,11 +885,11 @@ int prt_hip_test_camera(prt_hip_ctx* c, uint32_t x, uint32_t y, uint32_t state, 
     if (!c || !out92) return fail(PRT_HIP_EINVAL, "bad argument");
     if (!c->haveCamera) return fail(PRT_HIP_ESTATE, "set a camera first");
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf d;
-    HIP_TRY(d.alloc(92 * 4));
-    hipLaunchKernelGGL(camera_kernel, dim3(1), dim3(64), 0, c->stream, c->cam, x, y, state, d.as<float>());
+    DevBuf<float> d;
+    HIP_TRY(d.fit(92, c->stream));
+    hipLaunchKernelGGL(camera_kernel, dim3(1), dim3(64), 0, c->stream, c->cam, x, y, state, d);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out92, d.p, 92 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out92, d, 92 * 4, hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -983,19 +921,19 @@ int prt_hip_test_taps(prt_hip_ctx* c, uint32_t n, const uint32_t* records, int c
         }
     }
     HIP_TRY(hipSetDevice(c->device));
-    DevBuf din, dout, dcls;
-    HIP_TRY(din.alloc((size_t)n * 16));
-    HIP_TRY(dout.alloc((size_t)n * 48));
-    HIP_TRY(dcls.alloc(c->ed.classWordOf.size() * 4));
-    HIP_TRY(hipMemcpy(din.p, records, (size_t)n * 16, hipMemcpyHostToDevice));
-    if (!c->ed.classWordOf.empty()) HIP_TRY(hipMemcpy(dcls.p, c->ed.classWordOf.data(), c->ed.classWordOf.size() * 4, hipMemcpyHostToDevice));
+    DevBuf<uint32_t> din, dout, dcls;
+    HIP_TRY(din.fit((size_t)n * 4, c->stream));
+    HIP_TRY(dout.fit((size_t)n * 12, c->stream));
+    HIP_TRY(dcls.fit(c->ed.classWordOf.size(), c->stream));
+    HIP_TRY(hipMemcpy(din, records, (size_t)n * 16, hipMemcpyHostToDevice));
+    if (!c->ed.classWordOf.empty()) HIP_TRY(hipMemcpy(dcls, c->ed.classWordOf.data(), c->ed.classWordOf.size() * 4, hipMemcpyHostToDevice));
     blocks = row_blocks(n, blocks);
-    if (counting) hipLaunchKernelGGL(taps_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls.as<uint32_t>(), n, din.as<uint32_t>(), dout.as<uint32_t>());
-    else hipLaunchKernelGGL(taps_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls.as<uint32_t>(), n, din.as<uint32_t>(), dout.as<uint32_t>());
+    if (counting) hipLaunchKernelGGL(taps_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls, n, din, dout);
+    else hipLaunchKernelGGL(taps_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, dcls, n, din, dout);
     int rc = prt_launched("taps_kernel");
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -1027,18 +965,18 @@ int prt_hip_test_surface(prt_hip_ctx* c, uint32_t n, const uint32_t* records, in
             return fail(PRT_HIP_EINVAL, "surface: bad mesh or primitive index");
         rec[5 * (size_t)r + 1] = slotOf[mesh][prim];
     }
-    DevBuf din, dout;
-    HIP_TRY(din.alloc((size_t)n * 20));
-    HIP_TRY(dout.alloc((size_t)n * 80));
-    HIP_TRY(hipMemcpy(din.p, rec.data(), (size_t)n * 20, hipMemcpyHostToDevice));
+    DevBuf<uint32_t> din, dout;
+    HIP_TRY(din.fit((size_t)n * 5, c->stream));
+    HIP_TRY(dout.fit((size_t)n * 20, c->stream));
+    HIP_TRY(hipMemcpy(din, rec.data(), (size_t)n * 20, hipMemcpyHostToDevice));
     blocks = row_blocks(n, blocks);
     const uint32_t anyBump = c->ed.anyBump ? 1u : 0u;
-    if (counting) hipLaunchKernelGGL(surface_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din.as<uint32_t>(), dout.as<uint32_t>());
-    else hipLaunchKernelGGL(surface_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din.as<uint32_t>(), dout.as<uint32_t>());
+    if (counting) hipLaunchKernelGGL(surface_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din, dout);
+    else hipLaunchKernelGGL(surface_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din, dout);
     int rc = prt_launched("surface_kernel");
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 80, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 80, hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < n; r++) // the material as the reference names it: its index within the mesh
         out[20 * (size_t)r + 5] -= c->ed.meshes[records[5 * (size_t)r]].matBase;
     return PRT_HIP_OK;

@@ -226,25 +226,6 @@ int null_argument(const char* what)
     return fail(PRT_HIP_EINVAL, std::string(what) + ": NULL argument");
 }
 
-// staging buffer `k` of the HOST flavour, at least `bytes` large
-int stage(prt_hip_ctx* c, int k, size_t bytes)
-{
-    if (c->qStageBytes[k] >= bytes) return PRT_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream)); // an earlier query may still use the old one
-    if (c->qStage[k]) (void)hipFree(c->qStage[k]);
-    c->qStage[k] = nullptr;
-    c->qStageBytes[k] = 0;
-    HIP_TRY(hipMalloc(&c->qStage[k], bytes));
-    c->qStageBytes[k] = bytes;
-    return PRT_HIP_OK;
-}
-
-int counts_ready(prt_hip_ctx* c)
-{
-    if (!c->qCounts) HIP_TRY(hipMalloc(&c->qCounts, sizeof(unsigned long long)));
-    return PRT_HIP_OK;
-}
-
 // One launch of a traversal kernel over the batch on the context's stream, timed as a render.
 int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surf, uint8_t* occ, bool any)
 {
@@ -256,7 +237,7 @@ int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits,
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
-    QueryArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, occ, c->work, c->spill, c->spillThreads, c->counters};
+    QueryArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, occ, c->work, c->spill, c->spillThreads(), c->counters};
     hipEvent_t ev0, ev1;
     if ((rc = prt_timing_pair(c, &ev0, &ev1))) return rc;
     HIP_TRY(hipEventRecord(ev0, s));
@@ -266,7 +247,6 @@ int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits,
     else hipLaunchKernelGGL(query_nearest_kernel<false>, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
     if ((rc = prt_launched(name))) return rc;
     HIP_TRY(hipEventRecord(ev1, s));
-    c->timed = false;
     return PRT_HIP_OK;
 }
 
@@ -289,7 +269,7 @@ int inverse_ready(prt_hip_ctx* c)
         a.slotBase[m] = rm.slotBase;
         a.slotCount[m] = rm.slotCount;
     }
-    HIP_TRY(hipMalloc(&c->qInv, R.slots * sizeof(uint32_t)));
+    HIP_TRY(c->qInv.fit(R.slots, c->stream));
     a.inv = c->qInv;
     HIP_TRY(hipMemsetAsync(c->qInv, 0xff, R.slots * sizeof(uint32_t), c->stream));
     const uint32_t blocks = std::min<uint32_t>((a.slots + 255u) / 256u, 65535u);
@@ -299,8 +279,9 @@ int inverse_ready(prt_hip_ctx* c)
 
 int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surf)
 {
-    int rc;
-    if ((rc = inverse_ready(c)) || (rc = counts_ready(c))) return rc;
+    int rc = inverse_ready(c);
+    if (rc) return rc;
+    HIP_TRY(c->qCounts.fit(1, c->stream));
     HIP_TRY(hipMemsetAsync(c->qCounts, 0, sizeof(unsigned long long), c->stream));
     SurfaceArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, c->qInv, c->qCounts};
     const uint32_t blocks = std::min<uint32_t>((n + 255u) / 256u, (uint32_t)c->computeUnits * 8u);
@@ -309,24 +290,6 @@ int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hi
 }
 
 } // namespace
-
-void prt_query_forget(prt_hip_ctx* c)
-{
-    if (c->qInv) (void)hipFree(c->qInv);
-    c->qInv = nullptr;
-}
-
-void prt_query_release(prt_hip_ctx* c)
-{
-    prt_query_forget(c);
-    if (c->qCounts) (void)hipFree(c->qCounts);
-    c->qCounts = nullptr;
-    for (int k = 0; k < 4; k++) {
-        if (c->qStage[k]) (void)hipFree(c->qStage[k]);
-        c->qStage[k] = nullptr;
-        c->qStageBytes[k] = 0;
-    }
-}
 
 extern "C" {
 
@@ -337,15 +300,14 @@ int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_h
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (flags & PRT_HIP_QUERY_HOST) {
-        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 1, (size_t)n * sizeof(prt_hit))) ||
-            (surfaces && (rc = stage(c, 2, (size_t)n * sizeof(prt_surface)))))
-            return rc;
         hipStream_t s = c->stream;
-        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        if ((rc = launch_trace(c, n, (const prt_ray*)c->qStage[0], (prt_hit*)c->qStage[1], surfaces ? (prt_surface*)c->qStage[2] : nullptr, nullptr, false)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(hits, c->qStage[1], (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
-        if (surfaces) HIP_TRY(hipMemcpyAsync(surfaces, c->qStage[2], (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c->qRays.grow(n, s));
+        HIP_TRY(c->qHits.grow(n, s));
+        if (surfaces) HIP_TRY(c->qSurf.grow(n, s));
+        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        if ((rc = launch_trace(c, n, c->qRays, c->qHits, surfaces ? (prt_surface*)c->qSurf : nullptr, nullptr, false))) return rc;
+        HIP_TRY(hipMemcpyAsync(hits, c->qHits, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
+        if (surfaces) HIP_TRY(hipMemcpyAsync(surfaces, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return PRT_HIP_OK;
     }
@@ -363,11 +325,12 @@ int prt_hip_query_any(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, uint8_t* 
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (flags & PRT_HIP_QUERY_HOST) {
-        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 3, (size_t)n))) return rc;
         hipStream_t s = c->stream;
-        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        if ((rc = launch_trace(c, n, (const prt_ray*)c->qStage[0], nullptr, nullptr, (uint8_t*)c->qStage[3], true))) return rc;
-        HIP_TRY(hipMemcpyAsync(occluded, c->qStage[3], (size_t)n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c->qRays.grow(n, s));
+        HIP_TRY(c->qOccl.grow(n, s));
+        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        if ((rc = launch_trace(c, n, c->qRays, nullptr, nullptr, c->qOccl, true))) return rc;
+        HIP_TRY(hipMemcpyAsync(occluded, c->qOccl, (size_t)n, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return PRT_HIP_OK;
     }
@@ -384,14 +347,14 @@ int prt_hip_query_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (flags & PRT_HIP_QUERY_HOST) {
-        if ((rc = stage(c, 0, (size_t)n * sizeof(prt_ray))) || (rc = stage(c, 1, (size_t)n * sizeof(prt_hit))) ||
-            (rc = stage(c, 2, (size_t)n * sizeof(prt_surface))))
-            return rc;
         hipStream_t s = c->stream;
-        HIP_TRY(hipMemcpyAsync(c->qStage[0], rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->qStage[1], hits, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
-        if ((rc = launch_surface(c, n, (const prt_ray*)c->qStage[0], (const prt_hit*)c->qStage[1], (prt_surface*)c->qStage[2]))) return rc;
-        HIP_TRY(hipMemcpyAsync(surfaces, c->qStage[2], (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c->qRays.grow(n, s));
+        HIP_TRY(c->qHits.grow(n, s));
+        HIP_TRY(c->qSurf.grow(n, s));
+        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c->qHits, hits, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
+        if ((rc = launch_surface(c, n, c->qRays, c->qHits, c->qSurf))) return rc;
+        HIP_TRY(hipMemcpyAsync(surfaces, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return PRT_HIP_OK;
     }

@@ -237,30 +237,19 @@ int check_temporal(const prt_temporal_params* t)
     return PRT_HIP_OK;
 }
 
-void free_records(prt_hip_ctx* c)
-{
-    for (int k = 0; k < 3; k++) {
-        if (c->tpHist[k]) (void)hipFree(c->tpHist[k]);
-        if (c->tpPend[k]) (void)hipFree(c->tpPend[k]);
-        c->tpHist[k] = c->tpPend[k] = nullptr;
-    }
-    c->tpPixels = 0;
-    c->tpHaveHist = c->tpHavePend = false;
-}
-
 // The six record planes at the camera's size.  Records of another size were dropped when the camera changed, so nothing is lost.
 int records_ready(prt_hip_ctx* c)
 {
     const size_t n = (size_t)c->cam.width * c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->tpPixels == n) return PRT_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_records(c);
+    bool fresh = false;
+    hipError_t e = hipSuccess;
     for (int k = 0; k < 3; k++) {
-        HIP_TRY(hipMalloc(&c->tpHist[k], n * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c->tpPend[k], n * sizeof(float4)));
+        if (e == hipSuccess) e = c->tpHist[k].fit(n, c->stream, &fresh);
+        if (e == hipSuccess) e = c->tpPend[k].fit(n, c->stream, &fresh);
     }
-    c->tpPixels = n;
+    if (fresh) c->tpHaveHist = c->tpHavePend = false;
+    HIP_TRY(e);
     return PRT_HIP_OK;
 }
 
@@ -268,14 +257,10 @@ int position_plane(prt_hip_ctx* c)
 {
     const size_t n = (size_t)c->cam.width * c->cam.height;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->tpPosPixels == n) return PRT_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->tpPos) (void)hipFree(c->tpPos);
-    c->tpPos = nullptr;
-    c->tpPosPixels = 0;
-    c->tpPosValid = c->tpHostPos = false;
-    HIP_TRY(hipMalloc(&c->tpPos, n * sizeof(float4)));
-    c->tpPosPixels = n;
+    bool fresh = false;
+    hipError_t e = c->tpPos.fit(n, c->stream, &fresh);
+    if (fresh) c->tpPosValid = c->tpHostPos = false;
+    HIP_TRY(e);
     return PRT_HIP_OK;
 }
 
@@ -296,10 +281,9 @@ int position_ready(prt_hip_ctx* c, bool force = false)
     if ((rc = prt_launch_resources(c, resident))) return rc;
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
     HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
-    PosArgs A{c->sc, c->cam, c->tpPos, c->work, c->spill, c->spillThreads, c->counters};
+    PosArgs A{c->sc, c->cam, c->tpPos, c->work, c->spill, c->spillThreads(), c->counters};
     hipLaunchKernelGGL(position_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
     if ((rc = prt_launched("position_kernel"))) return rc;
-    c->timed = false;
     c->tpPosValid = true;
     return PRT_HIP_OK;
 }
@@ -311,7 +295,7 @@ int run_merge(prt_hip_ctx* c, const prt_denoise_params* d, const prt_temporal_pa
     const size_t n = (size_t)W * H;
     MergeArgs A{};
     A.acc = (const float4*)c->accSum;
-    A.mom = (c->accMom && c->momPixels == n && !c->momClear) ? c->accMom : nullptr;
+    A.mom = (c->accMom.size() == n && !c->momClear) ? c->accMom : nullptr;
     A.albedo = c->dnAlbedo;
     A.normal = c->dnNormal;
     A.pos = c->tpPos;
@@ -375,7 +359,7 @@ void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next)
         return;
     }
     if (c->tpHavePend) { // work already queued on the context's stream keeps its pointers; later work sees the swapped ones
-        for (int k = 0; k < 3; k++) std::swap(c->tpHist[k], c->tpPend[k]);
+        for (int k = 0; k < 3; k++) c->tpHist[k].swap(c->tpPend[k]);
         c->tpHistCam = c->tpPendCam;
         c->tpHaveHist = true;
         c->tpHavePend = false;
@@ -389,15 +373,6 @@ void prt_temporal_forget(prt_hip_ctx* c)
     c->tpHaveHist = c->tpHavePend = false;
 }
 
-void prt_temporal_release(prt_hip_ctx* c)
-{
-    free_records(c);
-    if (c->tpPos) (void)hipFree(c->tpPos);
-    c->tpPos = nullptr;
-    c->tpPosPixels = 0;
-    c->tpPosValid = c->tpHostPos = false;
-}
-
 extern "C" {
 
 int prt_hip_denoise_get_position(prt_hip_ctx* c, float* xyzt)
@@ -406,7 +381,7 @@ int prt_hip_denoise_get_position(prt_hip_ctx* c, float* xyzt)
     int rc = position_ready(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(xyzt, c->tpPos, c->tpPosPixels * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(xyzt, c->tpPos, c->tpPos.size() * sizeof(float4), hipMemcpyDeviceToHost));
     return PRT_HIP_OK;
 }
 
@@ -422,7 +397,7 @@ int prt_hip_denoise_set_position(prt_hip_ctx* c, const float* xyzt)
     int rc = position_plane(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream)); // a denoise may still be reading the old plane
-    HIP_TRY(hipMemcpy(c->tpPos, xyzt, c->tpPosPixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->tpPos, xyzt, c->tpPos.size() * sizeof(float4), hipMemcpyHostToDevice));
     c->tpHostPos = true;
     c->tpPosValid = false;
     return PRT_HIP_OK;
@@ -456,8 +431,8 @@ int prt_hip_history_export(prt_hip_ctx* c, uint32_t which, prt_camera_desc* came
         return fail(PRT_HIP_ESTATE, which == 0 ? "history_export: there is no history" : "history_export: there is no pending record");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    float4* const* pl = which == 0 ? c->tpHist : c->tpPend;
-    const size_t bytes = c->tpPixels * sizeof(float4);
+    const DevBuf<float4>* pl = which == 0 ? c->tpHist : c->tpPend;
+    const size_t bytes = c->tpHist[0].size() * sizeof(float4);
     HIP_TRY(hipMemcpy(colorVar, pl[0], bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(posLen, pl[1], bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(normal, pl[2], bytes, hipMemcpyDeviceToHost));
@@ -474,7 +449,7 @@ int prt_hip_history_import(prt_hip_ctx* c, const prt_camera_desc* camera, const 
     int rc = records_ready(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream)); // a denoise may still be reading the old history
-    const size_t bytes = c->tpPixels * sizeof(float4);
+    const size_t bytes = c->tpHist[0].size() * sizeof(float4);
     HIP_TRY(hipMemcpy(c->tpHist[0], colorVar, bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->tpHist[1], posLen, bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->tpHist[2], normal, bytes, hipMemcpyHostToDevice));
@@ -521,7 +496,7 @@ int prt_hip_test_temporal_profile(prt_hip_ctx* c, const prt_denoise_params* d, c
     }
     // the G-buffer launch writes the iterations' spare plane, never the image; both figures include the two small memsets of a launch
     HIP_TRY(hipEventRecord(ev[2], s));
-    if ((rc = prt_hip_render_gbuffer(c, 0, 0, c->cam.width - 1, c->cam.height - 1, 0, c->accSeed, 1.0f, (float*)c->dnPlane[1], nullptr))) return rc;
+    if ((rc = prt_hip_render_gbuffer(c, 0, 0, c->cam.width - 1, c->cam.height - 1, 0, c->accSeed, 1.0f, (float*)(float4*)c->dnPlane[1], nullptr))) return rc;
     HIP_TRY(hipEventRecord(ev[3], s));
     HIP_TRY(hipEventSynchronize(ev[3]));
     HIP_TRY(hipEventElapsedTime(&ms[3], ev[2], ev[3]));

@@ -49,7 +49,7 @@ void prt_free_scene(prt_hip_ctx* c)
     for (void* p : c->sceneAllocs) (void)hipFree(p);
     c->sceneAllocs.clear();
     prt_refit_forget(c);
-    prt_query_forget(c);
+    c->qInv.release(); // the inverse triangle table is the scene's (prt_query.hip)
     c->ed = PrtEdit{};
     c->haveScene = false;
 }

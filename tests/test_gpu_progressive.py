@@ -249,3 +249,62 @@ def test_passes_on_a_callers_stream(tracer):
     for k, what in enumerate(("accumulate", "adaptive", "resolve", "gbuffer")):
         assert not (bits(got[k]) == 0xffffffff).any(), f"{what}: the caller's buffer still holds its fill"
         assert_bits_equal(got[k], want[k], f"{what} on a caller's stream")
+
+
+def _everything_at_this_size(t):
+    """Every call that (re)allocates a context buffer, at the tracer's current camera; returns what the calls returned."""
+    W, H = t._camera.width, t._camera.height
+    out = {}
+    out["pass 1"] = t.accumulate(8)
+    out["pass 2"] = t.accumulate(8)
+    out["rays of pass 2"] = t.last_stats["raysTraced"]
+    out["resolve"] = t.accum_resolve()
+    out["adaptive"], out["active"] = t.adaptive_pass(8, 0.02, 16, 64)
+    out["error 5x3"] = t.accum_error(x0=2, y0=1, x1=6, y1=3)
+    out["error"] = t.accum_error()
+    out["denoise"] = t.denoise()
+    out["temporal"] = t.denoise_temporal()
+    t.display_reset()  # the adaptation state outlives a camera change on purpose
+    out["display"] = t.display(prt_amd.DisplayParams.make(meter=True))
+    out["gbuffer"] = t.gbuffer(0)
+    for n in (64, 1000, 8):  # the staging buffers grow, then are kept
+        k = np.arange(n)
+        rays = prt_amd.pixel_centre_rays(t._camera.desc, k % W, (k // W) % H)
+        out[f"hits {n}"], out[f"surfaces {n}"] = t.query_nearest(rays["org"], rays["dir"], rays["tMax"], surface=True)
+    out["stats"] = {k: v for k, v in t.stats().items() if not k.startswith("kernel")}  # (the times are not results)
+    return out
+
+
+def test_one_context_walked_through_camera_sizes_equals_fresh_contexts():
+    """The context's buffers follow the camera: at each of 48x32, 32x48 (as many pixels, another shape), 64x40 (more, and no multiple
+    of the 16-pixel tile) and 48x32 again, one tracer returns bit for bit what a fresh tracer returns that only ever saw that size.
+    Before anything is rendered at a new size, the framebuffer of the old size is refused, not read."""
+    scene, _, _ = prt_amd.setup_cornell_box(48, 32)
+    camera_of = lambda w, h: prt_amd.Camera().create((0, 0.965, 2.6), (0, 0, -1.0), w, h)  # noqa: E731
+    walked = prt_amd.PathTracer()
+    try:
+        walked.upload_scene(scene)
+        for W, H in ((48, 32), (32, 48), (64, 40), (48, 32)):
+            walked.set_camera(camera_of(W, H))
+            if (W, H) == (64, 40):
+                with pytest.raises(prt_amd.PrtError) as e:
+                    walked._download_rect(0, 0, W - 1, H - 1, stats=False)
+                assert "(-5)" in str(e.value) and "nothing rendered into the context framebuffer" in str(e.value)  # PRT_HIP_ESTATE
+            got = _everything_at_this_size(walked)
+            fresh = prt_amd.PathTracer()
+            try:
+                fresh.upload_scene(scene)
+                fresh.set_camera(camera_of(W, H))
+                want = _everything_at_this_size(fresh)
+            finally:
+                fresh.close()
+            assert got.keys() == want.keys()
+            assert want["rays of pass 2"] > 0 and "raysTraced" in want["stats"]
+            for k in want:
+                if isinstance(want[k], np.ndarray):
+                    assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (W, H, k)
+                    assert got[k].tobytes() == want[k].tobytes(), f"{W}x{H}: {k} differs from a fresh context's"
+                else:
+                    assert got[k] == want[k], (W, H, k, got[k], want[k])
+    finally:
+        walked.close()
