@@ -38,7 +38,11 @@ extern "C" {
 typedef struct prt_hip_ctx prt_hip_ctx;
 
 /* Material fields the path reads (material.h:30-44).  reflectionType: 0 diffuse, 1 specular,
- * 2 refraction (material.h:24-28).  diffuseMap/bumpMap index prt_scene_desc.textures, -1 = none. */
+ * 2 refraction (material.h:24-28).  diffuseMap/bumpMap index prt_scene_desc.textures, -1 = none.
+ * Any float is accepted in diffuse and emissive (and in a directional light); the image is what the reference computes from them.
+ * Refraction is undefined in the reference (path_tracer.cpp never writes the path's next direction and normalises stack
+ * contents); here it is defined: a refraction surface scatters along a ZERO direction in every bounce, i.e. it sends one
+ * counted ray that misses, and the path's emission and its pending light addend still count. */
 typedef struct {
     float diffuse[3];
     float emissive[3];

@@ -1495,10 +1495,13 @@ static v3 compute_radiance(const orc_scene* scene, uint32_t* rng, const orc_hit 
     uint32_t depth = 0;
     v3 lightDir[LANES], lightIntensity[LANES], nextRayDir[LANES];
     memset(lightDir, 0, sizeof(lightDir)); memset(lightIntensity, 0, sizeof(lightIntensity));
-    memset(nextRayDir, 0, sizeof(nextRayDir));
 
     while (depth < maxDepth) {
         int directLighting = 0;
+        /* A refraction material (reflectionType 2) writes no nextRayDir: the reference normalises stack garbage there.  Defined as
+         * in the kernels (prt_frame.h shade_round): the direction is zero in EVERY bounce, so the scatter ray is normalize(0) = NaN,
+         * a counted ray that misses.  Diffuse and specular paths overwrite their entry below. */
+        memset(nextRayDir, 0, sizeof(nextRayDir));
         for (uint32_t path = 0; path < alivePaths; path++) {
             const orc_material* material = materials[path];
             v3 normal = normals[path];

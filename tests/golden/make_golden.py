@@ -21,6 +21,9 @@ Outputs (all small, data only -- no reference source text):
                        reference's Scene::intersect / Scene::occluded answers, single and packet
   hostile_taps.npz     the maps, meshes and records of tests/prt_hostile_taps.py and the answers of the reference's own texture.cpp /
                        material.cpp / mesh.cpp to them (oracle/_ref/ref_shade)
+  hostile_shade.npz    the reference-defined scenes of tests/prt_hostile_shade.py (hostile materials and lights on a 32x32 stage and in a
+                       24x24 closed box): their arrays and light, and PathTracer::TraceBlock's image at 8 spp with its two ray counts
+                       (oracle/_ref/ref_path_stats)
 
 radiance_c1_crop, gbuffer and scene_digests were rendered through ref_path (surface fetch and texture taps forwarded to the oracle);
 tests/test_hostile_taps_cpu.py renders them again through ref_path_real (the reference's own) and requires the committed bytes.
@@ -326,6 +329,23 @@ def dump_hostile_taps():
     assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "hostile_rays.npz")), os.path.getsize(path)
 
 
+def dump_hostile_shade():
+    # tests/prt_hostile_shade.py: materials and lights at the IEEE corners of the bounce loop (emission test, Russian roulette, light
+    # addend), rendered whole by the compiled reference.  Only scenes the reference defines are stored; the generator asserts it.
+    import prt_hostile_shade as S
+    out = S.generate()
+    for name in S.FIXTURE:
+        d = S.desc(name)
+        rgb, st = T.ref_render(d, S.SPP, (0, 0, d.width - 1, d.height - 1), seed=S.SEED, stats=True)
+        out[f"{name}/ref_image"] = rgb
+        out[f"{name}/ref_rays"] = np.array([st["raysTraced"], st["occludedTraced"]], dtype=np.uint64)
+        print("hostile shade", name, st["raysTraced"], st["occludedTraced"], "NaN", int(np.isnan(rgb).sum()), "of", rgb.size)
+    path = os.path.join(HERE, "hostile_shade.npz")
+    np.savez_compressed(path, **out)
+    print("hostile shade:", os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) <= 256 * 1024, os.path.getsize(path)
+
+
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", T.ORACLE_DIR])
     dump_cornell()
@@ -339,3 +359,4 @@ if __name__ == "__main__":
     dump_scene_digests()
     dump_hostile()
     dump_hostile_taps()
+    dump_hostile_shade()
