@@ -22,6 +22,7 @@ SOURCES = [
     "prt_edit.hip",
     "prt_display.hip",
     "prt_query.hip",
+    "prt_rowtests.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",
     "host/prt_models.cpp",

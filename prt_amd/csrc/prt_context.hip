@@ -1,5 +1,5 @@
 // prt_context.hip -- the context behind the C-ABI handle (include/prt_hip.h): its lifetime, the last-error string, the camera, the
-// scaffold every entry point shares (prt_internal.h), and what reads a context back: download, statistics and the sticky error
+// scaffold every entry point shares and the host half of a batch launch (prt_internal.h), and what reads a context back: download, statistics and the sticky error
 // words.  Host code only: no kernel is defined or launched here, so that the frame kernels' code objects (prt_kernels.hip) do not
 // move when it changes.
 #include <algorithm>
@@ -96,6 +96,32 @@ int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1)
     *ev0 = c->evT0[c->ringUsed];
     *ev1 = c->evT1[c->ringUsed];
     c->ringUsed++;
+    return PRT_HIP_OK;
+}
+
+int prt_batch_begin(prt_hip_ctx* c, uint64_t items, uint32_t resident, bool timed, BatchLaunch* L)
+{
+    hipStream_t s = c->stream;
+    int rc = prt_launch_resources(c, resident);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
+    L->ctl = BatchCtl{c->work, c->spill, c->spillThreads(), c->counters};
+    L->blocks = (uint32_t)std::min<uint64_t>((items + PRT_BLOCK - 1) / PRT_BLOCK, resident);
+    L->ev1 = nullptr;
+    if (timed) {
+        hipEvent_t ev0;
+        if ((rc = prt_timing_pair(c, &ev0, &L->ev1))) return rc;
+        HIP_TRY(hipEventRecord(ev0, s));
+    }
+    return PRT_HIP_OK;
+}
+
+int prt_batch_end(prt_hip_ctx* c, const BatchLaunch& L, const char* kernel)
+{
+    int rc = prt_launched(kernel);
+    if (rc) return rc;
+    if (L.ev1) HIP_TRY(hipEventRecord(L.ev1, c->stream));
     return PRT_HIP_OK;
 }
 

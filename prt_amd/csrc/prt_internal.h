@@ -10,6 +10,7 @@
 #include "../../include/prt_hip.h"
 #include "prt_devbuf.h"
 #include "prt_device.h"
+#include "prt_batch.h"
 
 #define PRT_WORK_WORDS 512 // control words of a launch (frame kernel: prt_frame.h PRT_CTRL_CURSORS; claim cursor of the G-buffer kernel)
 #define PRT_STICKY_WORDS 160 // behind the control words and NEVER cleared by a render: [0] error flags of any earlier launch (1 watchdog, 2 stack
@@ -180,6 +181,17 @@ int prt_launched(const char* kernel);
 int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1);
 // The spill columns of the traversal stacks for a launch of `blocks` workgroups.
 int prt_launch_resources(prt_hip_ctx* c, uint32_t blocks);
+// One launch of a batch kernel (prt_batch.h) over `items` rays on the context's stream, `resident` workgroups at the most.  begin
+// sizes the spill columns, clears the statistics and the control words and fills L.ctl and L.blocks; the caller launches L.blocks
+// workgroups of PRT_BLOCK threads with L.ctl in the kernel's arguments; end reports a refused launch under the kernel's name.
+// timed: prt_hip_get_stats counts and times the launch as it does a render (an event pair of the timing ring around it).
+struct BatchLaunch {
+    BatchCtl ctl;
+    uint32_t blocks;
+    hipEvent_t ev1; // timed: recorded behind the launch; else null
+};
+int prt_batch_begin(prt_hip_ctx* c, uint64_t items, uint32_t resident, bool timed, BatchLaunch* L);
+int prt_batch_end(prt_hip_ctx* c, const BatchLaunch& L, const char* kernel);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
 // The ONE place that writes a material record (prt_hip_upload_scene, prt_hip_update_materials); its size is tied to the stride the

@@ -1,8 +1,8 @@
 // prt_query.hip -- ray queries (include/prt_hip.h "ray queries"): nearest hit, any hit and surface records for batches of the caller's
-// own rays.  The traversal is trace_loop of prt_device.h, unchanged, behind a ray source that reads prt_ray records and a sink that
-// writes prt_hit / prt_surface / one byte; the surface fetch is get_surface, sample_bump and sample_diffuse, unchanged.  In a
-// translation unit of its own, as prt_temporal.hip and prt_display.hip are, so that the code objects of every other kernel -- the
-// frame kernel's above all -- do not move.
+// own rays.  The traversal is trace_loop of prt_device.h, unchanged, in the shell every batch kernel shares (prt_batch.h), behind a ray
+// source that reads prt_ray records and a sink that writes prt_hit / prt_surface / one byte; the surface fetch is get_surface,
+// sample_bump and sample_diffuse, unchanged.  In a translation unit of its own, as prt_temporal.hip and prt_display.hip are, so that
+// the code objects of every other kernel -- the frame kernel's above all -- do not move.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,10 +34,7 @@ struct QueryArgs {
     prt_hit* hits;
     float4* surf;       // 5 x float4 per record, or nullptr
     uint8_t* occ;
-    uint32_t* cursor;
-    uint32_t* spill;
-    uint32_t spillStride;
-    unsigned long long* counters;
+    BatchCtl ctl;
 };
 
 __device__ __forceinline__ void store_miss(float4* q)
@@ -69,7 +66,7 @@ template <bool SURFACE>
 struct QuerySrc {
     const QueryArgs* A;
     __device__ __forceinline__ uint32_t count() const { return A->n; }
-    __device__ __forceinline__ uint32_t* cursor() const { return A->cursor; }
+    __device__ __forceinline__ uint32_t* cursor() const { return A->ctl.cursor; }
     __device__ __forceinline__ void load(uint32_t i, Vec3& org, Vec3& dir, float& maxT, uint32_t& rev) const
     {
         const float4 a = gld4(A->rays + 2 * (size_t)i), b = gld4(A->rays + 2 * (size_t)i + 1);
@@ -106,36 +103,18 @@ struct QuerySrc {
 template <bool SURFACE>
 __global__ __launch_bounds__(PRT_BLOCK) void query_nearest_kernel(QueryArgs A)
 {
-    __shared__ uint32_t ldsRef[PRT_STACK_LDS * PRT_BLOCK];
-    __shared__ float ldsT[PRT_BLOCK];
-    const uint32_t tid = threadIdx.x;
-    __shared__ uint32_t coopTbl[(PRT_BLOCK / 64) * PRT_COOP_STRIDE];
-    const StackT<PRT_STACK_LDS> st{(lds_u32*)&ldsRef[tid], (lds_f32*)&ldsT[tid], A.spill, A.spillStride, nullptr,
-                                   (lds_u32*)&coopTbl[(tid >> 6) * PRT_COOP_STRIDE]};
     QuerySrc<SURFACE> src{&A};
-    Traffic tr{};
-    uint32_t overflow = 0;
-    trace_loop<PRT_MODE_SINGLE, false>(A.sc, src, st, tr, overflow);
-    if (overflow) atomicAdd(&A.counters[7], 1ull);
-    if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.counters[0], (unsigned long long)A.n); // raysTraced
+    trace_batch<PRT_MODE_SINGLE>(A.sc, src, A.ctl);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&A.ctl.counters[0], (unsigned long long)A.n); // raysTraced
 }
 
 __global__ __launch_bounds__(PRT_BLOCK) void query_any_kernel(QueryArgs A)
 {
-    __shared__ uint32_t ldsRef[PRT_STACK_LDS * PRT_BLOCK];
-    __shared__ float ldsT[PRT_BLOCK];
-    const uint32_t tid = threadIdx.x;
-    __shared__ uint32_t coopTbl[(PRT_BLOCK / 64) * PRT_COOP_STRIDE];
-    const StackT<PRT_STACK_LDS> st{(lds_u32*)&ldsRef[tid], (lds_f32*)&ldsT[tid], A.spill, A.spillStride, nullptr,
-                                   (lds_u32*)&coopTbl[(tid >> 6) * PRT_COOP_STRIDE]};
     QuerySrc<false> src{&A};
-    Traffic tr{};
-    uint32_t overflow = 0;
-    trace_loop<PRT_MODE_OCC_SINGLE, false>(A.sc, src, st, tr, overflow);
-    if (overflow) atomicAdd(&A.counters[7], 1ull);
-    if (blockIdx.x == 0 && tid == 0) {
-        atomicAdd(&A.counters[0], (unsigned long long)A.n); // raysTraced
-        atomicAdd(&A.counters[1], (unsigned long long)A.n); // occludedTraced
+    trace_batch<PRT_MODE_OCC_SINGLE>(A.sc, src, A.ctl);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd(&A.ctl.counters[0], (unsigned long long)A.n); // raysTraced
+        atomicAdd(&A.ctl.counters[1], (unsigned long long)A.n); // occludedTraced
     }
 }
 
@@ -230,24 +209,14 @@ int null_argument(const char* what)
 int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surf, uint8_t* occ, bool any)
 {
     hipStream_t s = c->stream;
-    const uint32_t want = (n + PRT_BLOCK - 1) / PRT_BLOCK;
-    const uint32_t resident = (uint32_t)(c->computeUnits * PRT_QUERY_BLOCKS_PER_CU);
-    const uint32_t blocks = std::min<uint32_t>(want, resident);
-    int rc = prt_launch_resources(c, resident);
+    BatchLaunch L;
+    int rc = prt_batch_begin(c, n, (uint32_t)c->computeUnits * PRT_QUERY_BLOCKS_PER_CU, true, &L);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
-    HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
-    QueryArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, occ, c->work, c->spill, c->spillThreads(), c->counters};
-    hipEvent_t ev0, ev1;
-    if ((rc = prt_timing_pair(c, &ev0, &ev1))) return rc;
-    HIP_TRY(hipEventRecord(ev0, s));
-    const char* name = any ? "query_any_kernel" : "query_nearest_kernel";
-    if (any) hipLaunchKernelGGL(query_any_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
-    else if (surf) hipLaunchKernelGGL(query_nearest_kernel<true>, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL(query_nearest_kernel<false>, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
-    if ((rc = prt_launched(name))) return rc;
-    HIP_TRY(hipEventRecord(ev1, s));
-    return PRT_HIP_OK;
+    QueryArgs A{c->sc, query_meshes(c), n, (const float4*)rays, hits, (float4*)surf, occ, L.ctl};
+    if (any) hipLaunchKernelGGL(query_any_kernel, dim3(L.blocks), dim3(PRT_BLOCK), 0, s, A);
+    else if (surf) hipLaunchKernelGGL(query_nearest_kernel<true>, dim3(L.blocks), dim3(PRT_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL(query_nearest_kernel<false>, dim3(L.blocks), dim3(PRT_BLOCK), 0, s, A);
+    return prt_batch_end(c, L, any ? "query_any_kernel" : "query_nearest_kernel");
 }
 
 // The inverse table of the uploaded scene on the context's stream (first use after an upload).
@@ -289,6 +258,67 @@ int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hi
     return prt_launched("query_surface_kernel");
 }
 
+// One query: what it launches, and its arrays -- the caller's or the context's staged copies; null: the query has no such array.
+// hitsIn: the hits QUERY_SURFACE fetches records of (nothing is traced then).
+enum QueryKind { QUERY_NEAREST, QUERY_ANY, QUERY_SURFACE };
+struct QueryIO {
+    QueryKind kind;
+    const prt_ray* rays;
+    const prt_hit* hitsIn;
+    prt_hit* hits;
+    prt_surface* surf;
+    uint8_t* occ;
+};
+
+int launch_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q)
+{
+    if (q.kind == QUERY_SURFACE) return launch_surface(c, n, q.rays, q.hitsIn, q.surf);
+    return launch_trace(c, n, q.rays, q.hits, q.surf, q.occ, q.kind == QUERY_ANY);
+}
+
+// PRT_HIP_QUERY_HOST: the arrays are host memory.  They are staged in the context's buffers, and the answers are in them on return.
+int query_staged(prt_hip_ctx* c, uint32_t n, const QueryIO& q)
+{
+    hipStream_t s = c->stream;
+    HIP_TRY(c->qRays.grow(n, s));
+    if (q.hits || q.hitsIn) HIP_TRY(c->qHits.grow(n, s));
+    if (q.surf) HIP_TRY(c->qSurf.grow(n, s));
+    if (q.occ) HIP_TRY(c->qOccl.grow(n, s));
+    HIP_TRY(hipMemcpyAsync(c->qRays, q.rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+    if (q.hitsIn) HIP_TRY(hipMemcpyAsync(c->qHits, q.hitsIn, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
+    const QueryIO d{q.kind, c->qRays, q.hitsIn ? (const prt_hit*)c->qHits : nullptr, q.hits ? (prt_hit*)c->qHits : nullptr,
+                    q.surf ? (prt_surface*)c->qSurf : nullptr, q.occ ? (uint8_t*)c->qOccl : nullptr};
+    int rc = launch_query(c, n, d);
+    if (rc) return rc;
+    if (q.hits) HIP_TRY(hipMemcpyAsync(q.hits, c->qHits, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
+    if (q.surf) HIP_TRY(hipMemcpyAsync(q.surf, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
+    if (q.occ) HIP_TRY(hipMemcpyAsync(q.occ, c->qOccl, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PRT_HIP_OK;
+}
+
+// The arrays are device memory: checked for the alignment the kernels load and store with, then queued around the caller's stream.
+int query_direct(prt_hip_ctx* c, uint32_t n, const QueryIO& q, void* stream, const char* what)
+{
+    const bool records = q.hits || q.hitsIn || q.surf;
+    if (!aligned(q.rays, 16) || !aligned(q.hits, 4) || !aligned(q.hitsIn, 4) || !aligned(q.surf, 16)) // (null is aligned)
+        return fail(PRT_HIP_EINVAL, std::string(what) + (records ? ": rays and surfaces must be 16-byte aligned, hits 4-byte aligned"
+                                                                 : ": rays must be 16-byte aligned"));
+    hipStream_t caller;
+    int rc;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_query(c, n, q))) return rc;
+    return prt_stream_leave(c, caller);
+}
+
+// What the three queries share behind their NULL checks.
+int run_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q, uint32_t flags, void* stream, const char* what)
+{
+    int rc = check_batch(c, n, flags, what);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return (flags & PRT_HIP_QUERY_HOST) ? query_staged(c, n, q) : query_direct(c, n, q, stream, what);
+}
+
 } // namespace
 
 extern "C" {
@@ -296,73 +326,19 @@ extern "C" {
 int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
     if (!c || !rays || !hits) return null_argument("query_nearest");
-    int rc = check_batch(c, n, flags, "query_nearest");
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (flags & PRT_HIP_QUERY_HOST) {
-        hipStream_t s = c->stream;
-        HIP_TRY(c->qRays.grow(n, s));
-        HIP_TRY(c->qHits.grow(n, s));
-        if (surfaces) HIP_TRY(c->qSurf.grow(n, s));
-        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        if ((rc = launch_trace(c, n, c->qRays, c->qHits, surfaces ? (prt_surface*)c->qSurf : nullptr, nullptr, false))) return rc;
-        HIP_TRY(hipMemcpyAsync(hits, c->qHits, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
-        if (surfaces) HIP_TRY(hipMemcpyAsync(surfaces, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return PRT_HIP_OK;
-    }
-    if (!aligned(rays, 16) || !aligned(hits, 4) || (surfaces && !aligned(surfaces, 16)))
-        return fail(PRT_HIP_EINVAL, "query_nearest: rays and surfaces must be 16-byte aligned, hits 4-byte aligned");
-    hipStream_t caller;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_trace(c, n, rays, hits, surfaces, nullptr, false))) return rc;
-    return prt_stream_leave(c, caller);
+    return run_query(c, n, QueryIO{QUERY_NEAREST, rays, nullptr, hits, surfaces, nullptr}, flags, stream, "query_nearest");
 }
 
 int prt_hip_query_any(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, uint8_t* occluded, uint32_t flags, void* stream)
 {
     if (!c || !rays || !occluded) return null_argument("query_any");
-    int rc = check_batch(c, n, flags, "query_any");
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (flags & PRT_HIP_QUERY_HOST) {
-        hipStream_t s = c->stream;
-        HIP_TRY(c->qRays.grow(n, s));
-        HIP_TRY(c->qOccl.grow(n, s));
-        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        if ((rc = launch_trace(c, n, c->qRays, nullptr, nullptr, c->qOccl, true))) return rc;
-        HIP_TRY(hipMemcpyAsync(occluded, c->qOccl, (size_t)n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return PRT_HIP_OK;
-    }
-    if (!aligned(rays, 16)) return fail(PRT_HIP_EINVAL, "query_any: rays must be 16-byte aligned");
-    hipStream_t caller;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_trace(c, n, rays, nullptr, nullptr, occluded, true))) return rc;
-    return prt_stream_leave(c, caller);
+    return run_query(c, n, QueryIO{QUERY_ANY, rays, nullptr, nullptr, nullptr, occluded}, flags, stream, "query_any");
 }
 
 int prt_hip_query_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
     if (!c || !rays || !hits || !surfaces) return null_argument("query_surface");
-    int rc = check_batch(c, n, flags, "query_surface");
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (flags & PRT_HIP_QUERY_HOST) {
-        hipStream_t s = c->stream;
-        HIP_TRY(c->qRays.grow(n, s));
-        HIP_TRY(c->qHits.grow(n, s));
-        HIP_TRY(c->qSurf.grow(n, s));
-        HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c->qHits, hits, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
-        if ((rc = launch_surface(c, n, c->qRays, c->qHits, c->qSurf))) return rc;
-        HIP_TRY(hipMemcpyAsync(surfaces, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return PRT_HIP_OK;
-    }
-    if (!aligned(rays, 16) || !aligned(hits, 4) || !aligned(surfaces, 16))
-        return fail(PRT_HIP_EINVAL, "query_surface: rays and surfaces must be 16-byte aligned, hits 4-byte aligned");
-    hipStream_t caller;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_surface(c, n, rays, hits, surfaces))) return rc;
-    return prt_stream_leave(c, caller);
+    return run_query(c, n, QueryIO{QUERY_SURFACE, rays, hits, nullptr, surfaces, nullptr}, flags, stream, "query_surface");
 }
 
 int prt_hip_query_get_counts(prt_hip_ctx* c, uint64_t* invalidHits)

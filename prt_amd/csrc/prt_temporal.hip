@@ -28,10 +28,7 @@ struct PosArgs {
     DevScene sc;
     DevCamera cam;
     float4* xyzt;
-    uint32_t* cursor;
-    uint32_t* spill;
-    uint32_t spillStride;
-    unsigned long long* counters;
+    BatchCtl ctl;
 };
 
 __device__ __forceinline__ Vec3 centre_dir(const DevCamera& cam, uint32_t x, uint32_t y)
@@ -50,7 +47,7 @@ __device__ __forceinline__ Vec3 centre_dir(const DevCamera& cam, uint32_t x, uin
 struct PosSrc {
     const PosArgs* A;
     __device__ __forceinline__ uint32_t count() const { return A->cam.width * A->cam.height; }
-    __device__ __forceinline__ uint32_t* cursor() const { return A->cursor; }
+    __device__ __forceinline__ uint32_t* cursor() const { return A->ctl.cursor; }
     __device__ __forceinline__ void load(uint32_t i, Vec3& org, Vec3& dir, float& maxT, uint32_t& rev) const
     {
         org = mk3(A->cam.pos[0], A->cam.pos[1], A->cam.pos[2]);
@@ -72,17 +69,8 @@ struct PosSrc {
 
 __global__ __launch_bounds__(PRT_BLOCK) void position_kernel(PosArgs A)
 {
-    __shared__ uint32_t ldsRef[PRT_STACK_LDS * PRT_BLOCK];
-    __shared__ float ldsT[PRT_BLOCK];
-    const uint32_t tid = threadIdx.x;
-    __shared__ uint32_t coopTbl[(PRT_BLOCK / 64) * PRT_COOP_STRIDE];
-    const StackT<PRT_STACK_LDS> st{(lds_u32*)&ldsRef[tid], (lds_f32*)&ldsT[tid], A.spill, A.spillStride, nullptr,
-                                   (lds_u32*)&coopTbl[(tid >> 6) * PRT_COOP_STRIDE]};
     PosSrc src{&A};
-    Traffic tr{};
-    uint32_t overflow = 0;
-    trace_loop<PRT_MODE_SINGLE, false>(A.sc, src, st, tr, overflow);
-    if (overflow) atomicAdd(&A.counters[7], 1ull);
+    trace_batch<PRT_MODE_SINGLE>(A.sc, src, A.ctl);
 }
 
 // ============================================================================ the merge kernel
@@ -265,7 +253,7 @@ int position_plane(prt_hip_ctx* c)
 }
 
 // The position guide of the current view on the context's stream: the host's own, or one launch of the position kernel over the
-// whole image when it is stale (force: also when it is not).  The launch shape is prt_hip_render_gbuffer's.
+// whole image when it is stale (force: also when it is not).  Launched as the G-buffer is: as many workgroups, not timed.
 int position_ready(prt_hip_ctx* c, bool force = false)
 {
     if (!c->haveScene || !c->haveCamera) return fail(PRT_HIP_ESTATE, "upload a scene and set a camera first");
@@ -274,16 +262,11 @@ int position_ready(prt_hip_ctx* c, bool force = false)
     if (!force && (c->tpHostPos || c->tpPosValid)) return PRT_HIP_OK;
     const uint32_t W = c->cam.width, H = c->cam.height;
     if ((uint64_t)W * H > 0xffffffffull) return fail(PRT_HIP_EINVAL, "image too large");
-    hipStream_t s = c->stream;
-    const uint32_t want = (uint32_t)(((uint64_t)W * H + PRT_BLOCK - 1) / PRT_BLOCK);
-    const uint32_t resident = (uint32_t)(c->computeUnits * 4);
-    const uint32_t blocks = std::min<uint32_t>(want, resident);
-    if ((rc = prt_launch_resources(c, resident))) return rc;
-    HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
-    HIP_TRY(hipMemsetAsync(c->work, 0, PRT_WORK_WORDS * sizeof(uint32_t), s));
-    PosArgs A{c->sc, c->cam, c->tpPos, c->work, c->spill, c->spillThreads(), c->counters};
-    hipLaunchKernelGGL(position_kernel, dim3(blocks), dim3(PRT_BLOCK), 0, s, A);
-    if ((rc = prt_launched("position_kernel"))) return rc;
+    BatchLaunch L;
+    if ((rc = prt_batch_begin(c, (uint64_t)W * H, (uint32_t)c->computeUnits * PRT_BATCH_BLOCKS_PER_CU, false, &L))) return rc;
+    PosArgs A{c->sc, c->cam, c->tpPos, L.ctl};
+    hipLaunchKernelGGL(position_kernel, dim3(L.blocks), dim3(PRT_BLOCK), 0, c->stream, A);
+    if ((rc = prt_batch_end(c, L, "position_kernel"))) return rc;
     c->tpPosValid = true;
     return PRT_HIP_OK;
 }
