@@ -697,6 +697,39 @@ int prt_hip_query_surface(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, con
                           uint32_t flags, void* stream);
 int prt_hip_query_get_counts(prt_hip_ctx* ctx, uint64_t* invalidHits); /* synchronous: records of the last prt_hip_query_surface refused on the device */
 
+/* radiance: what a baker asks instead of a hit record -- the path-traced radiance arriving along each ray (emission, sun and sky
+ * light, every bounce): light probes and irradiance volumes, lightmap texels, reflection cube maps and panoramas, any camera model
+ * the reference lacks.  The frame kernel itself (prt_frame.h) with a ray source that is the caller's array instead of the context's
+ * camera, and an output that is the caller's array instead of a camera-sized image.
+ *
+ * Definition.  Probe q (0-based) is, bit for bit, pixel (0, 0) of prt_hip_render under the camera
+ *     pos = rays[q].org,  dir = rays[q].dir (as given: the caller does not normalise it),  up = right = (0, 0, 0),
+ *     width = height = 1,  invWidth = invHeight = 1
+ * with params whose seed is seed + q (uint32 wrap).  So: the generator starts at lowbias32(q + seed) | 1; the eight primary rays of
+ * every packet are the same ray, run through camera.cpp:46-56 (both jitter terms are multiplied by the zero vectors), avgDir is their
+ * lane-ordered sum over 8, and each packet consumes 16 draws; the primary traversal (limit 100000, camera.cpp:64), the bounce loop,
+ * Russian roulette, the shadow-ray skip, the environment light and the defined refraction are the frame kernel's own;
+ *     radiance[3q .. 3q+2] = exposure * colour / samples.
+ * rays[q].tMax and pad are ignored.  A direction whose squared length overflows or underflows in float -- zero, 1e-30 or 3e20 long,
+ * or with an inf or NaN component -- normalises to zero or to non-finite components, and the probe returns what the reference returns
+ * for such a camera ray -- black (+0) -- and counts what the reference counts for it, its `samples` primary rays and no others; it is
+ * not refused and it does not disturb its neighbours.  A NaN in org is answered the same way.
+ *
+ * params: samples a multiple of 8 from 8 to 2040; maxDepth (<= 255), rrDepth, exposure as in prt_hip_render; rank must be 0 and
+ * nranks 1 (probes are not split over ranks); countTraffic must be 0 (the probe kernel has no counting build); tileSize is ignored.
+ * n: 1 .. 2^24 probes.  Anything else is PRT_HIP_EINVAL with a message, refused before anything is launched, radiance untouched.
+ * Pointers, flags and stream as for the other queries: DEVICE pointers by default, rays 16-byte aligned and radiance 4-byte aligned;
+ * with PRT_HIP_QUERY_HOST both are HOST pointers staged through the context's buffers and the call is synchronous; other flag bits
+ * are refused; the query is ordered after the work queued on stream and before what is queued next.
+ * State: needs a scene and NO camera (PRT_HIP_ESTATE without a scene).  It reads the scene and changes nothing else: the camera, the
+ * accumulator, the moments, the guides, the position plane, the history, the display state and the framebuffer are untouched, and so
+ * is what the last render left for the gathers.  For prt_hip_get_stats it is a render launch: kernelMs, raysTraced, occludedTraced,
+ * nPx = n, stackOverflow.  One persistent launch whatever n is.
+ * Not built: probes do not accumulate over calls (a caller averages equal-sample calls with different seeds itself), the eight lanes
+ * of a packet cannot carry distinct rays, and a batch is not split over ranks. */
+int prt_hip_query_radiance(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, const prt_render_params* params,
+                           float* radiance /* 3*n floats */, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

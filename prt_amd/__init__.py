@@ -187,6 +187,7 @@ EXPORTS = [
     "prt_hip_update_lights", "prt_hip_update_materials", "prt_hip_update_textures",
     "prt_hip_display", "prt_hip_download_display", "prt_hip_display_get_state", "prt_hip_display_reset", "prt_hip_upload",
     "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
+    "prt_hip_query_radiance",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -301,6 +302,7 @@ def _load(path, with_test_entry_points):
     L.prt_hip_query_any.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.prt_hip_query_surface.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
     L.prt_hip_query_get_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.prt_hip_query_radiance.argtypes = [vp, C.c_uint32, vp, C.POINTER(RenderParams), vp, C.c_uint32, vp]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
@@ -1083,6 +1085,30 @@ class PathTracer:
         n = C.c_uint64()
         self._chk(self._L.prt_hip_query_get_counts(self._ctx, C.byref(n)), "prt_hip_query_get_counts")
         return int(n.value)
+
+    def _probe_params(self, spp, seed, exposure, max_depth):
+        p = self.params(spp, exposure=1.0 if exposure is None else exposure, max_depth=max_depth)
+        if seed is not None:
+            p.seed = seed
+        return p
+
+    def query_radiance_async(self, n, d_rays, d_radiance, spp, seed=None, exposure=None, max_depth=None, stream=None):
+        """Queue prt_hip_query_radiance on device arrays: d_rays (n prt_ray, 16-byte aligned), d_radiance (3 * n float32) are device
+        pointers (int).  Probe q is traced under seed + q (seed None: the tracer's); max_depth / rr_depth are the tracer's."""
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        self._chk(self._L.prt_hip_query_radiance(self._ctx, n, d_rays, C.byref(p), d_radiance, 0, stream), "prt_hip_query_radiance")
+
+    def query_radiance(self, org, dir, spp, seed=None, exposure=None, max_depth=None):
+        """The path-traced radiance arriving along every ray: org, dir (n, 3) float32 (dir as it is: not normalised), spp a multiple
+        of 8 from 8 to 2040.  Returns (n, 3) float32 = exposure * colour / spp, probe q being pixel (0, 0) of a 1 x 1 camera at
+        org[q] looking along dir[q] under seed + q; sets last_stats (nPx = n).  Needs a scene and no camera."""
+        rays = make_rays(org, dir, 0.0)
+        out = np.zeros((len(rays), 3), dtype=np.float32)
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        self._chk(self._L.prt_hip_query_radiance(self._ctx, len(rays), rays.ctypes.data_as(C.c_void_p), C.byref(p),
+                                                 out.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_query_radiance")
+        self.last_stats = self.stats()  # raises on stack overflow
+        return out
 
     def pick(self, x, y):
         """What lies under pixel (x, y) of the current camera: the ray through the pixel's centre (the position guide's ray) ->

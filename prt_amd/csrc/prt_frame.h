@@ -145,6 +145,14 @@ struct FrameAdaptArgs {
     float4* accMom;       // per camera pixel: {mean, M2, bits(m), 0} of the luminance of its adaptive packets (Welford)
 };
 
+// Radiance queries (prt_hip_query_radiance): frame_kernel_probe's arguments are a FrameArgs followed by the caller's rays.
+// Work item w is probe w: the pixel code of its group is w itself (not x | y << 16), the "pixel" is (w, 0) of an image one row high whose
+// camera -- 1 x 1, up = right = 0 -- takes position and direction from rays[w] instead of A.cam.
+struct FrameProbeArgs {
+    FrameArgs f;
+    const prt_ray* rays; // totalWork records {org, tMax, dir, pad}: org and dir are read, as two 16-byte loads
+};
+
 struct __attribute__((aligned(16))) BlockState { // LDS, one per workgroup
     // one stack column per thread: PRT_STACK_LDS (12) references, or 6 (reference, entry distance) pairs for the packet traversal
     uint32_t stack[PRT_STACK_LDS * PRT_BLOCK];
@@ -259,6 +267,19 @@ __device__ __forceinline__ const FrameAdaptArgs& frame_adapt_args(uint64_t bits)
     return *(const FrameAdaptArgs*)(const __attribute__((address_space(4))) FrameAdaptArgs*)(((uint64_t)hi << 32) | lo);
 }
 
+// frame_kernel_probe only: the same segment read as FrameProbeArgs
+__device__ __forceinline__ const FrameProbeArgs& frame_probe_args(uint64_t bits)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
+    return *(const FrameProbeArgs*)(const __attribute__((address_space(4))) FrameProbeArgs*)(((uint64_t)hi << 32) | lo);
+}
+// PROBE: origin (a = 0) or direction (a = 1) of probe q, one 16-byte load
+__device__ __forceinline__ Vec3 probe_ray_vec(uint64_t kargs, uint32_t q, uint32_t a)
+{
+    const float4 v = gld4((const float4*)frame_probe_args(kargs).rays + 2 * (size_t)q + a);
+    return mk3(v.x, v.y, v.z);
+}
+
 // Counting build: a role call's event counts go to the block's 64-bit sums.
 __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& tr)
 {
@@ -286,11 +307,13 @@ __device__ __forceinline__ void block_count_traffic(BlockLds B, const Traffic& t
 // who holds the shade lock and publishes them).  Returns, in every lane of the group, the group's new pending word: the
 // number of rays emitted, or PEND_DONE when the pixel has been written.  ACC (frame_kernel_acc): the pixel's last packet adds
 // the pass to the accumulator and writes the mean over the pixel's total.  ADAPT (frame_kernel_adapt, implies ACC): every packet
-// end also folds the packet's mean luminance into the pixel's moment record.
-template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
+// end also folds the packet's mean luminance into the pixel's moment record.  PROBE (frame_kernel_probe): the group's pixel code is a
+// probe index q, its output 3 floats at rgb + 3 * q, and the camera's position and direction are those of rays[q].
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT, bool PROBE = false>
 __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t poolLocal)
 {
     static_assert(ACC || !ADAPT, "an adaptive pass is an accumulate pass");
+    static_assert(!PROBE || !ACC, "probes do not accumulate");
     // a function of its own: its registers are those of a shade kernel, whatever the caller keeps live around it
     const FrameArgs& A = frame_args(kargs);
     const BlockLds B = block_lds();
@@ -320,7 +343,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         float4 c = gld4(&A.gColor[g]);
         color = mk3(c.x, c.y, c.z);
     }
-    const uint32_t x = pixel & 0xffffu, y = pixel >> 16;
+    const uint32_t x = PROBE ? pixel : pixel & 0xffffu, y = PROBE ? 0u : pixel >> 16; // (PROBE: cam.width is 1, so x + y * width = q)
 
     // slot state
     Vec3 pos = mk3(0, 0, 0), rayDir = mk3(0, 0, 0), normal = mk3(0, 0, 0), beta = mk3(1, 1, 1), result = mk3(0, 0, 0), ndir = mk3(0, 0, 0);
@@ -356,6 +379,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         uint2 hb = gld2u(&A.hitB[gs]);
         float4 s2 = nt_load4(&A.S2[gs]); // the primary ray's direction
         Vec3 pdir = mk3(s2.x, s2.y, s2.z), porg = mk3(cam.pos[0], cam.pos[1], cam.pos[2]);
+        if constexpr (PROBE) porg = probe_ray_vec(kargs, pixel, 0);
         DevHit h{ha.x, ha.y, ha.z, ha.w, hb.x, hb.y};
         bool isHit = h.t != -1.0f;
         Surf5 sv{mk3(0, 0, 0), Vec2{0, 0}, 0, 0};
@@ -633,7 +657,15 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
     if (needCamera) {
         DevRay pr;
         Vec3 avgDir;
-        camera_packet(cam, rng, x, y, slot, gbase, pr, avgDir);
+        if constexpr (PROBE) { // pixel (0, 0) of the 1 x 1 camera at rays[q]: camera_packet's own arithmetic on the substituted fields
+            DevCamera pc = cam;
+            const Vec3 o = probe_ray_vec(kargs, pixel, 0), d = probe_ray_vec(kargs, pixel, 1);
+            pc.pos[0] = o.x; pc.pos[1] = o.y; pc.pos[2] = o.z;
+            pc.dir[0] = d.x; pc.dir[1] = d.y; pc.dir[2] = d.z;
+            camera_packet(pc, rng, 0u, 0u, slot, gbase, pr, avgDir);
+        } else {
+            camera_packet(cam, rng, x, y, slot, gbase, pr, avgDir);
+        }
         reverseBits = (avgDir.x < 0.0f ? 1u : 0u) | (avgDir.y < 0.0f ? 2u : 0u) | (avgDir.z < 0.0f ? 4u : 0u);
         ndir = pr.dir;
         emitPrimary = true;
@@ -741,9 +773,17 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
 // when the queue is empty and its last ray is done.  A finished ray's result is stored to the owner slot and the owner
 // group's pending word is decremented one loop turn later -- by then the step phase in between has waited for younger
 // loads, so the store has completed (vector memory operations of a wave retire in order) and the release fence is free.
-template <int MODE, bool COUNT>
+// QMODE = the traversal mode, or PRT_MODE_PACKET | PRT_QUEUE_PROBE (frame_kernel_probe's primary rays): such a ray starts at the origin
+// of its group's probe, read when the lane takes the ray -- once per ray, so the step loop holds no more registers than the camera's.
+// (A bit of the mode and not a template parameter of its own: the four trace_queue<mode, COUNT> keep their symbols, which the ISA
+// checks of tools/ and tests/ look for, and their code.)
+#define PRT_QUEUE_PROBE 4
+template <int QMODE, bool COUNT>
 __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 {
+    constexpr int MODE = QMODE & 3;
+    constexpr bool PROBE = (QMODE & PRT_QUEUE_PROBE) != 0;
+    static_assert(!PROBE || MODE == PRT_MODE_PACKET, "only primary rays start at a probe's origin");
     constexpr int NLDS = (MODE == PRT_MODE_PACKET) ? PRT_STACK_LDS_PACKET : PRT_STACK_LDS;
     const FrameArgs& A = frame_args(kargs);
     const BlockLds B = block_lds();
@@ -876,6 +916,7 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
                 if (MODE == PRT_MODE_PACKET) {
                     float4 s2 = nt_load4(&A.S2[gs]);
                     org = camPos;
+                    if constexpr (PROBE) org = probe_ray_vec(kargs, gld(&A.gPixel[blockIdx.x * PRT_POOL_GROUPS + (owner >> 3)]), 0);
                     dir = mk3(s2.x, s2.y, s2.z);
                     maxT = 100000.0f; // camera.cpp:64
                 } else if (MODE == PRT_MODE_SINGLE) {
@@ -1034,8 +1075,8 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 // ---------------------------------------------------------------------------------------------------------------- roles
 // Shade role (the caller holds the lock): give empty rows new work, then sweep the pending words and run the ready groups.
 // ACC: a pixel the accumulator has samples of starts from its stored generator state and colour sum instead of its seed.
-// ADAPT: work item w is the pixel of the launch's compacted list, list[w].
-template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
+// ADAPT: work item w is the pixel of the launch's compacted list, list[w].  PROBE: work item w is probe w, and w is its pixel code.
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT, bool PROBE = false>
 __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
 {
     const FrameArgs& A = frame_args(kargs);
@@ -1078,6 +1119,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         if (valid) {
             uint32_t pixel;
             if constexpr (ADAPT) pixel = gld(&frame_adapt_args(kargs).list[w]);
+            else if constexpr (PROBE) pixel = w;
             else pixel = work_item_pixel(A, w);
             gst(&A.gPixel[P], pixel);
             if constexpr (ACC) {
@@ -1096,7 +1138,8 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
                 gst(&A.gInfo[P], (uint32_t)PH_START << 20);
                 gst4(&A.gColor[P], sum);
             } else {
-                gst(&A.gRng[P], pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u);
+                if constexpr (PROBE) gst(&A.gRng[P], pixel_seed(pixel, 0u, A.cam.width, A.p.seed)); // pixel (0, 0) under seed + q
+                else gst(&A.gRng[P], pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u);
                 gst(&A.gInfo[P], (uint32_t)PH_START << 20);
                 gst4(&A.gColor[P], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
             }
@@ -1125,7 +1168,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         const uint32_t j = i + (lane >> 3);
         const bool has = j < n;
         const uint32_t local = has ? lds_ld(&readyList[j]) : 0u;
-        const uint32_t np = shade_pass<COUNT, ENV, ACC, ADAPT>(kargs, has ? poolBase + local : PRT_NONE, local);
+        const uint32_t np = shade_pass<COUNT, ENV, ACC, ADAPT, PROBE>(kargs, has ? poolBase + local : PRT_NONE, local);
         // (shade_pass has published the groups' state, their pending words and the queue tails, in that order)
         const bool head = has && (lane & 7u) == 0u;
         const bool done = head && np == PEND_DONE;
@@ -1151,7 +1194,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
 
 // The persistent launch (frame_kernel / frame_kernel_acc / frame_kernel_adapt below): the roles reach the arguments through the
 // kernel-argument segment.
-template <bool COUNT, bool ENV, bool ACC, bool ADAPT>
+template <bool COUNT, bool ENV, bool ACC, bool ADAPT, bool PROBE = false>
 __device__ __forceinline__ void frame_body()
 {
     const uint64_t kargs = frame_kernarg_bits();
@@ -1256,7 +1299,7 @@ __device__ __forceinline__ void frame_body()
             half = bcast0(half);
             if (bcast0(got)) {
                 wg_acquire();
-                did = shade_role<COUNT, ENV, ACC, ADAPT>(kargs, half);
+                did = shade_role<COUNT, ENV, ACC, ADAPT, PROBE>(kargs, half);
                 if (lane == 0) lds_st_rel(&B->lock[half], 0u);
                 PROF(tShade, nShade++);
             }
@@ -1264,7 +1307,7 @@ __device__ __forceinline__ void frame_body()
         if (!did && total > 0u) {
             best = bcast0(best);
             if (PRT_BALANCE && lane == 0) lds_add(&B->qWaves[best], 1u);
-            if (best == Q_PRIMARY) trace_queue<PRT_MODE_PACKET, COUNT>(kargs);
+            if (best == Q_PRIMARY) trace_queue<PRT_MODE_PACKET | (PROBE ? PRT_QUEUE_PROBE : 0), COUNT>(kargs);
             else if (best == Q_SCATTER) trace_queue<PRT_MODE_SINGLE, COUNT>(kargs);
             else if (best == Q_OCC_PACKET) trace_queue<PRT_MODE_OCC_PACKET, COUNT>(kargs);
             else trace_queue<PRT_MODE_OCC_SINGLE, COUNT>(kargs);
@@ -1364,6 +1407,13 @@ template <bool COUNT, bool ENV>
 __global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel_adapt(const FrameAdaptArgs kernargs)
 {
     frame_body<COUNT, ENV, true, true>();
+}
+
+// A batch of radiance probes (prt_hip_query_radiance): the frame kernel with a camera per work item, read from the caller's rays.
+template <bool ENV>
+__global__ __launch_bounds__(PRT_BLOCK, PRT_FRAME_WAVES) void frame_kernel_probe(const FrameProbeArgs kernargs)
+{
+    frame_body<false, ENV, false, false, true>();
 }
 
 // exposure * sum / count of an accumulator record (+0 where the count is 0) into one pixel of a framebuffer

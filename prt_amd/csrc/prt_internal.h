@@ -156,6 +156,7 @@ struct prt_hip_ctx {
     DevBuf<prt_hit> qHits;
     DevBuf<prt_surface> qSurf;
     DevBuf<uint8_t> qOccl;
+    DevBuf<float> qRad;                // prt_hip_query_radiance: 3 floats per probe
 };
 
 
@@ -192,6 +193,9 @@ struct BatchLaunch {
 };
 int prt_batch_begin(prt_hip_ctx* c, uint64_t items, uint32_t resident, bool timed, BatchLaunch* L);
 int prt_batch_end(prt_hip_ctx* c, const BatchLaunch& L, const char* kernel);
+// prt_kernels.hip, for prt_hip_query_radiance (prt_query.hip): one launch of the frame kernel's probe instantiation over n checked
+// probes on the context's stream, timed as a render: d_rays and d_radiance (3 * n floats) are device memory, p has been checked
+int prt_frame_probe(prt_hip_ctx* c, uint32_t n, const prt_ray* d_rays, const prt_render_params* p, float* d_radiance);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
 // The ONE place that writes a material record (prt_hip_upload_scene, prt_hip_update_materials); its size is tied to the stride the

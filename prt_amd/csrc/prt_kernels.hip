@@ -122,10 +122,11 @@ static int frame_layout(prt_hip_ctx* c, uint32_t blocks, bool env, FrameArgs& A)
     return PRT_HIP_OK;
 }
 
-enum FrameKind { FRAME_ONE_SHOT, FRAME_ACC, FRAME_ADAPT }; // frame_kernel, frame_kernel_acc, frame_kernel_adapt
-static const char* const kFrameKernelName[] = {"frame_kernel", "frame_kernel_acc", "frame_kernel_adapt"};
+enum FrameKind { FRAME_ONE_SHOT, FRAME_ACC, FRAME_ADAPT, FRAME_PROBE }; // frame_kernel, frame_kernel_acc, frame_kernel_adapt, frame_kernel_probe
+static const char* const kFrameKernelName[] = {"frame_kernel", "frame_kernel_acc", "frame_kernel_adapt", "frame_kernel_probe"};
 
-static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s, FrameKind kind)
+// probeRays: FRAME_PROBE only, the totalWork rays of the launch (device memory)
+static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, hipStream_t s, FrameKind kind, const prt_ray* probeRays = nullptr)
 {
     const prt_render_params* p = &A.p;
     A.totalWork = (uint32_t)totalWork;
@@ -161,7 +162,11 @@ static int render_frame_kernel(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork,
             else hipLaunchKernelGGL((K<false, false>), dim3(blocks), dim3(PRT_BLOCK), 0, s, ARGS);             \
         }                                                                                                      \
     } while (0)
-    if (kind == FRAME_ADAPT) { // an adaptive pass: the accumulate launch with the pixel list and the moments behind its arguments
+    if (kind == FRAME_PROBE) { // a batch of probes: the caller's rays behind the arguments (no counting build: prt_hip_query_radiance)
+        const FrameProbeArgs dAP{A, probeRays};
+        if (env) hipLaunchKernelGGL(frame_kernel_probe<true>, dim3(blocks), dim3(PRT_BLOCK), 0, s, dAP);
+        else hipLaunchKernelGGL(frame_kernel_probe<false>, dim3(blocks), dim3(PRT_BLOCK), 0, s, dAP);
+    } else if (kind == FRAME_ADAPT) { // an adaptive pass: the accumulate launch with the pixel list and the moments behind its arguments
         const FrameAdaptArgs dAD{FrameAccArgs{A, c->accRng, c->accSum}, c->adList, c->accMom};
         PRT_LAUNCH_FRAME(frame_kernel_adapt, dAD);
     } else if (kind == FRAME_ACC) { // a progressive pass: the same launch with the accumulator behind the arguments
@@ -232,7 +237,7 @@ static int frame_finish(prt_hip_ctx* c, const FrameLaunch& F)
 }
 
 // The launch itself, over `totalWork` work items, timed by the context's event ring.
-static int frame_launch(prt_hip_ctx* c, FrameLaunch& F, uint64_t totalWork, FrameKind kind)
+static int frame_launch_timed(prt_hip_ctx* c, FrameArgs& A, uint64_t totalWork, FrameKind kind, const prt_ray* probeRays = nullptr)
 {
     hipStream_t s = c->stream;
     HIP_TRY(hipMemsetAsync(c->counters, 0, PRT_STAT_SHARDS * PRT_STAT_STRIDE * sizeof(unsigned long long), s));
@@ -240,9 +245,15 @@ static int frame_launch(prt_hip_ctx* c, FrameLaunch& F, uint64_t totalWork, Fram
     int rc = prt_timing_pair(c, &ev0, &ev1);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ev0, s));
-    if ((rc = render_frame_kernel(c, F.A, totalWork, s, kind)) || (rc = prt_launched(kFrameKernelName[kind]))) return rc;
+    if ((rc = render_frame_kernel(c, A, totalWork, s, kind, probeRays)) || (rc = prt_launched(kFrameKernelName[kind]))) return rc;
     HIP_TRY(hipEventRecord(ev1, s));
-    return frame_finish(c, F);
+    return PRT_HIP_OK;
+}
+
+static int frame_launch(prt_hip_ctx* c, FrameLaunch& F, uint64_t totalWork, FrameKind kind)
+{
+    int rc = frame_launch_timed(c, F.A, totalWork, kind);
+    return rc ? rc : frame_finish(c, F);
 }
 
 // One launch of the frame kernel over a checked rectangle (prt_hip_render, prt_hip_render_accumulate).
@@ -565,3 +576,18 @@ int prt_hip_accum_import_moments(prt_hip_ctx* c, const float* mom)
 }
 
 } // extern "C"
+
+// ---- radiance queries (prt_hip_query_radiance, prt_query.hip): one timed launch of frame_kernel_probe over n probes on the context's
+// stream.  The camera of the launch is the degenerate one of the header's definition -- 1 x 1, up = right = 0 -- whose position and
+// direction the kernel takes from d_rays; the image is d_radiance.  Neither the context's camera nor its framebuffer, nor what a
+// render leaves for the gathers, is read or written.
+int prt_frame_probe(prt_hip_ctx* c, uint32_t n, const prt_ray* d_rays, const prt_render_params* p, float* d_radiance)
+{
+    FrameArgs A{};
+    A.sc = c->sc;
+    A.cam.width = A.cam.height = 1;
+    A.cam.invWidth = A.cam.invHeight = 1.0f;
+    A.p = *p;
+    A.rgb = d_radiance;
+    return frame_launch_timed(c, A, n, FRAME_PROBE, d_rays);
+}

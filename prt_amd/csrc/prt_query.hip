@@ -3,6 +3,8 @@
 // source that reads prt_ray records and a sink that writes prt_hit / prt_surface / one byte; the surface fetch is get_surface,
 // sample_bump and sample_diffuse, unchanged.  In a translation unit of its own, as prt_temporal.hip and prt_display.hip are, so that
 // the code objects of every other kernel -- the frame kernel's above all -- do not move.
+// prt_hip_query_radiance (radiance along the caller's rays) has its checks and its staging here; its kernel is the frame kernel's probe
+// instantiation, launched by prt_frame_probe (prt_kernels.hip), which shares the launch code of the renders.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -319,9 +321,59 @@ int run_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q, uint32_t flags, void
     return (flags & PRT_HIP_QUERY_HOST) ? query_staged(c, n, q) : query_direct(c, n, q, stream, what);
 }
 
+// ============================================================================ radiance along the caller's rays
+#define PRT_QUERY_MAX_PROBES (1u << 24)
+
+// What prt_hip_query_radiance asks of its scalar arguments; everything is refused before anything is queued.
+int check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags)
+{
+    const char* what = "query_radiance";
+    if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
+    if (n == 0 || n > PRT_QUERY_MAX_PROBES) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^24");
+    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
+        return fail(PRT_HIP_EINVAL, std::string(what) + ": samples must be a multiple of 8 from 8 to 2040");
+    if (p->maxDepth > 255) return fail(PRT_HIP_EINVAL, std::string(what) + ": maxDepth too large");
+    if (p->rank != 0 || p->nranks != 1) return fail(PRT_HIP_EINVAL, std::string(what) + ": probes are not split over ranks (rank 0 of nranks 1)");
+    if (p->countTraffic != 0) return fail(PRT_HIP_EINVAL, std::string(what) + ": countTraffic must be 0 (the probe kernel has no counting build)");
+    return PRT_HIP_OK;
+}
+
+int radiance_staged(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance)
+{
+    hipStream_t s = c->stream;
+    HIP_TRY(c->qRays.grow(n, s));
+    HIP_TRY(c->qRad.grow(3 * (size_t)n, s));
+    HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
+    int rc = prt_frame_probe(c, n, c->qRays, p, c->qRad);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(radiance, c->qRad, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PRT_HIP_OK;
+}
+
+int radiance_direct(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance, void* stream)
+{
+    if (!aligned(rays, 16) || !aligned(radiance, 4)) return fail(PRT_HIP_EINVAL, "query_radiance: rays must be 16-byte aligned, radiance 4-byte aligned");
+    hipStream_t caller;
+    int rc;
+    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = prt_frame_probe(c, n, rays, p, radiance))) return rc;
+    return prt_stream_leave(c, caller);
+}
+
 } // namespace
 
 extern "C" {
+
+int prt_hip_query_radiance(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance, uint32_t flags,
+                           void* stream)
+{
+    if (!c || !rays || !p || !radiance) return null_argument("query_radiance");
+    int rc = check_radiance(c, n, p, flags);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return (flags & PRT_HIP_QUERY_HOST) ? radiance_staged(c, n, rays, p, radiance) : radiance_direct(c, n, rays, p, radiance, stream);
+}
 
 int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {

@@ -46,6 +46,26 @@ def kernel_resources(kernel="_Z12frame_kernelILb0ELb0EEv9FrameArgs"):
     return out
 
 
+def device_asm_and_resources():
+    """(the listing of device_asm(), {function name: its resource-usage remarks}) from ONE compilation."""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC", "-pthread", "-ldl")]
+        cmd = [B.hipcc()] + flags + ["--cuda-device-only", "-S", os.path.join(B.CSRC, "prt_kernels.hip"), "-o", out, "-Rpass-analysis=kernel-resource-usage"]
+        err = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, check=True).stderr
+        asm = open(out).read()
+    res, cur = {}, None
+    for ln in err.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = res.setdefault(m.group(1), {})
+        elif cur is not None:
+            m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
+            if m:
+                cur[m.group(1).strip()] = int(m.group(2))
+    return asm, res
+
+
 def function_body(asm, name=FUNC):
     a = asm.index(f"\n{name}:")
     b = asm.index(f".size\t{name}", a)
@@ -122,15 +142,19 @@ def summary(body):
 
 
 if __name__ == "__main__":
-    lines = function_body(device_asm())
+    # --func NAME / --kernel NAME: another traversal function (the probe kernel's primary rays: _Z11trace_queueILi4ELb0EEvm) and the
+    # kernel whose resources are printed (_Z18frame_kernel_probeILb0EEv14FrameProbeArgs)
+    func = sys.argv[sys.argv.index("--func") + 1] if "--func" in sys.argv else FUNC
+    kernel = sys.argv[sys.argv.index("--kernel") + 1] if "--kernel" in sys.argv else None
+    lines = function_body(device_asm(), func)
     loop, body = step_loop(lines)
     n, kinds, scratch = summary(body)
-    print(f"{FUNC}: step loop header {loop}, {n} instructions in its blocks (static count, all paths): "
+    print(f"{func}: step loop header {loop}, {n} instructions in its blocks (static count, all paths): "
           + ", ".join(f"{v} {k}*" for k, v in kinds.items() if v))
     print("scratch_ instructions inside the loop:", len(scratch))
     for s in scratch:
         print("   ", s)
-    print("frame_kernel<false, false>:", kernel_resources())
+    print(f"{kernel}:" if kernel else "frame_kernel<false, false>:", kernel_resources(kernel) if kernel else kernel_resources())
     if "--dump" in sys.argv:
         with open(sys.argv[sys.argv.index("--dump") + 1], "w") as f:
             f.write(f"; gfx950 ISA of the step loop of trace_queue<1, false> (scatter rays), source_sha16 {B.source_sha16()}\n")
