@@ -499,6 +499,63 @@ typedef struct {
 } prt_mesh_update;
 int prt_hip_update_meshes(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, void* stream);
 
+/* ---- geometry updates from device memory: prt_hip_update_meshes for callers that deform ON THE DEVICE (simulation, skinning, a
+ * PyTorch kernel on the same card).  positions / normals are DEVICE pointers: the refit's gather kernel reads the caller's array where
+ * it lies -- no staging copy in front of it -- ordered on `stream` after whatever the caller queued there (the kernel that wrote the
+ * positions).  The caller's arrays may be reused when the call returns.  What the host path expects the caller to bring along, the
+ * library computes (prt_deform.hip):
+ *   - PRT_HIP_NORMALS_RECOMPUTE: Mesh::calculateVertexNormals (mesh.cpp:108-149) of the new positions, bit for bit, by two kernels.  One
+ *     lane per face: fn = normalize(cross(p1 - p0, p2 - p0)), (0, 0, 0) when a component is NaN.  One lane per vertex walks the vertex's
+ *     incidence list in the order the reference's sequential loop reaches that vertex's corners (faces descending, corners ascending
+ *     within a face; a face that names the vertex twice appears twice): n = acc + fn; if (sqrtf(dot(n, n)) > 0) acc = n; the result
+ *     is normalize(acc).  The sequential loop touches a vertex's accumulator at that vertex's own corners only, so the walk is the same
+ *     arithmetic in the same order.  The incidence list (CSR) is built on the host at a mesh's first RECOMPUTE from the device's own
+ *     leaf tables and kept with the scene (4 bytes per vertex + 36 bytes per triangle); PRT_HIP_EINVAL when the leaves of the uploaded
+ *     tree do not name every triangle exactly once.
+ *   - PRT_HIP_DEFORM_RADIUS_AUTO: the radius of Scene::add / Scene::updatePositions (scene.cpp:23-26): per mesh the box over ALL
+ *     vertexCount positions (Mesh::calculateBounds: vertices no triangle uses count), merged over the meshes, center = 0.5f * (upper +
+ *     lower), radius = length(upper - center) in f32.  The box of a deformed mesh is a min / max reduction over the new positions
+ *     (exact and order independent up to the sign of a zero, which the radius cannot see); the box of a mesh never touched was taken
+ *     from the descriptor at upload; a mesh last changed by prt_hip_update_meshes has its staged copy reduced when it is next needed.
+ * The contract is prt_hip_update_meshes': afterwards the context is in exactly the state prt_hip_upload_scene produces from the same
+ * topology with the new positions, normals and radius; the same things are invalidated; the call synchronises the context's stream
+ * once (root boxes, vertex boxes).  Refusals (a refused call changes nothing): everything prt_hip_update_meshes refuses; an unknown
+ * normalsMode or flag bit; GIVEN with NULL normals, KEEP / RECOMPUTE with non-NULL normals; GIVEN or RECOMPUTE for a mesh uploaded
+ * without vertex normals; PRT_HIP_DEFORM_RADIUS_AUTO with a non-zero radius.  Without AUTO, radius is prt_mesh_update's.
+ * Memory: 12 bytes per vertex (24 with normals) of every mesh ever updated, as for prt_hip_update_meshes: the library keeps its own
+ * copy (written by the kernel that reduces the box) for prt_hip_get_mesh_vertices. ---- */
+#define PRT_HIP_NORMALS_KEEP      0u  /* as normals == NULL in prt_hip_update_meshes */
+#define PRT_HIP_NORMALS_GIVEN     1u  /* read `normals` */
+#define PRT_HIP_NORMALS_RECOMPUTE 2u  /* Mesh::calculateVertexNormals (mesh.cpp:108-149) of the new positions, on the device */
+#define PRT_HIP_DEFORM_HOST        1u /* positions / normals are HOST pointers (staged and copied as today); default: DEVICE pointers */
+#define PRT_HIP_DEFORM_RADIUS_AUTO 2u /* radius = Scene radius of the updated scene, computed by the library; prt_mesh_deform.radius must be 0 */
+typedef struct {
+    uint32_t mesh, vertexCount;  /* as prt_mesh_update */
+    const float* positions;      /* 3*vertexCount */
+    const float* normals;        /* 3*vertexCount with PRT_HIP_NORMALS_GIVEN, else NULL */
+    uint32_t normalsMode;        /* PRT_HIP_NORMALS_* */
+    float radius;                /* as prt_mesh_update; 0 with PRT_HIP_DEFORM_RADIUS_AUTO */
+} prt_mesh_deform;
+int prt_hip_deform_meshes(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_deform* deforms, uint32_t flags, void* stream);
+/* The current positions and vertex normals of a mesh, from the copies the library keeps since the mesh's first update (either call);
+ * either pointer may be NULL.  Targets are device pointers (the copies are queued, ordered with `stream`), or host pointers with
+ * PRT_HIP_DEFORM_HOST (synchronous).  PRT_HIP_ESTATE for a mesh never updated, or whose normals never were ("no update yet: the caller
+ * still holds what it uploaded").  With it a caller that deforms on the device brings a host Scene in step, or reads the recomputed normals. */
+int prt_hip_get_mesh_vertices(prt_hip_ctx* ctx, uint32_t mesh, float* positions, float* normals, uint32_t flags, void* stream);
+/* The tree readout: what a refit has cost in the builder's own terms.  area(box) = 2.0f * (ex*ey + ey*ez + ez*ex) in f32
+ * (vecmath.cpp:75-79); internalArea = sum of area over the internal nodes, root included; leafArea = sum of primCount * area over the
+ * leaves; both summed in f64 in a fixed order (one kernel over the mesh's node records: block tree, per-block partials, one final
+ * block; the root's own box is added on the host), so a run repeats itself bit for bit.  sahCost = (0.125 * internalArea + leafArea) /
+ * rootArea, 0.125 being the builder's traversal constant (bvh.cpp:111).  sahCostAtUpload is the same quantity of the tree as uploaded,
+ * taken before the mesh's first update: sahCost / sahCostAtUpload is the number to watch, and to rebuild on.  vertexBox: lower, upper
+ * of Mesh::calculateBounds; rootBox: the tree's; radius: the scene's.  Synchronous; changes nothing in the context. */
+typedef struct {
+    float vertexBox[6], rootBox[6], radius;
+    double internalArea, leafArea, rootArea, sahCost, sahCostAtUpload;
+    uint32_t internalNodes, leaves;
+} prt_mesh_info;
+int prt_hip_mesh_info(prt_hip_ctx* ctx, uint32_t mesh, prt_mesh_info* out);
+
 /* ---- scene edits: the lights, single materials and the texels of single textures of the uploaded scene, replaced in place.  Everything
  * else that changes in a look-dev session -- the sun, the environment map, a material colour, a repainted texture -- without the
  * flattening and the copies of a whole prt_hip_upload_scene.  The contract of all three calls: after the call the context is in exactly

@@ -57,6 +57,10 @@ int prt_hip_test_scene_arrays(prt_hip_ctx* ctx, uint64_t counts[5], float* wnode
  * median time of the gather kernels, ms[1] = median of the level launches and the finish kernel (the copies of the caller's arrays
  * lie before both).  Ends with one real prt_hip_update_meshes.  Synchronous. */
 int prt_hip_test_refit_profile(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_update* updates, uint32_t reps, float* ms2);
+/* tools/refit_bench.py --device: prt_hip_deform_meshes' device work queued `reps` times between HIP events on the context's stream;
+ * ms[0..4] = medians of keep + box, face normals, vertex normals, gather, level launches + finish.  Ends with one real
+ * prt_hip_deform_meshes.  Synchronous. */
+int prt_hip_test_deform_profile(prt_hip_ctx* ctx, uint32_t count, const prt_mesh_deform* deforms, uint32_t flags, uint32_t reps, float* ms5);
 /* Occlusion rays of the context's last render (or accumulate / adaptive pass) that the frame kernel answered without a walk: the
  * surface faces away from the slot's light, so an unoccluded answer would add +-0.  They are part of
  * prt_hip_stats.occludedTraced and raysTraced, which count the reference's rays; 0 for a render with countTraffic, which walks every

@@ -112,6 +112,28 @@ class MeshUpdate(C.Structure):
                 ("radius", C.c_float)]
 
 
+class MeshDeform(C.Structure):
+    """prt_mesh_deform (include/prt_hip.h "geometry updates from device memory")."""
+    _fields_ = [("mesh", C.c_uint32), ("vertexCount", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p),
+                ("normalsMode", C.c_uint32), ("radius", C.c_float)]
+
+    NORMALS_KEEP, NORMALS_GIVEN, NORMALS_RECOMPUTE = 0, 1, 2
+    HOST, RADIUS_AUTO = 1, 2
+
+
+class MeshInfo(C.Structure):
+    """prt_mesh_info: the tree readout of prt_hip_mesh_info."""
+    _fields_ = [("vertexBox", C.c_float * 6), ("rootBox", C.c_float * 6), ("radius", C.c_float), ("internalArea", C.c_double),
+                ("leafArea", C.c_double), ("rootArea", C.c_double), ("sahCost", C.c_double), ("sahCostAtUpload", C.c_double),
+                ("internalNodes", C.c_uint32), ("leaves", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(vertexBox=np.array(self.vertexBox[:], dtype=np.float32), rootBox=np.array(self.rootBox[:], dtype=np.float32),
+                    radius=np.float32(self.radius), internalArea=float(self.internalArea), leafArea=float(self.leafArea),
+                    rootArea=float(self.rootArea), sahCost=float(self.sahCost), sahCostAtUpload=float(self.sahCostAtUpload),
+                    internalNodes=int(self.internalNodes), leaves=int(self.leaves))
+
+
 class LightUpdate(C.Structure):
     _fields_ = [("hasDirectionalLight", C.c_uint32), ("lightDir", C.c_float * 3), ("lightIntensity", C.c_float * 3),
                 ("envMode", C.c_uint32), ("envWidth", C.c_int32), ("envHeight", C.c_int32), ("envTexels", C.POINTER(C.c_float))]
@@ -184,6 +206,7 @@ EXPORTS = [
     "prt_hip_denoise_set_guides", "prt_hip_denoise_get_guides", "prt_hip_accum_denoise", "prt_hip_denoise_variance",
     "prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
     "prt_hip_history_export", "prt_hip_history_import", "prt_hip_update_meshes",
+    "prt_hip_deform_meshes", "prt_hip_get_mesh_vertices", "prt_hip_mesh_info",
     "prt_hip_update_lights", "prt_hip_update_materials", "prt_hip_update_textures",
     "prt_hip_display", "prt_hip_download_display", "prt_hip_display_get_state", "prt_hip_display_reset", "prt_hip_upload",
     "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
@@ -201,7 +224,7 @@ TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos"
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
                 "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
                 "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile", "prt_hip_test_taps",
-                "prt_hip_test_surface"]
+                "prt_hip_test_surface", "prt_hip_test_deform_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -290,6 +313,9 @@ def _load(path, with_test_entry_points):
     L.prt_hip_history_export.argtypes = [vp, C.c_uint32, C.POINTER(CameraDesc), vp, vp, vp]
     L.prt_hip_history_import.argtypes = [vp, C.POINTER(CameraDesc), vp, vp, vp]
     L.prt_hip_update_meshes.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), vp]
+    L.prt_hip_deform_meshes.argtypes = [vp, C.c_uint32, C.POINTER(MeshDeform), C.c_uint32, vp]
+    L.prt_hip_get_mesh_vertices.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.prt_hip_mesh_info.argtypes = [vp, C.c_uint32, C.POINTER(MeshInfo)]
     L.prt_hip_update_lights.argtypes = [vp, C.POINTER(LightUpdate), vp]
     L.prt_hip_update_materials.argtypes = [vp, C.c_uint32, C.POINTER(MaterialUpdate), vp]
     L.prt_hip_update_textures.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), vp]
@@ -312,6 +338,7 @@ def _load(path, with_test_entry_points):
         L.prt_hip_test_edit_profile.argtypes = [vp, C.c_uint32, C.POINTER(TextureUpdate), C.c_uint32, vp]
         L.prt_hip_test_scene_arrays.argtypes = [vp, C.POINTER(C.c_uint64), vp, vp, vp, vp, vp, vp, vp]
         L.prt_hip_test_refit_profile.argtypes = [vp, C.c_uint32, C.POINTER(MeshUpdate), C.c_uint32, vp]
+        L.prt_hip_test_deform_profile.argtypes = [vp, C.c_uint32, C.POINTER(MeshDeform), C.c_uint32, C.c_uint32, vp]
         L.prt_hip_trace_rays.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_float, vp]
         L.prt_hip_test_leaf.argtypes = [vp, C.c_uint32, vp, vp]
         L.prt_hip_test_sincos.argtypes = [vp, C.c_uint32, vp, vp, vp]
@@ -598,6 +625,66 @@ class PathTracer:
             ups[k].radius = d.radius
         self._chk(self._L.prt_hip_update_meshes(self._ctx, len(ids), ups, stream), "prt_hip_update_meshes")
         self._scene = scene
+
+    # ---- geometry updates from device memory (include/prt_hip.h)
+    def _deforms(self, updates, host):
+        """[(mesh, positions, normals_or_mode), ...] -> (MeshDeform array, the host arrays it points into)."""
+        if self._scene is None:
+            raise PrtError("deform_meshes: upload a scene first")
+        d = self._scene.describe().contents
+        ups, keep = (MeshDeform * max(len(updates), 1))(), []
+
+        def pointer(a, count):
+            if host:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != 3 * count:
+                    raise PrtError(f"deform_meshes: {a.size} floats for {count} vertices")
+                keep.append(a)
+                return a.ctypes.data
+            return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
+
+        for k, (m, positions, normals) in enumerate(updates):
+            if not 0 <= m < d.meshCount:
+                raise PrtError(f"deform_meshes: the scene has no mesh {m}")
+            ups[k].mesh, ups[k].vertexCount = m, d.meshes[m].vertexCount
+            ups[k].positions = pointer(positions, ups[k].vertexCount)
+            if normals is None or (isinstance(normals, (int, np.integer)) and int(normals) in (0, 2)):  # (a mode, not a pointer)
+                ups[k].normalsMode = int(normals or 0)
+            else:
+                ups[k].normalsMode, ups[k].normals = MeshDeform.NORMALS_GIVEN, pointer(normals, ups[k].vertexCount)
+        return ups, keep
+
+    def deform_meshes(self, updates, host=False, radius_auto=True, stream=None):
+        """prt_hip_deform_meshes: new vertex positions for meshes of the uploaded scene, read from DEVICE memory on `stream`.  updates =
+        [(mesh, positions, normals_or_mode), ...]: positions (and given normals) are integer device pointers or objects with
+        data_ptr() (a torch tensor), numpy arrays with host=True; normals_or_mode is MeshDeform.NORMALS_KEEP (or None),
+        MeshDeform.NORMALS_RECOMPUTE, or the normals themselves.  radius_auto: the library computes the scene's radius; False keeps
+        the current one.  The host Scene is not touched: mesh_vertices + Scene.update_positions bring it in step."""
+        ups, keep = self._deforms(updates, host)
+        flags = (MeshDeform.HOST if host else 0) | (MeshDeform.RADIUS_AUTO if radius_auto else 0)
+        self._chk(self._L.prt_hip_deform_meshes(self._ctx, len(updates), ups, flags, stream), "prt_hip_deform_meshes")
+
+    def mesh_vertices(self, mesh, normals=True):
+        """prt_hip_get_mesh_vertices to the host: (positions, normals) of mesh `mesh` as (V, 3) float32 arrays, as the library holds
+        them since the mesh's first update; normals=False returns (positions, None)."""
+        if self._scene is None:
+            raise PrtError("mesh_vertices: upload a scene first")
+        d = self._scene.describe().contents
+        if not 0 <= mesh < d.meshCount:
+            raise PrtError(f"mesh_vertices: the scene has no mesh {mesh}")
+        v = d.meshes[mesh].vertexCount
+        P = np.zeros((v, 3), np.float32)
+        N = np.zeros((v, 3), np.float32) if normals else None
+        self._chk(self._L.prt_hip_get_mesh_vertices(self._ctx, mesh, P.ctypes.data_as(C.c_void_p), None if N is None else N.ctypes.data_as(C.c_void_p),
+                                                    MeshDeform.HOST, None), "prt_hip_get_mesh_vertices")
+        return P, N
+
+    def mesh_info(self, mesh):
+        """prt_hip_mesh_info as a dict: vertexBox, rootBox, radius, internalArea, leafArea, rootArea, sahCost, sahCostAtUpload,
+        internalNodes, leaves.  sahCost / sahCostAtUpload is what a refit has cost the tree."""
+        info = MeshInfo()
+        self._chk(self._L.prt_hip_mesh_info(self._ctx, mesh, C.byref(info)), "prt_hip_mesh_info")
+        return info.as_dict()
 
     # ---- scene edits (include/prt_hip.h "scene edits"): lights, materials and texels of the uploaded scene, replaced in place
     def update_lights(self, scene, env=True, stream=None):

@@ -19,6 +19,7 @@ SOURCES = [
     "prt_denoise.hip",
     "prt_temporal.hip",
     "prt_refit.hip",
+    "prt_deform.hip",
     "prt_edit.hip",
     "prt_display.hip",
     "prt_query.hip",

@@ -46,6 +46,21 @@ struct PrtRefitMesh {
     std::vector<std::pair<uint32_t, uint32_t>> levels; // per depth (root's record first): {first entry in levelList, entries}
     float* dPos = nullptr;                // staging of the caller's positions / normals (3 * vertexCount floats), allocated by the first update
     float* dNrm = nullptr;
+    // device-side deformation (prt_deform.hip)
+    float vbox[6] = {};                   // Mesh::calculateBounds of the current positions (lower, upper), over ALL vertices
+    bool vboxValid = false;               // false after prt_hip_update_meshes: reduced from dPos when next needed
+    uint32_t* csrOff = nullptr;           // incidence list, built by the first PRT_HIP_NORMALS_RECOMPUTE: vertexCount + 1 offsets,
+    uint32_t* csrFace = nullptr;          // one face per corner (faces descending, corners ascending within a face),
+    uint32_t* faceVtx = nullptr;          // the index buffer (3 per face, mesh order) and
+    float* faceNrm = nullptr;             // the face normals of the last recompute (3 per face)
+    bool sahCaptured = false;             // sahUpload holds {internalArea, leafArea, rootArea} of the tree as uploaded
+    double sahUpload[3] = {};
+};
+// One mesh of a refit whose arrays are already on the device (prt_refit_queue): pos / nrm are what the gather kernel reads
+struct PrtRefitSrc {
+    uint32_t mesh;
+    const float* pos;
+    const float* nrm; // NULL: the shade records keep their normals
 };
 struct PrtRefit {
     std::vector<PrtRefitMesh> meshes;
@@ -59,6 +74,12 @@ struct PrtRefit {
     bool anyBump = false;
     float* rootOut = nullptr;      // device: PRT_MAX_BVH x 6 floats, the refitted root boxes
     float* rootHost = nullptr;     // pinned host copy of it
+    // prt_deform.hip, allocated on first use: the vertex boxes of a call (PRT_MAX_BVH x 6 floats), their pinned host copy, and the
+    // per-block partials of the box and SAH reductions
+    float* vboxOut = nullptr;
+    float* vboxHost = nullptr;
+    float* boxPartial = nullptr;
+    double* sahPartial = nullptr;
 };
 
 // Scene edits (prt_edit.hip): what the checks of prt_hip_update_materials / prt_hip_update_textures need from the upload, kept on the host.
@@ -230,6 +251,16 @@ inline void prt_accum_forget(prt_hip_ctx* c)
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
                     const std::vector<uint32_t>& slotVtx, bool anyBump);
 void prt_refit_forget(prt_hip_ctx* c);
+// prt_refit.hip, shared with prt_hip_deform_meshes (prt_deform.hip): every refusal of prt_hip_update_meshes; the staging buffers of the
+// named meshes (normals too where `normals` is set); gather, levels and finish of the named meshes queued on s, reading device
+// arrays (ev, optional, 3 events: before the gathers, after them, after the finish kernel); and, once the context's stream has been
+// synchronised behind the copy of rootOut to rootHost, the root boxes, the radius (0 keeps it) and everything the call invalidates
+int prt_refit_check(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u);
+int prt_refit_staging(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u);
+int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* src, hipStream_t s, hipEvent_t* ev);
+void prt_refit_commit(prt_hip_ctx* c, uint32_t count, const uint32_t* meshes, float radius);
+// prt_deform.hip: the SAH sums of the mesh's tree as uploaded, kept before its first update (PrtRefitMesh::sahUpload)
+int prt_deform_capture_sah(prt_hip_ctx* c, uint32_t mesh);
 // prt_denoise.hip: the view or the scene changed, or the planes are new (guides of either origin are dropped)
 void prt_denoise_forget(prt_hip_ctx* c);
 // prt_denoise.hip, for the temporal stage (prt_temporal.hip), which replaces the prepare step and then runs the same iterations:

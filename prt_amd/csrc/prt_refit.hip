@@ -10,6 +10,8 @@
 //           deepest first: the kernel boundary hands a level's boxes to the level above, so nothing inside a launch depends
 //           on another workgroup.  min / max of finite floats is exact and order independent (up to the sign of a zero).
 // The root boxes travel back to the host (DevScene is a by-value kernel argument), which costs the call one synchronisation.
+// prt_hip_deform_meshes (prt_deform.hip) shares the checks, the staging buffers, the three kernels (prt_refit_queue reads device
+// arrays wherever they lie) and the commit with prt_hip_update_meshes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -168,24 +170,34 @@ int upload_array(prt_hip_ctx* c, const std::vector<T>& v, T** out)
     return PRT_HIP_OK;
 }
 
-// Queues the copies of the caller's arrays, then gather, levels and finish for the named meshes on s.  ev (optional, 3 events):
-// recorded before the gathers, after them and after the finish kernel.
+// Queues the copies of the caller's host arrays into the staging buffers, then the refit reading them (prt_refit_queue).
 int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipStream_t s, hipEvent_t* ev)
 {
     PrtRefit& R = c->rf;
-    float* tris = const_cast<float*>(c->sc.tris);
-    float4* wnodes = const_cast<float4*>(c->sc.wnodes);
+    PrtRefitSrc src[PRT_MAX_BVH];
     for (uint32_t k = 0; k < count; k++) { // the caller's arrays first (the library copies)
         PrtRefitMesh& M = R.meshes[u[k].mesh];
         const size_t bytes = (size_t)M.vertexCount * 3 * sizeof(float);
         HIP_TRY(hipMemcpyAsync(M.dPos, u[k].positions, bytes, hipMemcpyHostToDevice, s));
         if (u[k].normals) HIP_TRY(hipMemcpyAsync(M.dNrm, u[k].normals, bytes, hipMemcpyHostToDevice, s));
+        M.vboxValid = false; // (the vertex box of the staged copy is reduced when a later call asks for it: prt_deform.hip)
+        src[k] = PrtRefitSrc{u[k].mesh, M.dPos, u[k].normals ? M.dNrm : nullptr};
     }
+    return prt_refit_queue(c, count, src, s, ev);
+}
+
+} // namespace
+
+int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStream_t s, hipEvent_t* ev)
+{
+    PrtRefit& R = c->rf;
+    float* tris = const_cast<float*>(c->sc.tris);
+    float4* wnodes = const_cast<float4*>(c->sc.wnodes);
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = R.meshes[u[k].mesh];
         if (M.slotCount == 0) continue;
-        GatherArgs g{R.slotVtx, M.dPos, u[k].normals ? M.dNrm : nullptr, tris, const_cast<float4*>(c->sc.shade),
+        GatherArgs g{R.slotVtx, u[k].pos, u[k].nrm, tris, const_cast<float4*>(c->sc.shade),
                      R.anyBump ? const_cast<float4*>(c->sc.bump) : nullptr, M.slotBase, M.slotCount, M.hasNormals ? 0u : 1u};
         hipLaunchKernelGGL(refit_gather_kernel, dim3((M.slotCount + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, g);
         int rc = prt_launched("refit_gather_kernel");
@@ -216,7 +228,7 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
 }
 
 // every refusal of prt_hip_update_meshes; nothing has changed when it returns non-zero
-int check_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
+int prt_refit_check(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
 {
     if (!c) return fail(PRT_HIP_EINVAL, "NULL argument");
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
@@ -238,7 +250,7 @@ int check_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
 }
 
 // staging buffers of the named meshes (kept with the scene)
-int staging_ready(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
+int prt_refit_staging(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
 {
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = c->rf.meshes[u[k].mesh];
@@ -259,7 +271,22 @@ int staging_ready(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
     return PRT_HIP_OK;
 }
 
-} // namespace
+void prt_refit_commit(prt_hip_ctx* c, uint32_t count, const uint32_t* meshes, float radius)
+{
+    for (uint32_t k = 0; k < count; k++) memcpy(c->sc.rootBox[meshes[k]], c->rf.rootHost + 6 * meshes[k], 6 * sizeof(float));
+    if (radius != 0.0f) c->sc.radius = radius;
+    // what was sampled or derived from the old geometry
+    prt_accum_forget(c);
+    prt_denoise_forget(c);
+    if (c->haveCamera) {
+        prt_camera_desc same;
+        static_assert(sizeof(same) == sizeof(c->cam), "camera layouts must match");
+        memcpy(&same, &c->cam, sizeof(same));
+        prt_temporal_camera_change(c, &same); // the same promotion as a camera move of unchanged size
+    } else {
+        prt_temporal_forget(c);
+    }
+}
 
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
                     const std::vector<uint32_t>& slotVtx, bool anyBump)
@@ -314,6 +341,7 @@ int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std
 void prt_refit_forget(prt_hip_ctx* c)
 {
     if (c->rf.rootHost) (void)hipHostFree(c->rf.rootHost);
+    if (c->rf.vboxHost) (void)hipHostFree(c->rf.vboxHost);
     c->rf = PrtRefit{}; // (the device arrays went with sceneAllocs)
 }
 
@@ -321,30 +349,24 @@ extern "C" {
 
 int prt_hip_update_meshes(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* updates, void* stream)
 {
-    int rc = check_update(c, count, updates);
+    int rc = prt_refit_check(c, count, updates);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = staging_ready(c, count, updates))) return rc;
+    if ((rc = prt_refit_staging(c, count, updates))) return rc;
+    for (uint32_t k = 0; k < count; k++) // prt_hip_mesh_info compares against the tree as uploaded
+        if ((rc = prt_deform_capture_sah(c, updates[k].mesh))) return rc;
     hipStream_t s = c->stream, caller;
     if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = queue_update(c, count, updates, s, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(c->rf.rootHost, c->rf.rootOut, PRT_MAX_BVH * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
     if ((rc = prt_stream_leave(c, caller))) return rc;
     HIP_TRY(hipStreamSynchronize(s)); // the root boxes are part of DevScene, which every later launch takes by value
+    uint32_t ids[PRT_MAX_BVH];
+    float radius = 0.0f; // with several updates the last non-zero one holds
     for (uint32_t k = 0; k < count; k++) {
-        memcpy(c->sc.rootBox[updates[k].mesh], c->rf.rootHost + 6 * updates[k].mesh, 6 * sizeof(float));
-        if (updates[k].radius != 0.0f) c->sc.radius = updates[k].radius;
+        ids[k] = updates[k].mesh;
+        if (updates[k].radius != 0.0f) radius = updates[k].radius;
     }
-    // what was sampled or derived from the old geometry
-    prt_accum_forget(c);
-    prt_denoise_forget(c);
-    if (c->haveCamera) {
-        prt_camera_desc same;
-        static_assert(sizeof(same) == sizeof(c->cam), "camera layouts must match");
-        memcpy(&same, &c->cam, sizeof(same));
-        prt_temporal_camera_change(c, &same); // the same promotion as a camera move of unchanged size
-    } else {
-        prt_temporal_forget(c);
-    }
+    prt_refit_commit(c, count, ids, radius);
     return PRT_HIP_OK;
 }
 
@@ -377,11 +399,13 @@ int prt_hip_test_scene_arrays(prt_hip_ctx* c, uint64_t counts[5], float* wnodes,
 // the context's state is that of one prt_hip_update_meshes.
 int prt_hip_test_refit_profile(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* updates, uint32_t reps, float* ms2)
 {
-    int rc = check_update(c, count, updates);
+    int rc = prt_refit_check(c, count, updates);
     if (rc) return rc;
     if (!ms2 || reps == 0) return fail(PRT_HIP_EINVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = staging_ready(c, count, updates))) return rc;
+    if ((rc = prt_refit_staging(c, count, updates))) return rc;
+    for (uint32_t k = 0; k < count; k++)
+        if ((rc = prt_deform_capture_sah(c, updates[k].mesh))) return rc;
     hipEvent_t ev[3];
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
     std::vector<float> g, l;

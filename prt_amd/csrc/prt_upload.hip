@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 #include "prt_internal.h"
 
@@ -283,6 +284,17 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
             rm.vertexCount = md.vertexCount;
             rm.primCount = md.primCount;
             rm.hasNormals = md.normals ? 1u : 0u;
+            // Mesh::calculateBounds (mesh.cpp:302-309): over ALL vertices, for the radius of prt_hip_deform_meshes (prt_deform.hip)
+            for (int j = 0; j < 3; j++) {
+                rm.vbox[j] = std::numeric_limits<float>::max();
+                rm.vbox[3 + j] = std::numeric_limits<float>::lowest();
+            }
+            for (uint32_t v = 0; v < md.vertexCount; v++)
+                for (int j = 0; j < 3; j++) {
+                    rm.vbox[j] = std::fmin(rm.vbox[j], md.positions[3 * v + j]);
+                    rm.vbox[3 + j] = std::fmax(rm.vbox[3 + j], md.positions[3 * v + j]);
+                }
+            rm.vboxValid = true;
             refitMeshes.push_back(std::move(rm));
         }
         // shading records (Mesh::getSurfaceProperties, mesh.cpp:311-364) in LEAF order, like the triangles: a hit names its
