@@ -327,6 +327,33 @@ int prt_hip_accum_import_moments(prt_hip_ctx* ctx, const float* mom);
  * error: an accumulate pass that also keeps moments).  There is no depth or position guide.  In a multi-rank run it works on
  * whatever this context's accumulator holds: pixels the rank does not own (count 0) stay +0.
  *
+ * Comparisons.  Every comparison is the IEEE comparison and false for NaN, here and in "temporal reprojection", and in both blocks
+ * max(a, b) means a > b ? a : b, which is b when a is NaN: a NaN albedo channel demodulates by 0.015625f (in the prepare step, the
+ * temporal stage and the multiply-back of the output alike), and a NaN dn gives wn = 0.  Within an iteration "V_p < 0" stands for
+ * the negation of the test "V_p >= 0" above it: a NaN V_p is unknown (no g, wl = 1.0f, no sumV, V'_p = -1).  Only the prepare
+ * step's V0_p = v_p < 0 ? -1 : ... is the literal test: a NaN v_p gives a NaN V0_p, which the first iteration reads as unknown.
+ *
+ * What follows for non-finite state.  The accumulator may hold NaN and infinite sums (a render of a scene with such materials or
+ * lights produces them, and prt_hip_accum_import takes any bits), the moments and the guides likewise.  The filter does not contain
+ * them.  Colour: a NaN or +-inf channel of the sum of ONE pixel of a fully valid image makes the output non-finite exactly on the
+ * square |dx|, |dy| <= 2*(2^k - 1) around it after k iterations, clipped to the image: 5 x 5, 13 x 13, 29 x 29, 61 x 61 and
+ * 125 x 125 pixels.  A weight of 0 does not protect a tap, because 0 * NaN is NaN and 0 * inf is NaN; only taps that are skipped
+ * (outside the image, count 0) stop the spread, so a valid pixel among count-0 pixels at all its tap offsets keeps a finite value.
+ * An infinity is still an infinity at its own pixel after the first iteration (every other tap there has wl = 0 or w finite) and
+ * NaN on the rest of the square; from the second iteration on the whole square is NaN.  Variance: a NaN V is unknown (-1) for good
+ * after one iteration and is never read as a tap, so it touches no neighbour.  A +inf V spreads: den becomes infinite and wl = 1
+ * wherever the 3x3 average sees it, and sumV takes (w*w) * inf, which is inf, or NaN where w is 0, so every pixel with a known V that
+ * taps it ends with an infinite or unknown V while all colours stay finite.  Such a V comes from an import with count < 8 with m >= 2
+ * (n >> 3 is 0) or from an infinite M2.  A negative M2 is a negative v: unknown.  Guides: a NaN albedo channel is a source like a NaN
+ * sum, with or without demodulation (wa is NaN to and from the pixel), except that a pixel with no other tap comes out as
+ * exposure * ((c / 0.015625f) * 0.015625f).  A +inf albedo channel has wa = 0 to every finite neighbour and harms nobody else; with
+ * demodulation its own channel is 0 * inf = NaN.  A negative (or -inf) albedo demodulates by 0.015625f, one above 1 by itself: there is
+ * no upper clamp.  A NaN normal channel is harmless (every wn to and from the pixel is 0: it keeps its own value, as a miss does).
+ * A long normal has wn above 1, and wn raised to 2^normalPowerLog2 can overflow: length 1.04 is finite at every setting, length 40
+ * gives w = +inf, or NaN against a weight of 0, and is a source for the taps it has a positive dot product with.  The display
+ * transform shows a NaN as 0, so a poisoned square is black on screen.  A host that imports accumulators or guides should check
+ * them; prt_hip_accum_denoise does not.
+ *
  * Guides: the context owns two camera-sized planes, albedo and normal.  Each is the average of K = guideSamples launches of the
  * G-buffer kernel (prt_hip_render_gbuffer type 0, respectively type 2, exposure 1; launch k = 0..K-1 with seed boundSeed + k, uint32
  * wrap-around, boundSeed = the accumulator's bound seed): g = g_0; g = g + g_k (k = 1..K-1); g = g * (1.0f / K), per float.  They
@@ -418,6 +445,16 @@ int prt_hip_denoise_variance(prt_hip_ctx* ctx, float* var);
  * before demodulation (the albedo guide of one surface point differs between two views), and no material or primitive id is used.
  * An invalid pixel stays invalid.  A pixel whose centre ray misses never takes history and never becomes history.  Without a
  * history (fresh context, after a reset, maxHistory = 0) the result is prt_hip_accum_denoise's, bit for bit.
+ *
+ * Non-finite state (comparisons and max(a, b) as "denoised previews" states them: IEEE, false for NaN).  The merge contains
+ * nothing either.  A tap with a NaN hLen is skipped (!(hLen_q > 0)); a +inf hLen is accepted and capped (q < maxHistory is false, so
+ * Hl = maxHistory), a denormal one is accepted and weighs nothing.  A NaN hV is not summed (hV_q >= 0 is false); a +inf hV makes Hv and vm
+ * infinite, and V spreads from there as an infinite V does.  A NaN v_p or Hv fails its >= 0 test and takes the next branch of vm.
+ * A NaN in hX or hN fails the acceptance test; an infinite hN can pass it.  A non-finite history colour enters every merged pixel
+ * whose accepted bilinear taps include it, whatever the tap's weight (0 * NaN is NaN): cm is non-finite there, the iterations
+ * spread it over the square of "denoised previews", and cm is carried in the pending record into the next history, where it merges
+ * again -- with an unchanged camera for as long as the view is denoised.  maxHistory caps the weight of a history, not of a NaN.
+ * prt_hip_history_reset ends this (so do prt_hip_upload_scene and a camera of another size); prt_hip_accum_denoise never sees it.
  *
  * Life cycle (what keeps samples from being counted twice):
  *   - a temporal denoise merges with the HISTORY only, never with pending, and overwrites pending: denoising the same view again

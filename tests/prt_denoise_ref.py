@@ -61,7 +61,7 @@ def denoise(total, count, mom, albedo, normal, iterations=5, normal_power_log2=5
         v = (mom[..., 1] / (m.astype(np.int64) - 1).astype(F)) / (count >> 3).astype(F)
         v = np.where(m >= 2, v, F(-1)).astype(F)
         if demodulate:
-            d = np.maximum(A, F(0.015625))
+            d = np.where(A > F(0.015625), A, F(0.015625)).astype(F)  # the header's max(a, b) = a > b ? a : b: 1/64 for a NaN albedo
             C = (c / d).astype(F)
             ld = lum(d)
             V = np.where(v < 0, F(-1), v / (ld * ld)).astype(F)

@@ -207,7 +207,7 @@ def denoise_temporal(total, count, mom, albedo, normal, position, history=None, 
     m = merge(total, count, mom, albedo, normal, position, history, position_tolerance, normal_cos, max_history)
     with np.errstate(all="ignore"):
         if demodulate:
-            d = np.maximum(m["A"], F(0.015625))
+            d = np.where(m["A"] > F(0.015625), m["A"], F(0.015625)).astype(F)  # max(a, b) = a > b ? a : b: 1/64 for a NaN albedo
             C = (m["cm"] / d).astype(F)
             ld = lum(d)
             V = np.where(m["vm"] < 0, F(-1), m["vm"] / (ld * ld)).astype(F)

@@ -50,7 +50,12 @@ def test_header_documents_the_filter():
                  "wl = V_p < 0 ? 1.0f : f(fabsf(L_p - lum(C_q)) / den)",
                  "sumV += (w*w) * (V_q >= 0 ? V_q : V_p)", "V'_p = V_p < 0 ? -1 : sumV / (sumW*sumW)",
                  "d_rgb_p = exposure * (C_final_p * d_p)", "g = g_0; g = g + g_k (k = 1..K-1); g = g * (1.0f / K)",
-                 "seed boundSeed + k", "BIASED", "no FMA", "PRT_HIP_ESTATE", "PRT_HIP_EINVAL", "1, 2, 4, 8 or 16"):
+                 "seed boundSeed + k", "BIASED", "no FMA", "PRT_HIP_ESTATE", "PRT_HIP_EINVAL", "1, 2, 4, 8 or 16",
+                 "Every comparison is the IEEE comparison and false for NaN", "max(a, b) means a > b ? a : b",
+                 "a NaN albedo channel demodulates by 0.015625f", "a NaN dn gives wn = 0", "a NaN V_p is unknown",
+                 "What follows for non-finite state", "|dx|, |dy| <= 2*(2^k - 1)", "125 x 125", "0 * NaN is NaN",
+                 "a NaN V is unknown (-1) for good", "A +inf V spreads", "count < 8 with m >= 2", "A NaN normal channel is harmless",
+                 "there is\n * no upper clamp", "length 40", "shows a NaN as 0"):
         assert rule in block, rule
 
 

@@ -74,7 +74,10 @@ def test_header_documents_the_stage():
                  "pending_p = {cm, vm}, {X_p, (valid_p and t_p >= 0) ? len : 0}, {N_p, 0};  pending camera = the current camera",
                  "RADIANCE space", "never with pending", "promotes it to history", "prt_hip_history_reset drop both",
                  "prt_hip_accum_reset / prt_hip_accum_import touch neither", "BIASED for view-dependent radiance",
-                 "varying `seed` per view", "16 bytes (position) plus 2 x 48 bytes", "no FMA", "PRT_HIP_ESTATE", "PRT_HIP_EINVAL"):
+                 "varying `seed` per view", "16 bytes (position) plus 2 x 48 bytes", "no FMA", "PRT_HIP_ESTATE", "PRT_HIP_EINVAL",
+                 "A tap with a NaN hLen is skipped", "A NaN hV is not summed", "takes the next branch of vm",
+                 "A non-finite history colour enters every merged pixel\n * whose accepted bilinear taps include it",
+                 "carried in the pending record into the next history", "prt_hip_history_reset ends this"):
         assert rule in block, rule
 
 
