@@ -35,11 +35,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return prt_fail(code, msg); }
 
-__device__ __forceinline__ Vec3 ld3(const float* p, uint32_t v)
-{
-    const float* q = p + 3 * (size_t)v;
-    return mk3(gld(q), gld(q + 1), gld(q + 2));
-}
 __device__ __forceinline__ void st3(float* p, uint32_t v, Vec3 a)
 {
     float* q = p + 3 * (size_t)v;
@@ -195,26 +190,15 @@ __global__ __launch_bounds__(PRT_DEFORM_BLOCK) void deform_sah_final_kernel(cons
 
 uint32_t blocks_of(uint32_t n) { return (n + PRT_DEFORM_BLOCK - 1) / PRT_DEFORM_BLOCK; }
 
-template <typename T>
-int scene_alloc(prt_hip_ctx* c, size_t count, T** out)
-{
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, std::max<size_t>(count * sizeof(T), 64)));
-    c->sceneAllocs.push_back(d);
-    *out = (T*)d;
-    return PRT_HIP_OK;
-}
-
-uint32_t sah_blocks_max(const prt_hip_ctx* c) { return (uint32_t)(c->rf.records / PRT_DEFORM_BLOCK + 1); }
+uint32_t sah_blocks_max(const prt_hip_ctx* c) { return (uint32_t)(c->arr.wnodes.size() / 4 / PRT_DEFORM_BLOCK + 1); } // (4 float4 per record)
 
 // the scratch arrays of this file (kept with the scene)
 int scratch_ready(prt_hip_ctx* c)
 {
     PrtRefit& R = c->rf;
-    int rc;
-    if (!R.vboxOut && (rc = scene_alloc(c, PRT_MAX_BVH * 6, &R.vboxOut))) return rc;
-    if (!R.boxPartial && (rc = scene_alloc(c, PRT_DEFORM_BOX_BLOCKS * 6, &R.boxPartial))) return rc;
-    if (!R.sahPartial && (rc = scene_alloc(c, 3 * ((size_t)sah_blocks_max(c) + 1), &R.sahPartial))) return rc; // (the last three: the sums)
+    if (!R.vboxOut) HIP_TRY(R.vboxOut.fit(PRT_MAX_BVH * 6, c->stream));
+    if (!R.boxPartial) HIP_TRY(R.boxPartial.fit(PRT_DEFORM_BOX_BLOCKS * 6, c->stream));
+    if (!R.sahPartial) HIP_TRY(R.sahPartial.fit(3 * ((size_t)sah_blocks_max(c) + 1), c->stream)); // (the last three: the sums)
     if (!R.vboxHost) HIP_TRY(hipHostMalloc((void**)&R.vboxHost, PRT_MAX_BVH * 6 * sizeof(float)));
     return PRT_HIP_OK;
 }
@@ -319,21 +303,15 @@ int csr_ready(prt_hip_ctx* c, uint32_t mesh)
     std::vector<uint32_t> cursor(off.begin(), off.end() - 1);
     for (uint32_t f = M.primCount; f-- > 0;) // mesh.cpp:112: faces descending, corners ascending
         for (int j = 0; j < 3; j++) face[cursor[idx[3 * (size_t)f + j]]++] = f;
-    uint32_t *dOff = nullptr, *dFace = nullptr, *dIdx = nullptr;
-    float* dFn = nullptr;
+    DevBuf<uint32_t> dOff, dFace, dIdx; // the mesh's only once all of it is on the device: a failure frees them here
+    DevBuf<float> dFn;
     int rc;
-    if ((rc = scene_alloc(c, off.size(), &dOff)) || (rc = scene_alloc(c, face.size(), &dFace)) || (rc = scene_alloc(c, idx.size(), &dIdx)) ||
-        (rc = scene_alloc(c, idx.size(), &dFn)))
-        return rc;
-    HIP_TRY(hipMemcpy(dOff, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    if (!idx.empty()) {
-        HIP_TRY(hipMemcpy(dFace, face.data(), face.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dIdx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-    }
-    M.csrFace = dFace;
-    M.faceVtx = dIdx;
-    M.faceNrm = dFn;
-    M.csrOff = dOff;
+    if ((rc = prt_upload(dOff, off, c->stream)) || (rc = prt_upload(dFace, face, c->stream)) || (rc = prt_upload(dIdx, idx, c->stream))) return rc;
+    HIP_TRY(dFn.fit(idx.size(), c->stream));
+    M.csrFace = std::move(dFace);
+    M.faceVtx = std::move(dIdx);
+    M.faceNrm = std::move(dFn);
+    M.csrOff = std::move(dOff);
     return PRT_HIP_OK;
 }
 
@@ -405,7 +383,7 @@ int queue_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, uint3
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = R.meshes[d[k].mesh];
         const bool given = d[k].normalsMode == PRT_HIP_NORMALS_GIVEN;
-        if ((rc = queue_box(c, d[k].mesh, src[k].pos, host ? nullptr : M.dPos, given ? src[k].nrm : nullptr, given && !host ? M.dNrm : nullptr, s))) return rc;
+        if ((rc = queue_box(c, d[k].mesh, src[k].pos, host ? nullptr : (float*)M.dPos, given ? src[k].nrm : nullptr, given && !host ? (float*)M.dNrm : nullptr, s))) return rc;
     }
     if (flags & PRT_HIP_DEFORM_RADIUS_AUTO) // meshes the host path changed since their box was taken
         for (uint32_t m = 0; m < R.meshes.size(); m++) {

@@ -11,6 +11,17 @@ public:
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    // Moving hands the memory over and leaves the source empty.  Assignment frees what the target held WITHOUT synchronising: as with
+    // release(), the caller answers for the stream that used that memory being idle.
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) {
+            release();
+            swap(o);
+        }
+        return *this;
+    }
     ~DevBuf() { release(); }
 
     operator T*() const { return p_; }
@@ -23,7 +34,7 @@ public:
         p_ = nullptr;
         n_ = 0;
     }
-    void swap(DevBuf& o) // the two exchange their memory (history and pending records, prt_temporal.hip)
+    void swap(DevBuf& o) noexcept // the two exchange their memory (history and pending records, prt_temporal.hip)
     {
         std::swap(p_, o.p_);
         std::swap(n_, o.n_);
@@ -44,7 +55,7 @@ private:
             release();
         }
         if (fresh) *fresh = true;
-        hipError_t e = hipMalloc((void**)&p_, n ? n * sizeof(T) : 16);
+        hipError_t e = hipMalloc((void**)&p_, n * sizeof(T) > 64 ? n * sizeof(T) : 64); // (never fewer than 64 bytes)
         if (e == hipSuccess) n_ = n;
         else p_ = nullptr;
         return e;

@@ -160,6 +160,11 @@ __device__ __forceinline__ uint32_t gld(const uint32_t* p) { return *(const PRT_
 __device__ __forceinline__ int32_t gld(const int32_t* p) { return *(const PRT_AS1 int32_t*)p; }
 __device__ __forceinline__ float gld(const float* p) { return *(const PRT_AS1 float*)p; }
 __device__ __forceinline__ uint32_t gld(const uint8_t* p) { return (uint32_t) * (const PRT_AS1 uint8_t*)p; }
+__device__ __forceinline__ Vec3 ld3(const float* p, uint32_t v) // triple v of an array of packed float triples (vertex positions, normals)
+{
+    const float* q = p + 3 * (size_t)v;
+    return mk3(gld(q), gld(q + 1), gld(q + 2));
+}
 __device__ __forceinline__ void gst(uint32_t* p, uint32_t v) { *(PRT_AS1 uint32_t*)p = v; }
 __device__ __forceinline__ void gst4(float4* p, float4 v)
 {

@@ -122,30 +122,25 @@ __global__ __launch_bounds__(PRT_EDIT_BLOCK) void alpha_class_kernel(const uint8
     words[i] = word;
 }
 
-// drops p from the scene's allocations and frees it
-void release_scene_alloc(prt_hip_ctx* c, const void* p)
-{
-    if (!p) return;
-    auto it = std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), (void*)p);
-    if (it != c->sceneAllocs.end()) c->sceneAllocs.erase(it);
-    (void)hipFree((void*)p);
-}
+struct EnvBuild { // the buffers of a new environment map, not yet the scene's
+    DevBuf<float4> texels;
+    DevBuf<float> vert, hor;
+    DevBuf<int32_t> firstX;
+    DevBuf<uint32_t> result; // {flags, envFirstY}
+};
 
-void release_env(prt_hip_ctx* c)
+// The scene's environment map becomes b's (an empty b: none), of W x H texels.  The old arrays are freed here: the stream is idle.
+void set_env(prt_hip_ctx* c, EnvBuild&& b, int32_t W, int32_t H, int32_t firstY)
 {
-    if (c->sc.hasEnv) {
-        release_scene_alloc(c, c->sc.envTexels);
-        release_scene_alloc(c, c->sc.envV);
-        release_scene_alloc(c, c->sc.envHor);
-        release_scene_alloc(c, c->sc.envFirstX);
-    }
-    c->sc.envTexels = nullptr;
-    c->sc.envV = nullptr;
-    c->sc.envHor = nullptr;
-    c->sc.envFirstX = nullptr;
-    c->sc.envW = c->sc.envH = 0;
-    c->sc.envFirstY = 0;
-    c->sc.hasEnv = 0;
+    c->sc.hasEnv = b.texels ? 1u : 0u;
+    c->arr.envTexels = std::move(b.texels);
+    c->arr.envV = std::move(b.vert);
+    c->arr.envHor = std::move(b.hor);
+    c->arr.envFirstX = std::move(b.firstX);
+    prt_scene_view(c);
+    c->sc.envW = W;
+    c->sc.envH = H;
+    c->sc.envFirstY = firstY;
 }
 
 // the samples of the old lights, materials or texels: accumulator, moments, estimator, history and pending record
@@ -155,33 +150,16 @@ void forget_radiance(prt_hip_ctx* c)
     c->tpHaveHist = c->tpHavePend = false;
 }
 
-struct EnvBuild { // the buffers of a new environment map, not yet the scene's
-    float4* texels = nullptr;
-    float* vert = nullptr;
-    float* hor = nullptr;
-    int32_t* firstX = nullptr;
-    uint32_t* result = nullptr; // {flags, envFirstY}
-    void release()
-    {
-        for (void* p : {(void*)texels, (void*)vert, (void*)hor, (void*)firstX, (void*)result})
-            if (p) (void)hipFree(p);
-        *this = EnvBuild{};
-    }
-};
-
-int env_alloc(EnvBuild& b, int32_t W, int32_t H)
+int env_alloc(EnvBuild& b, int32_t W, int32_t H, hipStream_t s)
 {
     const size_t n = (size_t)W * H;
-    auto get = [](void** p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 64)); }; // sizes as upload_vec's
-    hipError_t e = get((void**)&b.texels, n * sizeof(float4));
-    if (e == hipSuccess) e = get((void**)&b.vert, (size_t)H * sizeof(float));
-    if (e == hipSuccess) e = get((void**)&b.hor, n * sizeof(float));
-    if (e == hipSuccess) e = get((void**)&b.firstX, (size_t)H * sizeof(int32_t));
-    if (e == hipSuccess) e = get((void**)&b.result, 64);
-    if (e != hipSuccess) {
-        b.release();
+    hipError_t e = b.texels.fit(n, s);
+    if (e == hipSuccess) e = b.vert.fit((size_t)H, s);
+    if (e == hipSuccess) e = b.hor.fit(n, s);
+    if (e == hipSuccess) e = b.firstX.fit((size_t)H, s);
+    if (e == hipSuccess) e = b.result.fit(16, s);
+    if (e != hipSuccess) // (what was allocated goes with b)
         return fail(e == hipErrorOutOfMemory ? PRT_HIP_ENOMEM : PRT_HIP_ENODEVICE, std::string("environment light buffers: ") + hipGetErrorString(e));
-    }
     return PRT_HIP_OK;
 }
 
@@ -244,9 +222,9 @@ int check_materials(prt_hip_ctx* c, uint32_t count, const prt_material_update* u
         if (v.diffuseMap >= textures || v.bumpMap >= textures) return fail(PRT_HIP_EINVAL, which + "material texture index out of range");
         if (was.alphaTest && v.diffuseMap != was.diffuseMap)
             return fail(PRT_HIP_EINVAL, which + "another diffuseMap for a material uploaded with alphaTest (its alpha records are fixed at upload)");
-        if (v.bumpMap >= 0 && !E.anyBump) return fail(PRT_HIP_EINVAL, which + "bumpMap in a scene uploaded without bump-mapped materials (it has no bump records)");
+        if (v.bumpMap >= 0 && !c->arr.anyBump()) return fail(PRT_HIP_EINVAL, which + "bumpMap in a scene uploaded without bump-mapped materials (it has no bump records)");
         if (v.reflectionType > 2u) return fail(PRT_HIP_EINVAL, which + "reflectionType must be 0, 1 or 2");
-        if ((uint64_t)M.matBase + u[k].material >= E.matRecords) return fail(PRT_HIP_EINVAL, which + "internal: material record outside the table");
+        if ((uint64_t)M.matBase + u[k].material >= c->arr.mats.size() / PRT_MAT_STRIDE) return fail(PRT_HIP_EINVAL, which + "internal: material record outside the table");
     }
     return PRT_HIP_OK;
 }
@@ -268,9 +246,9 @@ int check_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u)
         for (uint32_t j = 0; j < k; j++)
             if (u[j].texture == u[k].texture) return fail(PRT_HIP_EINVAL, which + "texture " + std::to_string(u[k].texture) + " is named twice in one call");
         const uint64_t bytes = (uint64_t)d.y * d.z * d.w, words = ((uint64_t)d.y * d.z + 15) / 16;
-        if ((uint64_t)d.x + bytes > E.texelBytes) return fail(PRT_HIP_EINVAL, which + "internal: texture outside the texel array");
+        if ((uint64_t)d.x + bytes > c->arr.texels.size()) return fail(PRT_HIP_EINVAL, which + "internal: texture outside the texel array");
         const uint32_t first = E.classWordOf[u[k].texture];
-        if (first != 0xffffffffu && (uint64_t)first + words > E.classWords) return fail(PRT_HIP_EINVAL, which + "internal: class words outside their array");
+        if (first != 0xffffffffu && (uint64_t)first + words > c->arr.alphaClass.size()) return fail(PRT_HIP_EINVAL, which + "internal: class words outside their array");
     }
     return PRT_HIP_OK;
 }
@@ -279,7 +257,7 @@ int check_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u)
 int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, hipStream_t s, hipEvent_t* ev)
 {
     const PrtEdit& E = c->ed;
-    uint8_t* texels = const_cast<uint8_t*>(c->sc.texels);
+    uint8_t* texels = c->arr.texels;
     for (uint32_t k = 0; k < count; k++) {
         const uint4 d = E.texDesc[u[k].texture];
         HIP_TRY(hipMemcpyAsync(texels + d.x, u[k].texels, (size_t)d.y * d.z * d.w, hipMemcpyHostToDevice, s));
@@ -291,7 +269,7 @@ int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, 
         const uint4 d = E.texDesc[u[k].texture];
         const uint32_t words = (uint32_t)(((uint64_t)d.y * d.z + 15) / 16);
         hipLaunchKernelGGL(alpha_class_kernel, dim3((words + PRT_EDIT_BLOCK - 1) / PRT_EDIT_BLOCK), dim3(PRT_EDIT_BLOCK), 0, s, texels + d.x, (int32_t)d.y,
-                           (int32_t)d.z, (int32_t)d.w, const_cast<uint32_t*>(c->sc.alphaClass) + first, words);
+                           (int32_t)d.z, (int32_t)d.w, c->arr.alphaClass + first, words);
         int rc = prt_launched("alpha_class_kernel");
         if (rc) return rc;
     }
@@ -312,7 +290,7 @@ int prt_hip_update_lights(prt_hip_ctx* c, const prt_light_update* u, void* strea
     if (u->envMode == PRT_HIP_ENV_REPLACE) {
         const int32_t W = u->envWidth, H = u->envHeight;
         EnvBuild b; // NEW buffers: a refused map leaves the scene's own untouched
-        if ((rc = env_alloc(b, W, H))) return rc;
+        if ((rc = env_alloc(b, W, H, s))) return rc;
         uint32_t result[2] = {0u, 0u};
         hipError_t e = hipSuccess;
         if ((rc = prt_stream_enter(c, stream, &caller)) == PRT_HIP_OK && (rc = env_queue(b, W, H, u->envTexels, s, nullptr)) == PRT_HIP_OK) {
@@ -323,25 +301,14 @@ int prt_hip_update_lights(prt_hip_ctx* c, const prt_light_update* u, void* strea
         if (rc == PRT_HIP_OK && e != hipSuccess) rc = fail(PRT_HIP_ENODEVICE, std::string("environment light build: ") + hipGetErrorString(e));
         if (rc == PRT_HIP_OK) rc = env_refusal(result[0]);
         if (rc) {
-            (void)hipStreamSynchronize(s);
-            b.release();
+            (void)hipStreamSynchronize(s); // then b's buffers go with it
             return rc;
         }
-        release_env(c); // (the stream is idle: no launch still reads the old buffers)
-        for (void* p : {(void*)b.texels, (void*)b.vert, (void*)b.hor, (void*)b.firstX}) c->sceneAllocs.push_back(p);
-        (void)hipFree(b.result);
-        c->sc.envTexels = b.texels;
-        c->sc.envV = b.vert;
-        c->sc.envHor = b.hor;
-        c->sc.envFirstX = b.firstX;
-        c->sc.envW = W;
-        c->sc.envH = H;
-        c->sc.envFirstY = (int32_t)result[1];
-        c->sc.hasEnv = 1;
+        set_env(c, std::move(b), W, H, (int32_t)result[1]); // (the stream is idle: no launch still reads the old buffers)
     } else if (u->envMode == PRT_HIP_ENV_NONE && c->sc.hasEnv) {
         if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = prt_stream_leave(c, caller))) return rc;
         HIP_TRY(hipStreamSynchronize(s)); // launches queued before the call still read the buffers
-        release_env(c);
+        set_env(c, EnvBuild{}, 0, 0, 0);
     }
     c->sc.hasLight = u->hasDirectionalLight ? 1u : 0u;
     memcpy(c->sc.lightDir, u->lightDir, 12);
@@ -359,7 +326,7 @@ int prt_hip_update_materials(prt_hip_ctx* c, uint32_t count, const prt_material_
     for (uint32_t k = 0; k < count; k++) prt_material_record(updates[k].value, c->ed.texDesc, &records[(size_t)k * PRT_MAT_STRIDE]);
     hipStream_t s = c->stream, caller;
     if ((rc = prt_stream_enter(c, stream, &caller))) return rc;
-    float4* mats = const_cast<float4*>(c->sc.mats);
+    float4* mats = c->arr.mats;
     for (uint32_t k = 0; k < count; k++) {
         const size_t at = ((size_t)c->ed.meshes[updates[k].mesh].matBase + updates[k].material) * PRT_MAT_STRIDE;
         HIP_TRY(hipMemcpyAsync(mats + at, &records[(size_t)k * PRT_MAT_STRIDE], PRT_MAT_STRIDE * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -394,19 +361,19 @@ int prt_hip_test_shading_arrays(prt_hip_ctx* c, uint64_t counts[5], float* mats,
 {
     if (!c || !counts) return fail(PRT_HIP_EINVAL, "NULL argument");
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
-    const PrtEdit& E = c->ed;
+    const PrtSceneArrays& A = c->arr;
     const DevScene& sc = c->sc;
-    counts[0] = E.matRecords;
-    counts[1] = E.classWords;
-    counts[2] = E.texelBytes;
+    counts[0] = A.mats.size() / PRT_MAT_STRIDE;
+    counts[1] = A.alphaClass.size();
+    counts[2] = A.texels.size();
     counts[3] = sc.hasEnv ? (uint64_t)sc.envW : 0;
     counts[4] = sc.hasEnv ? (uint64_t)sc.envH : 0;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t n = (size_t)counts[3] * counts[4];
-    if (mats && E.matRecords) HIP_TRY(hipMemcpy(mats, sc.mats, E.matRecords * PRT_MAT_STRIDE * sizeof(float4), hipMemcpyDeviceToHost));
-    if (alphaClass && E.classWords) HIP_TRY(hipMemcpy(alphaClass, sc.alphaClass, E.classWords * 4, hipMemcpyDeviceToHost));
-    if (texels && E.texelBytes) HIP_TRY(hipMemcpy(texels, sc.texels, E.texelBytes, hipMemcpyDeviceToHost));
+    if (mats && counts[0]) HIP_TRY(hipMemcpy(mats, sc.mats, counts[0] * PRT_MAT_STRIDE * sizeof(float4), hipMemcpyDeviceToHost));
+    if (alphaClass && counts[1]) HIP_TRY(hipMemcpy(alphaClass, sc.alphaClass, counts[1] * 4, hipMemcpyDeviceToHost));
+    if (texels && counts[2]) HIP_TRY(hipMemcpy(texels, sc.texels, counts[2], hipMemcpyDeviceToHost));
     if (envTexels && n) HIP_TRY(hipMemcpy(envTexels, sc.envTexels, n * sizeof(float4), hipMemcpyDeviceToHost));
     if (envVertical && n) HIP_TRY(hipMemcpy(envVertical, sc.envV, (size_t)counts[4] * 4, hipMemcpyDeviceToHost));
     if (envHorizontal && n) HIP_TRY(hipMemcpy(envHorizontal, sc.envHor, n * 4, hipMemcpyDeviceToHost));
@@ -468,7 +435,7 @@ int prt_hip_test_edit_profile(prt_hip_ctx* c, uint32_t count, const prt_texture_
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
     std::vector<float> env, cls;
     EnvBuild b;
-    if (c->sc.hasEnv) rc = env_alloc(b, c->sc.envW, c->sc.envH);
+    if (c->sc.hasEnv) rc = env_alloc(b, c->sc.envW, c->sc.envH, c->stream);
     for (uint32_t r = 0; r < reps && rc == PRT_HIP_OK; r++) {
         float a = 0.0f, d = 0.0f;
         if (c->sc.hasEnv) {
@@ -486,8 +453,7 @@ int prt_hip_test_edit_profile(prt_hip_ctx* c, uint32_t count, const prt_texture_
         env.push_back(a);
         cls.push_back(d);
     }
-    (void)hipStreamSynchronize(c->stream);
-    b.release();
+    (void)hipStreamSynchronize(c->stream); // b's buffers go at the end of the scope
     for (auto& e : ev) (void)hipEventDestroy(e);
     if (rc) return rc;
     std::sort(env.begin(), env.end());

@@ -44,15 +44,15 @@ struct PrtRefitMesh {
     uint32_t primCount = 0;               // triangles of the mesh (slotCount minus the pad slots): the range of a caller's primId (prt_query.hip)
     uint32_t rootKid = 0;                 // the root as a kid word (see PrtRefit::kids)
     std::vector<std::pair<uint32_t, uint32_t>> levels; // per depth (root's record first): {first entry in levelList, entries}
-    float* dPos = nullptr;                // staging of the caller's positions / normals (3 * vertexCount floats), allocated by the first update
-    float* dNrm = nullptr;
+    DevBuf<float> dPos;                   // staging of the caller's positions / normals (3 * vertexCount floats), allocated by the first update
+    DevBuf<float> dNrm;
     // device-side deformation (prt_deform.hip)
     float vbox[6] = {};                   // Mesh::calculateBounds of the current positions (lower, upper), over ALL vertices
     bool vboxValid = false;               // false after prt_hip_update_meshes: reduced from dPos when next needed
-    uint32_t* csrOff = nullptr;           // incidence list, built by the first PRT_HIP_NORMALS_RECOMPUTE: vertexCount + 1 offsets,
-    uint32_t* csrFace = nullptr;          // one face per corner (faces descending, corners ascending within a face),
-    uint32_t* faceVtx = nullptr;          // the index buffer (3 per face, mesh order) and
-    float* faceNrm = nullptr;             // the face normals of the last recompute (3 per face)
+    DevBuf<uint32_t> csrOff;              // incidence list, built by the first PRT_HIP_NORMALS_RECOMPUTE: vertexCount + 1 offsets,
+    DevBuf<uint32_t> csrFace;             // one face per corner (faces descending, corners ascending within a face),
+    DevBuf<uint32_t> faceVtx;             // the index buffer (3 per face, mesh order) and
+    DevBuf<float> faceNrm;                // the face normals of the last recompute (3 per face)
     bool sahCaptured = false;             // sahUpload holds {internalArea, leafArea, rootArea} of the tree as uploaded
     double sahUpload[3] = {};
 };
@@ -64,22 +64,20 @@ struct PrtRefitSrc {
 };
 struct PrtRefit {
     std::vector<PrtRefitMesh> meshes;
-    uint32_t* slotVtx = nullptr;   // 3 vertex ids (within the mesh) per triangle slot; 0xffffffff in a pad slot
-    uint2* kids = nullptr;         // per wide record: its two children -- a leaf reference as the record holds it, or the child's own
+    DevBuf<uint32_t> slotVtx;      // 3 vertex ids (within the mesh) per triangle slot; 0xffffffff in a pad slot
+    DevBuf<uint2> kids;            // per wide record: its two children -- a leaf reference as the record holds it, or the child's own
                                    // record index (a PRT_REF_HOT reference resolved)
-    uint32_t* levelList = nullptr; // record indices by mesh and depth (PrtRefitMesh::levels)
-    uint32_t* hotOrder = nullptr;  // record index of every hot slot
+    DevBuf<uint32_t> levelList;    // record indices by mesh and depth (PrtRefitMesh::levels)
+    DevBuf<uint32_t> hotOrder;     // record index of every hot slot
     uint32_t hotCount = 0;
-    uint64_t records = 0, slots = 0;
-    bool anyBump = false;
-    float* rootOut = nullptr;      // device: PRT_MAX_BVH x 6 floats, the refitted root boxes
-    float* rootHost = nullptr;     // pinned host copy of it
+    DevBuf<float> rootOut;         // device: PRT_MAX_BVH x 6 floats, the refitted root boxes
+    float* rootHost = nullptr;     // pinned host copy of it (freed by prt_refit_forget, like vboxHost)
     // prt_deform.hip, allocated on first use: the vertex boxes of a call (PRT_MAX_BVH x 6 floats), their pinned host copy, and the
     // per-block partials of the box and SAH reductions
-    float* vboxOut = nullptr;
+    DevBuf<float> vboxOut;
     float* vboxHost = nullptr;
-    float* boxPartial = nullptr;
-    double* sahPartial = nullptr;
+    DevBuf<float> boxPartial;
+    DevBuf<double> sahPartial;
 };
 
 // Scene edits (prt_edit.hip): what the checks of prt_hip_update_materials / prt_hip_update_textures need from the upload, kept on the host.
@@ -91,8 +89,22 @@ struct PrtEdit {
     std::vector<PrtEditMesh> meshes;
     std::vector<uint4> texDesc;        // per texture: {offset in DevScene::texels, width, height, component}
     std::vector<uint32_t> classWordOf; // per texture: first word of its alpha cell classes, 0xffffffff = none were built
-    uint64_t matRecords = 0, classWords = 0, texelBytes = 0; // sizes of DevScene::mats (records), alphaClass (words), texels (bytes)
-    bool anyBump = false;              // the scene has bump records
+};
+
+// The owners of the arrays DevScene points to (prt_device.h), under the names it gives them.  DevScene is the by-value kernel argument,
+// a read-only view; host code that rewrites an array in place takes the pointer from here, and an array's size is its size().
+struct PrtSceneArrays {
+    DevBuf<float4> wnodes, hotNodes;
+    DevBuf<float> tris;
+    DevBuf<uint32_t> triAlpha, triPrim;
+    DevBuf<float4> shade, bump, mats, alpha; // bump holds records exactly when some material of the scene names a bump map
+    DevBuf<uint32_t> alphaClass;
+    DevBuf<uint4> texDesc;
+    DevBuf<uint8_t> texels;
+    DevBuf<float4> envTexels; // the four of the environment light: empty without one
+    DevBuf<float> envV, envHor;
+    DevBuf<int32_t> envFirstX;
+    bool anyBump() const { return bump.size() != 0; }
 };
 
 struct prt_hip_ctx {
@@ -111,8 +123,8 @@ struct prt_hip_ctx {
     bool haveScene = false, haveCamera = false;
     DevScene sc{};
     DevCamera cam{};
-    std::vector<void*> sceneAllocs;
-    PrtRefit rf;                // device allocations of it are in sceneAllocs
+    PrtSceneArrays arr;         // sc's pointers are prt_scene_view's copies of these
+    PrtRefit rf;
     PrtEdit ed;
     // render resources.  Every device buffer of the context is a DevBuf (prt_devbuf.h): it is freed with the context, and a (re)allocation
     // synchronises the context's stream before the old memory goes.
@@ -219,6 +231,16 @@ int prt_batch_end(prt_hip_ctx* c, const BatchLaunch& L, const char* kernel);
 int prt_frame_probe(prt_hip_ctx* c, uint32_t n, const prt_ray* d_rays, const prt_render_params* p, float* d_radiance);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
+// prt_upload.hip, the ONE place that writes a pointer of c->sc: each from its owner in c->arr (null where the owner is empty).  Called
+// when owners have changed: the upload, an environment map handed over or removed (prt_edit.hip), prt_free_scene.
+void prt_scene_view(prt_hip_ctx* c);
+// v on the device in b, which holds exactly v.size() elements afterwards (synchronous; `stream` as for DevBuf::fit)
+template <typename T> int prt_upload(DevBuf<T>& b, const std::vector<T>& v, hipStream_t stream)
+{
+    HIP_TRY(b.fit(v.size(), stream));
+    if (!v.empty()) HIP_TRY(hipMemcpy(b, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PRT_HIP_OK;
+}
 // The ONE place that writes a material record (prt_hip_upload_scene, prt_hip_update_materials); its size is tied to the stride the
 // kernels index with (sample_diffuse, sample_bump, shade_kernel: sc.mats + PRT_MAT_STRIDE * material).  A record count and an index
 // stride that disagree read another material's fields as texture descriptors -- a wild texel address on the device.  texDesc: per
@@ -249,7 +271,7 @@ inline void prt_accum_forget(prt_hip_ctx* c)
 // references in place), the record of every hot slot, and per mesh its slot range, vertex count and root reference
 // (PrtRefitMesh::rootKid = DevScene::rootRef on entry); prt_refit_forget drops the state with the scene
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
-                    const std::vector<uint32_t>& slotVtx, bool anyBump);
+                    const std::vector<uint32_t>& slotVtx);
 void prt_refit_forget(prt_hip_ctx* c);
 // prt_refit.hip, shared with prt_hip_deform_meshes (prt_deform.hip): every refusal of prt_hip_update_meshes; the staging buffers of the
 // named meshes (normals too where `normals` is set); gather, levels and finish of the named meshes queued on s, reading device

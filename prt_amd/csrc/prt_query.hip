@@ -226,23 +226,24 @@ int inverse_ready(prt_hip_ctx* c)
 {
     if (c->qInv) return PRT_HIP_OK;
     const PrtRefit& R = c->rf;
-    if (R.slots == 0 || R.slots > 0xffffffffull || !R.slotVtx || R.meshes.size() != c->sc.bvhCount)
+    const uint64_t slots = R.slotVtx.size() / 3;
+    if (slots == 0 || slots > 0xffffffffull || !R.slotVtx || R.meshes.size() != c->sc.bvhCount)
         return fail(PRT_HIP_ESTATE, "query_surface: the scene holds no triangle slots");
     IndexArgs a{};
     a.triPrim = c->sc.triPrim;
     a.slotVtx = R.slotVtx;
-    a.slots = (uint32_t)R.slots;
+    a.slots = (uint32_t)slots;
     a.meshes = c->sc.bvhCount;
     for (uint32_t m = 0; m < a.meshes; m++) {
         const PrtRefitMesh& rm = R.meshes[m];
-        if ((uint64_t)rm.slotBase + rm.slotCount > R.slots || rm.slotBase != c->sc.primBase[m])
+        if ((uint64_t)rm.slotBase + rm.slotCount > slots || rm.slotBase != c->sc.primBase[m])
             return fail(PRT_HIP_ESTATE, "query_surface: slot range outside the scene");
         a.slotBase[m] = rm.slotBase;
         a.slotCount[m] = rm.slotCount;
     }
-    HIP_TRY(c->qInv.fit(R.slots, c->stream));
+    HIP_TRY(c->qInv.fit(slots, c->stream));
     a.inv = c->qInv;
-    HIP_TRY(hipMemsetAsync(c->qInv, 0xff, R.slots * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->qInv, 0xff, slots * sizeof(uint32_t), c->stream));
     const uint32_t blocks = std::min<uint32_t>((a.slots + 255u) / 256u, 65535u);
     hipLaunchKernelGGL(query_index_kernel, dim3(blocks), dim3(256), 0, c->stream, a);
     return prt_launched("query_index_kernel");

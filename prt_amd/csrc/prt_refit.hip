@@ -44,11 +44,6 @@ struct GatherArgs {
     uint32_t faceNormals; // the mesh has no vertex normals: n0 is the face normal
 };
 
-__device__ __forceinline__ Vec3 ld3(const float* p, uint32_t v)
-{
-    const float* q = p + 3 * (size_t)v;
-    return mk3(gld(q), gld(q + 1), gld(q + 2));
-}
 __device__ __forceinline__ void st3(float4* rec, Vec3 v) // the first three floats of a record; the fourth is not positional
 {
     float* q = (float*)rec;
@@ -159,17 +154,6 @@ __global__ __launch_bounds__(PRT_REFIT_BLOCK) void refit_finish_kernel(RootArgs 
     }
 }
 
-template <typename T>
-int upload_array(prt_hip_ctx* c, const std::vector<T>& v, T** out)
-{
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, std::max<size_t>(v.size() * sizeof(T), 64)));
-    c->sceneAllocs.push_back(d);
-    if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = (T*)d;
-    return PRT_HIP_OK;
-}
-
 // Queues the copies of the caller's host arrays into the staging buffers, then the refit reading them (prt_refit_queue).
 int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipStream_t s, hipEvent_t* ev)
 {
@@ -181,7 +165,7 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
         HIP_TRY(hipMemcpyAsync(M.dPos, u[k].positions, bytes, hipMemcpyHostToDevice, s));
         if (u[k].normals) HIP_TRY(hipMemcpyAsync(M.dNrm, u[k].normals, bytes, hipMemcpyHostToDevice, s));
         M.vboxValid = false; // (the vertex box of the staged copy is reduced when a later call asks for it: prt_deform.hip)
-        src[k] = PrtRefitSrc{u[k].mesh, M.dPos, u[k].normals ? M.dNrm : nullptr};
+        src[k] = PrtRefitSrc{u[k].mesh, M.dPos, u[k].normals ? (float*)M.dNrm : nullptr};
     }
     return prt_refit_queue(c, count, src, s, ev);
 }
@@ -191,14 +175,14 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
 int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStream_t s, hipEvent_t* ev)
 {
     PrtRefit& R = c->rf;
-    float* tris = const_cast<float*>(c->sc.tris);
-    float4* wnodes = const_cast<float4*>(c->sc.wnodes);
+    PrtSceneArrays& A = c->arr; // the writable pointers are the owners'
+    float* tris = A.tris;
+    float4* wnodes = A.wnodes;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = R.meshes[u[k].mesh];
         if (M.slotCount == 0) continue;
-        GatherArgs g{R.slotVtx, u[k].pos, u[k].nrm, tris, const_cast<float4*>(c->sc.shade),
-                     R.anyBump ? const_cast<float4*>(c->sc.bump) : nullptr, M.slotBase, M.slotCount, M.hasNormals ? 0u : 1u};
+        GatherArgs g{R.slotVtx, u[k].pos, u[k].nrm, tris, A.shade, A.anyBump() ? (float4*)A.bump : nullptr, M.slotBase, M.slotCount, M.hasNormals ? 0u : 1u};
         hipLaunchKernelGGL(refit_gather_kernel, dim3((M.slotCount + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, g);
         int rc = prt_launched("refit_gather_kernel");
         if (rc) return rc;
@@ -220,7 +204,7 @@ int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStr
     }
     const uint32_t lanes = std::max<uint32_t>(ra.count, 3u * R.hotCount);
     hipLaunchKernelGGL(refit_finish_kernel, dim3((lanes + PRT_REFIT_BLOCK - 1) / PRT_REFIT_BLOCK), dim3(PRT_REFIT_BLOCK), 0, s, ra, tris, wnodes, R.rootOut,
-                       R.hotOrder, R.hotCount, const_cast<float4*>(c->sc.hotNodes));
+                       R.hotOrder, R.hotCount, A.hotNodes);
     int rc = prt_launched("refit_finish_kernel");
     if (rc) return rc;
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
@@ -254,19 +238,9 @@ int prt_refit_staging(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u)
 {
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = c->rf.meshes[u[k].mesh];
-        const size_t bytes = std::max<size_t>((size_t)M.vertexCount * 3 * sizeof(float), 64);
-        if (!M.dPos) {
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, bytes));
-            c->sceneAllocs.push_back(d);
-            M.dPos = (float*)d;
-        }
-        if (u[k].normals && !M.dNrm) {
-            void* d = nullptr;
-            HIP_TRY(hipMalloc(&d, bytes));
-            c->sceneAllocs.push_back(d);
-            M.dNrm = (float*)d;
-        }
+        const size_t floats = (size_t)M.vertexCount * 3;
+        if (!M.dPos) HIP_TRY(M.dPos.fit(floats, c->stream));
+        if (u[k].normals && !M.dNrm) HIP_TRY(M.dNrm.fit(floats, c->stream));
     }
     return PRT_HIP_OK;
 }
@@ -289,27 +263,25 @@ void prt_refit_commit(prt_hip_ctx* c, uint32_t count, const uint32_t* meshes, fl
 }
 
 int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std::vector<uint32_t>& hotOrder, std::vector<PrtRefitMesh>&& meshes,
-                    const std::vector<uint32_t>& slotVtx, bool anyBump)
+                    const std::vector<uint32_t>& slotVtx)
 {
     PrtRefit& R = c->rf;
     R = PrtRefit{};
     R.meshes = std::move(meshes);
-    R.records = wnodes.size() / 4;
-    R.slots = slotVtx.size() / 3;
-    R.anyBump = anyBump;
+    const size_t records = wnodes.size() / 4;
     R.hotCount = (uint32_t)hotOrder.size();
     auto bitsOf = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
     auto resolve = [&](uint32_t ref) -> uint32_t {
         if (ref & PRT_REF_LEAF) return ref;
         return (ref & PRT_REF_HOT) ? hotOrder[ref & (PRT_HOT_NODES - 1u)] : ref;
     };
-    std::vector<uint2> kids(R.records);
-    for (size_t r = 0; r < R.records; r++) {
+    std::vector<uint2> kids(records);
+    for (size_t r = 0; r < records; r++) {
         const float4& refs = wnodes[r * 4 + 3];
         kids[r] = make_uint2(resolve(bitsOf(refs.x)), resolve(bitsOf(refs.y)));
     }
     std::vector<uint32_t> levelList;
-    levelList.reserve(R.records);
+    levelList.reserve(records);
     for (PrtRefitMesh& M : R.meshes) {
         M.rootKid = resolve(M.rootKid);
         std::vector<uint32_t> level, next;
@@ -324,16 +296,13 @@ int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std
             level.swap(next);
         }
     }
-    if (levelList.size() != R.records) return fail(PRT_HIP_EINVAL, "internal: the wide records are not the trees of the scene's roots");
+    if (levelList.size() != records) return fail(PRT_HIP_EINVAL, "internal: the wide records are not the trees of the scene's roots");
     int rc;
-    if ((rc = upload_array(c, slotVtx, &R.slotVtx))) return rc;
-    if ((rc = upload_array(c, kids, &R.kids))) return rc;
-    if ((rc = upload_array(c, levelList, &R.levelList))) return rc;
-    if ((rc = upload_array(c, hotOrder, &R.hotOrder))) return rc;
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, PRT_MAX_BVH * 6 * sizeof(float)));
-    c->sceneAllocs.push_back(d);
-    R.rootOut = (float*)d;
+    if ((rc = prt_upload(R.slotVtx, slotVtx, c->stream))) return rc;
+    if ((rc = prt_upload(R.kids, kids, c->stream))) return rc;
+    if ((rc = prt_upload(R.levelList, levelList, c->stream))) return rc;
+    if ((rc = prt_upload(R.hotOrder, hotOrder, c->stream))) return rc;
+    HIP_TRY(R.rootOut.fit(PRT_MAX_BVH * 6, c->stream));
     HIP_TRY(hipHostMalloc((void**)&R.rootHost, PRT_MAX_BVH * 6 * sizeof(float)));
     return PRT_HIP_OK;
 }
@@ -342,7 +311,7 @@ void prt_refit_forget(prt_hip_ctx* c)
 {
     if (c->rf.rootHost) (void)hipHostFree(c->rf.rootHost);
     if (c->rf.vboxHost) (void)hipHostFree(c->rf.vboxHost);
-    c->rf = PrtRefit{}; // (the device arrays went with sceneAllocs)
+    c->rf = PrtRefit{}; // (the device arrays go with their DevBufs)
 }
 
 extern "C" {
@@ -376,19 +345,20 @@ int prt_hip_test_scene_arrays(prt_hip_ctx* c, uint64_t counts[5], float* wnodes,
 {
     if (!c || !counts) return fail(PRT_HIP_EINVAL, "NULL argument");
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
-    const PrtRefit& R = c->rf;
-    counts[0] = R.records;
+    const PrtSceneArrays& A = c->arr;
+    const uint64_t records = A.wnodes.size() / 4, slots = c->rf.slotVtx.size() / 3;
+    counts[0] = records;
     counts[1] = PRT_HOT_NODES;
-    counts[2] = R.slots;
-    counts[3] = R.anyBump ? R.slots : 0;
+    counts[2] = slots;
+    counts[3] = A.anyBump() ? slots : 0;
     counts[4] = c->sc.bvhCount;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (wnodes && R.records) HIP_TRY(hipMemcpy(wnodes, c->sc.wnodes, R.records * 64, hipMemcpyDeviceToHost));
-    if (hot) HIP_TRY(hipMemcpy(hot, c->sc.hotNodes, (size_t)PRT_HOT_NODES * 64, hipMemcpyDeviceToHost));
-    if (tris && R.slots) HIP_TRY(hipMemcpy(tris, c->sc.tris, R.slots * 36, hipMemcpyDeviceToHost));
-    if (shade && R.slots) HIP_TRY(hipMemcpy(shade, c->sc.shade, R.slots * 64, hipMemcpyDeviceToHost));
-    if (bump && counts[3]) HIP_TRY(hipMemcpy(bump, c->sc.bump, R.slots * 48, hipMemcpyDeviceToHost));
+    if (wnodes && records) HIP_TRY(hipMemcpy(wnodes, A.wnodes, records * 64, hipMemcpyDeviceToHost));
+    if (hot) HIP_TRY(hipMemcpy(hot, A.hotNodes, (size_t)PRT_HOT_NODES * 64, hipMemcpyDeviceToHost));
+    if (tris && slots) HIP_TRY(hipMemcpy(tris, A.tris, slots * 36, hipMemcpyDeviceToHost));
+    if (shade && slots) HIP_TRY(hipMemcpy(shade, A.shade, slots * 64, hipMemcpyDeviceToHost));
+    if (bump && counts[3]) HIP_TRY(hipMemcpy(bump, A.bump, slots * 48, hipMemcpyDeviceToHost));
     if (rootBoxes) memcpy(rootBoxes, c->sc.rootBox, sizeof(c->sc.rootBox));
     if (radius) *radius = c->sc.radius;
     return PRT_HIP_OK;

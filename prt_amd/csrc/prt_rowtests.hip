@@ -319,7 +319,7 @@ int prt_hip_test_taps(prt_hip_ctx* c, uint32_t n, const uint32_t* records, int c
     if (!c || !records || !out || n == 0) return fail(PRT_HIP_EINVAL, "bad argument");
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, "upload a scene first");
     // every address the kernel forms is checked here: the material exists, the flavours asked for have their maps and class words
-    std::vector<const prt_material*> matOf(c->ed.matRecords, nullptr);
+    std::vector<const prt_material*> matOf(c->arr.mats.size() / PRT_MAT_STRIDE, nullptr);
     for (const PrtEditMesh& m : c->ed.meshes)
         for (size_t k = 0; k < m.materials.size(); k++)
             if (m.matBase + k < matOf.size()) matOf[m.matBase + k] = &m.materials[k];
@@ -358,7 +358,7 @@ int prt_hip_test_surface(prt_hip_ctx* c, uint32_t n, const uint32_t* records, in
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     // mesh-order primId -> triangle slot, from the arrays the upload left on the device (a pad slot names no vertices)
-    const size_t slots = (size_t)c->rf.slots;
+    const size_t slots = c->rf.slotVtx.size() / 3;
     std::vector<uint32_t> triPrim(slots), slotVtx(3 * slots);
     if (slots) {
         HIP_TRY(hipMemcpy(triPrim.data(), c->sc.triPrim, slots * 4, hipMemcpyDeviceToHost));
@@ -384,7 +384,7 @@ int prt_hip_test_surface(prt_hip_ctx* c, uint32_t n, const uint32_t* records, in
     HIP_TRY(dout.fit((size_t)n * 20, c->stream));
     HIP_TRY(hipMemcpy(din, rec.data(), (size_t)n * 20, hipMemcpyHostToDevice));
     blocks = row_blocks(n, blocks);
-    const uint32_t anyBump = c->ed.anyBump ? 1u : 0u;
+    const uint32_t anyBump = c->arr.anyBump() ? 1u : 0u;
     if (counting) hipLaunchKernelGGL(surface_kernel<true>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din, dout);
     else hipLaunchKernelGGL(surface_kernel<false>, dim3(blocks), dim3(256), 0, c->stream, c->sc, anyBump, n, din, dout);
     int rc = prt_launched("surface_kernel");

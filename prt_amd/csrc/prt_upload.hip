@@ -33,25 +33,35 @@ inline float ubits(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
 } // namespace
 
-template <typename T>
-static int upload_vec(prt_hip_ctx* c, const std::vector<T>& v, const T** out)
+void prt_scene_view(prt_hip_ctx* c)
 {
-    void* d = nullptr;
-    size_t bytes = std::max<size_t>(v.size() * sizeof(T), 64);
-    HIP_TRY(hipMalloc(&d, bytes));
-    c->sceneAllocs.push_back(d);
-    if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = (const T*)d;
-    return PRT_HIP_OK;
+    const PrtSceneArrays& a = c->arr;
+    DevScene& sc = c->sc;
+    sc.wnodes = a.wnodes;
+    sc.hotNodes = a.hotNodes;
+    sc.tris = a.tris;
+    sc.triAlpha = a.triAlpha;
+    sc.triPrim = a.triPrim;
+    sc.shade = a.shade;
+    sc.bump = a.bump;
+    sc.mats = a.mats;
+    sc.alpha = a.alpha;
+    sc.alphaClass = a.alphaClass;
+    sc.texDesc = a.texDesc;
+    sc.texels = a.texels;
+    sc.envTexels = a.envTexels;
+    sc.envV = a.envV;
+    sc.envHor = a.envHor;
+    sc.envFirstX = a.envFirstX;
 }
 
 void prt_free_scene(prt_hip_ctx* c)
 {
-    for (void* p : c->sceneAllocs) (void)hipFree(p);
-    c->sceneAllocs.clear();
+    c->arr = PrtSceneArrays{};
     prt_refit_forget(c);
     c->qInv.release(); // the inverse triangle table is the scene's (prt_query.hip)
     c->ed = PrtEdit{};
+    prt_scene_view(c); // (every pointer null)
     c->haveScene = false;
 }
 
@@ -132,7 +142,8 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
     std::vector<PrtRefitMesh> refitMeshes;
     std::vector<uint32_t> hotOrder;
     PrtEdit ed;
-    DevScene sc{};
+    PrtSceneArrays arr; // the context's once everything is on the device: a failed upload frees what it had allocated
+    DevScene sc{};      // (its pointers stay null: prt_scene_view)
     sc.bvhCount = s->meshCount;
 
     for (uint32_t t = 0; t < s->textureCount; t++) {
@@ -404,10 +415,10 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
         std::vector<float4> tex((size_t)W * H);
         memcpy(tex.data(), s->envTexels, tex.size() * sizeof(float4));
         std::vector<float> vp(s->envVerticalP, s->envVerticalP + H), hp(s->envHorizontalP, s->envHorizontalP + (size_t)W * H);
-        if ((rc = upload_vec(c, tex, &sc.envTexels))) return rc;
-        if ((rc = upload_vec(c, vp, &sc.envV))) return rc;
-        if ((rc = upload_vec(c, hp, &sc.envHor))) return rc;
-        if ((rc = upload_vec(c, firstX, &sc.envFirstX))) return rc;
+        if ((rc = prt_upload(arr.envTexels, tex, c->stream))) return rc;
+        if ((rc = prt_upload(arr.envV, vp, c->stream))) return rc;
+        if ((rc = prt_upload(arr.envHor, hp, c->stream))) return rc;
+        if ((rc = prt_upload(arr.envFirstX, firstX, c->stream))) return rc;
         sc.envW = W;
         sc.envH = H;
         sc.envFirstY = firstStep(s->envVerticalP, H);
@@ -424,25 +435,26 @@ int prt_hip_upload_scene(prt_hip_ctx* c, const prt_scene_desc* s)
             if ((size_t)off + (size_t)w * h * comp > texels.size()) return fail(PRT_HIP_EINVAL, "internal: material map descriptor outside the texel array");
         }
     if (mats.size() % PRT_MAT_STRIDE != 0) return fail(PRT_HIP_EINVAL, "internal: material table is not a whole number of records");
-    if ((rc = upload_vec(c, wnodes, &sc.wnodes))) return rc;
-    if ((rc = upload_vec(c, hot, &sc.hotNodes))) return rc;
-    if ((rc = upload_vec(c, tris, &sc.tris))) return rc;
-    if ((rc = upload_vec(c, triAlpha, &sc.triAlpha))) return rc;
-    if ((rc = upload_vec(c, triPrim, &sc.triPrim))) return rc;
-    if ((rc = upload_vec(c, shade, &sc.shade))) return rc;
-    if ((rc = upload_vec(c, bump, &sc.bump))) return rc;
-    if ((rc = upload_vec(c, mats, &sc.mats))) return rc;
-    if ((rc = upload_vec(c, alpha, &sc.alpha))) return rc;
-    if ((rc = upload_vec(c, alphaClass, &sc.alphaClass))) return rc;
-    if ((rc = upload_vec(c, texDesc, &sc.texDesc))) return rc;
-    if ((rc = upload_vec(c, texels, &sc.texels))) return rc;
-    c->sc = sc;
+    if ((rc = prt_upload(arr.wnodes, wnodes, c->stream))) return rc;
+    if ((rc = prt_upload(arr.hotNodes, hot, c->stream))) return rc;
+    if ((rc = prt_upload(arr.tris, tris, c->stream))) return rc;
+    if ((rc = prt_upload(arr.triAlpha, triAlpha, c->stream))) return rc;
+    if ((rc = prt_upload(arr.triPrim, triPrim, c->stream))) return rc;
+    if ((rc = prt_upload(arr.shade, shade, c->stream))) return rc;
+    if ((rc = prt_upload(arr.bump, bump, c->stream))) return rc;
+    if ((rc = prt_upload(arr.mats, mats, c->stream))) return rc;
+    if ((rc = prt_upload(arr.alpha, alpha, c->stream))) return rc;
+    if ((rc = prt_upload(arr.alphaClass, alphaClass, c->stream))) return rc;
+    if ((rc = prt_upload(arr.texDesc, texDesc, c->stream))) return rc;
+    if ((rc = prt_upload(arr.texels, texels, c->stream))) return rc;
     for (uint32_t m = 0; m < sc.bvhCount; m++) refitMeshes[m].rootKid = sc.rootRef[m];
-    if ((rc = prt_refit_build(c, wnodes, hotOrder, std::move(refitMeshes), slotVtx, anyBump))) return rc;
-    ed.matRecords = mats.size() / PRT_MAT_STRIDE;
-    ed.classWords = alphaClass.size();
-    ed.texelBytes = texels.size();
-    ed.anyBump = anyBump;
+    if ((rc = prt_refit_build(c, wnodes, hotOrder, std::move(refitMeshes), slotVtx))) {
+        prt_refit_forget(c); // (whatever part of it was built)
+        return rc;
+    }
+    c->arr = std::move(arr);
+    c->sc = sc;
+    prt_scene_view(c);
     ed.texDesc = std::move(texDesc);
     ed.classWordOf = std::move(classWordOf);
     c->ed = std::move(ed);
