@@ -511,12 +511,10 @@ extern "C" int prt_hip_build_bvh(prt_hip_ctx* c, uint32_t primCount, const uint3
     char* scanTemp;
     HIP_TRY(mem.get(&scanTemp, scanBytes));
 
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    StageTimer tm(1); // its two events go with it on every return
     HIP_TRY(hipMemcpyAsync(dIdx, indices, (size_t)n * 12, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dPos, positions, (size_t)vertexCount * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e0, s));
+    HIP_TRY(tm.mark(s));
     const dim3 blk(256), grdN((n + 255) / 256);
     hipLaunchKernelGGL(iota_kernel, grdN, blk, 0, s, n, B.remap, B.posNode);
     // node 0 = the root over [0, n - 1]
@@ -570,16 +568,15 @@ extern "C" int prt_hip_build_bvh(prt_hip_ctx* c, uint32_t primCount, const uint3
         if (last > first) hipLaunchKernelGGL(index_kernel, dim3((last - first + 255) / 256), blk, 0, s, B, first, last);
     }
     hipLaunchKernelGGL(emit_kernel, dim3((nodeCount + 255) / 256), blk, 0, s, B, nodeCount, dOut);
-    HIP_TRY(hipEventRecord(e1, s));
+    HIP_TRY(tm.mark(s));
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return prt_fail(PRT_HIP_ELAUNCH, std::string("BVH build kernels: ") + hipGetErrorString(le));
     HIP_TRY(hipMemcpyAsync(nodes_out, dOut, (size_t)nodeCount * sizeof(prt_bvh_node), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(primRemapping_out, B.remap, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(tm.lap());
+    HIP_TRY(tm.median(0, &ms));
     if (buildMs) *buildMs = ms;
     *nodeCount_out = nodeCount;
     return PRT_HIP_OK;

@@ -91,8 +91,8 @@ static void fold_timing(prt_hip_ctx* c)
 int prt_timing_pair(prt_hip_ctx* c, hipEvent_t* ev0, hipEvent_t* ev1)
 {
     if (c->ringUsed == PRT_TIMING_RING) fold_timing(c);
-    if (!c->evT0[c->ringUsed]) HIP_TRY(hipEventCreate(&c->evT0[c->ringUsed]));
-    if (!c->evT1[c->ringUsed]) HIP_TRY(hipEventCreate(&c->evT1[c->ringUsed]));
+    HIP_TRY(c->evT0[c->ringUsed].make());
+    HIP_TRY(c->evT1[c->ringUsed].make());
     *ev0 = c->evT0[c->ringUsed];
     *ev1 = c->evT1[c->ringUsed];
     c->ringUsed++;
@@ -172,8 +172,8 @@ static int create_resources(prt_hip_ctx* c)
     c->computeUnits = prop.multiProcessorCount;
     c->name = prop.name[0] ? prop.name : prop.gcnArchName;
     HIP_TRY(hipStreamCreate(&c->stream));
-    HIP_TRY(hipEventCreateWithFlags(&c->evIn, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->evOut, hipEventDisableTiming));
+    HIP_TRY(c->evIn.make(hipEventDisableTiming));
+    HIP_TRY(c->evOut.make(hipEventDisableTiming));
     HIP_TRY(c->work.fit(PRT_WORK_WORDS + PRT_STICKY_WORDS, c->stream));
     HIP_TRY(hipMemset(c->work, 0, (PRT_WORK_WORDS + PRT_STICKY_WORDS) * sizeof(uint32_t)));
     HIP_TRY(c->counters.fit(PRT_STAT_SHARDS * PRT_STAT_STRIDE, c->stream));
@@ -210,16 +210,9 @@ void prt_hip_destroy(prt_hip_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     prt_free_scene(c);
-    if (c->adCountHost) (void)hipHostFree(c->adCountHost);
     prt_gather_release(c);
-    for (int k = 0; k < PRT_TIMING_RING; k++) {
-        if (c->evT0[k]) (void)hipEventDestroy(c->evT0[k]);
-        if (c->evT1[k]) (void)hipEventDestroy(c->evT1[k]);
-    }
-    if (c->evIn) (void)hipEventDestroy(c->evIn);
-    if (c->evOut) (void)hipEventDestroy(c->evOut);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c; // frees the context's buffers (DevBuf)
+    delete c; // frees the context's buffers, events and pinned memory (DevBuf, DevEvent, HostBuf)
 }
 
 int prt_hip_device_info(prt_hip_ctx* c, char* name, size_t cap, int* computeUnits)

@@ -199,7 +199,7 @@ int scratch_ready(prt_hip_ctx* c)
     if (!R.vboxOut) HIP_TRY(R.vboxOut.fit(PRT_MAX_BVH * 6, c->stream));
     if (!R.boxPartial) HIP_TRY(R.boxPartial.fit(PRT_DEFORM_BOX_BLOCKS * 6, c->stream));
     if (!R.sahPartial) HIP_TRY(R.sahPartial.fit(3 * ((size_t)sah_blocks_max(c) + 1), c->stream)); // (the last three: the sums)
-    if (!R.vboxHost) HIP_TRY(hipHostMalloc((void**)&R.vboxHost, PRT_MAX_BVH * 6 * sizeof(float)));
+    HIP_TRY(R.vboxHost.fit(PRT_MAX_BVH * 6));
     return PRT_HIP_OK;
 }
 
@@ -358,9 +358,9 @@ int prepare_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, prt
     return PRT_HIP_OK;
 }
 
-// The device work of a checked and prepared call on s.  ev (optional, 6 events): before the keep kernels, after them, after the face
-// kernels, after the vertex kernels, after the gathers, after the finish kernel.
-int queue_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, uint32_t flags, hipStream_t s, hipEvent_t* ev)
+// The device work of a checked and prepared call on s.  tm (optional, 6 marks): before the keep kernels, after them, after the face
+// kernels, and -- the three of prt_refit_queue -- after the vertex kernels, after the gathers, after the finish kernel.
+int queue_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, uint32_t flags, hipStream_t s, StageTimer* tm)
 {
     PrtRefit& R = c->rf;
     const bool host = (flags & PRT_HIP_DEFORM_HOST) != 0;
@@ -378,7 +378,7 @@ int queue_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, uint3
         }
         if (d[k].normalsMode == PRT_HIP_NORMALS_RECOMPUTE) src[k].nrm = M.dNrm;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     int rc;
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = R.meshes[d[k].mesh];
@@ -391,22 +391,21 @@ int queue_deform(prt_hip_ctx* c, uint32_t count, const prt_mesh_deform* d, uint3
             for (uint32_t k = 0; k < count; k++) named |= d[k].mesh == m;
             if (!named && !R.meshes[m].vboxValid && (rc = queue_box(c, m, R.meshes[m].dPos, nullptr, nullptr, nullptr, s))) return rc;
         }
-    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    if (tm) HIP_TRY(tm->mark(s));
     for (uint32_t k = 0; k < count; k++) {
         const PrtRefitMesh& M = R.meshes[d[k].mesh];
         if (d[k].normalsMode != PRT_HIP_NORMALS_RECOMPUTE || M.primCount == 0) continue;
         hipLaunchKernelGGL(deform_face_kernel, dim3(blocks_of(M.primCount)), dim3(PRT_DEFORM_BLOCK), 0, s, M.faceVtx, src[k].pos, M.faceNrm, M.primCount);
         if ((rc = prt_launched("deform_face_kernel"))) return rc;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+    if (tm) HIP_TRY(tm->mark(s));
     for (uint32_t k = 0; k < count; k++) {
         const PrtRefitMesh& M = R.meshes[d[k].mesh];
         if (d[k].normalsMode != PRT_HIP_NORMALS_RECOMPUTE || M.vertexCount == 0) continue;
         hipLaunchKernelGGL(deform_vertex_kernel, dim3(blocks_of(M.vertexCount)), dim3(PRT_DEFORM_BLOCK), 0, s, M.csrOff, M.csrFace, M.faceNrm, M.dNrm, M.vertexCount);
         if ((rc = prt_launched("deform_vertex_kernel"))) return rc;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[3], s));
-    return prt_refit_queue(c, count, src, s, ev ? ev + 3 : nullptr); // (which records ev[3] once more, at the same point)
+    return prt_refit_queue(c, count, src, s, tm);
 }
 
 // after the synchronisation: the vertex boxes, the radius (AUTO) and what prt_hip_update_meshes commits
@@ -549,24 +548,13 @@ int prt_hip_test_deform_profile(prt_hip_ctx* c, uint32_t count, const prt_mesh_d
     if (!ms5 || reps == 0) return fail(PRT_HIP_EINVAL, "NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = prepare_deform(c, count, deforms, as))) return rc;
-    hipEvent_t ev[6];
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    std::vector<float> t[5];
-    for (uint32_t r = 0; r < reps && rc == PRT_HIP_OK; r++) {
-        rc = queue_deform(c, count, deforms, flags, c->stream, ev);
-        if (rc == PRT_HIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PRT_HIP_ELAUNCH, "deform profile: synchronise failed");
-        for (int j = 0; j < 5 && rc == PRT_HIP_OK; j++) {
-            float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, ev[j], ev[j + 1]);
-            t[j].push_back(ms);
-        }
+    StageTimer tm(5);
+    for (uint32_t r = 0; r < reps; r++) {
+        if ((rc = queue_deform(c, count, deforms, flags, c->stream, &tm))) return rc;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(PRT_HIP_ELAUNCH, "deform profile: synchronise failed");
+        HIP_TRY(tm.lap());
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    for (int j = 0; j < 5; j++) {
-        std::sort(t[j].begin(), t[j].end());
-        ms5[j] = t[j][t[j].size() / 2];
-    }
+    for (uint32_t j = 0; j < 5; j++) HIP_TRY(tm.median(j, &ms5[j]));
     return prt_hip_deform_meshes(c, count, deforms, flags, nullptr);
 }
 #endif

@@ -265,27 +265,27 @@ int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K)
 
 namespace {
 
-// Prepare + iterations on the context's stream.  ev (optional, iterations + 2 events): recorded before the prepare kernel and
-// after every launch.
-int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev)
+// Prepare + iterations on the context's stream.  tm (optional, iterations + 2 marks): before the prepare kernel and after every
+// launch.
+int run_filter(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, StageTimer* tm)
 {
     const uint32_t W = c->cam.width, H = c->cam.height;
     const size_t n = (size_t)W * H;
     hipStream_t s = c->stream;
     const float4* mom = (c->accMom.size() == n && !c->momClear) ? c->accMom : nullptr;
     int rc;
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     hipLaunchKernelGGL(dn_prepare_kernel, dim3(grid1d(c, n)), dim3(256), 0, s, (const float4*)c->accSum, mom, (const float*)c->dnAlbedo,
                        (const float*)c->dnNormal, n, (int)d->demodulate, c->dnPlane[0], c->dnGuideA, c->dnGuideN);
     if ((rc = prt_launched("dn_prepare_kernel"))) return rc;
-    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
-    return prt_denoise_iterations(c, d, exposure, d_rgb, ev ? ev + 2 : nullptr);
+    if (tm) HIP_TRY(tm->mark(s));
+    return prt_denoise_iterations(c, d, exposure, d_rgb, tm);
 }
 
 } // namespace
 
-// The iterations on dnPlane[0] (what a prepare step left there) into d_rgb.  ev (optional, `iterations` events): one after every launch.
-int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev)
+// The iterations on dnPlane[0] (what a prepare step left there) into d_rgb.  tm (optional, `iterations` marks): one after every launch.
+int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, StageTimer* tm)
 {
     const uint32_t W = c->cam.width, H = c->cam.height;
     hipStream_t s = c->stream;
@@ -300,7 +300,7 @@ int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float ex
         else
             hipLaunchKernelGGL(dn_iter_kernel<false>, grid, dim3(DN_TILE_X * DN_TILE_Y), 0, s, A);
         if ((rc = prt_launched("dn_iter_kernel"))) return rc;
-        if (ev) HIP_TRY(hipEventRecord(ev[i], s));
+        if (tm) HIP_TRY(tm->mark(s));
         cur ^= 1;
     }
     c->dnLast = cur;
@@ -435,19 +435,19 @@ int prt_hip_test_denoise_profile(prt_hip_ctx* c, const prt_denoise_params* d, fl
     HIP_TRY(hipSetDevice(c->device));
     float* rgb = nullptr;
     if ((rc = prt_denoise_guides_ready(c, d->guideSamples)) || (rc = prt_own_framebuffer(c, &rgb))) return rc;
-    hipEvent_t ev[8] = {};
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
     // the whole filter between two events, then the same again with an event after every launch
-    HIP_TRY(hipEventRecord(ev[0], c->stream));
+    StageTimer whole(1), each(d->iterations + 1);
+    HIP_TRY(whole.mark(c->stream));
     if ((rc = run_filter(c, d, exposure, rgb, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(ev[1], c->stream));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[6], ev[0], ev[1]));
-    if ((rc = run_filter(c, d, exposure, rgb, ev))) return rc;
-    HIP_TRY(hipEventSynchronize(ev[1 + d->iterations]));
+    HIP_TRY(whole.mark(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(whole.lap());
+    HIP_TRY(whole.median(0, &ms[6]));
+    if ((rc = run_filter(c, d, exposure, rgb, &each))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(each.lap());
     for (uint32_t k = 0; k < 6; k++) ms[k] = 0.0f;
-    for (uint32_t k = 0; k <= d->iterations; k++) HIP_TRY(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-    for (auto& e : ev) (void)hipEventDestroy(e);
+    for (uint32_t k = 0; k <= d->iterations; k++) HIP_TRY(each.median(k, &ms[k]));
     return PRT_HIP_OK;
 }
 
@@ -469,17 +469,14 @@ int prt_hip_test_copy_yardstick(prt_hip_ctx* c, uint64_t pixels, int read16, int
     for (int k = 0; k < read12; k++, q += n * 12) A.r12[k] = (const float*)q;
     if (write12) A.w12 = (float*)q;
     A.nr16 = read16; A.nr12 = read12; A.nw16 = write16; A.nw12 = write12; A.n = n;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    StageTimer tm(1);
     hipLaunchKernelGGL(dn_copy_kernel, dim3(grid1d(c, n)), dim3(256), 0, c->stream, A); // warm-up
-    HIP_TRY(hipEventRecord(e0, c->stream));
+    HIP_TRY(tm.mark(c->stream));
     hipLaunchKernelGGL(dn_copy_kernel, dim3(grid1d(c, n)), dim3(256), 0, c->stream, A);
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(tm.mark(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(tm.lap());
+    HIP_TRY(tm.median(0, ms));
     return prt_launched("dn_copy_kernel");
 }
 

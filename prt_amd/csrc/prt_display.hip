@@ -159,34 +159,34 @@ int dp_own_buffer(prt_hip_ctx* c, uint32_t format, uint8_t** d_out)
     return PRT_HIP_OK;
 }
 
-// The launches of one display on the context's stream; ev (optional, 4 events): before the metering, after the histogram, after the
-// resolve, after the transform.
+// The launches of one display on the context's stream; tm (optional, 4 marks): before the metering, after the histogram, after the
+// resolve, after the transform (without metering the first three follow one another).
 int dp_queue(prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const prt_display_params* p, const float* d_rgb, uint8_t* d_out,
-             hipEvent_t* ev)
+             StageTimer* tm)
 {
     int rc;
     hipStream_t s = c->stream;
     const uint32_t W = c->cam.width;
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     if (p->meter) {
         const DpRect R = dp_rect(W, x0, y0, x1, y1, DP_BLOCK, false);
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)R.rows * R.chunks, (uint64_t)c->computeUnits * 8);
         HIP_TRY(hipMemsetAsync(c->dpHist, 0, DP_HIST_WORDS * sizeof(uint32_t), s));
         hipLaunchKernelGGL(display_hist_kernel, dim3(blocks), dim3(DP_BLOCK), 0, s, d_rgb, R, c->dpHist);
         if ((rc = prt_launched("display_hist_kernel"))) return rc;
-        if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+        if (tm) HIP_TRY(tm->mark(s));
         hipLaunchKernelGGL(display_resolve_kernel, dim3(1), dim3(64), 0, s, (const uint32_t*)c->dpHist, *p, c->dpState);
         if ((rc = prt_launched("display_resolve_kernel"))) return rc;
-    } else if (ev) {
-        HIP_TRY(hipEventRecord(ev[1], s));
+    } else if (tm) {
+        HIP_TRY(tm->mark(s));
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+    if (tm) HIP_TRY(tm->mark(s));
     const DpRect R = dp_rect(W, x0, y0, x1, y1, DP_BLOCK, true);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((uint64_t)R.rows * R.chunks, (uint64_t)c->computeUnits * 4);
     const uint32_t vec = ((uintptr_t)d_rgb % 16 == 0 && (uintptr_t)d_out % 16 == 0) ? 1u : 0u;
     hipLaunchKernelGGL(display_transform_kernel, dim3(blocks), dim3(DP_BLOCK), 0, s, d_rgb, d_out, R, *p, (const prt_display_state*)c->dpState, vec);
     if ((rc = prt_launched("display_transform_kernel"))) return rc;
-    if (ev) HIP_TRY(hipEventRecord(ev[3], s));
+    if (tm) HIP_TRY(tm->mark(s));
     return PRT_HIP_OK;
 }
 } // namespace
@@ -290,24 +290,13 @@ int prt_hip_test_display_profile(prt_hip_ctx* c, const prt_display_params* p, ui
     HIP_TRY(hipSetDevice(c->device));
     uint8_t* d_out = nullptr;
     if ((rc = dp_state_ready(c)) || (rc = dp_own_buffer(c, p->format, &d_out))) return rc;
-    hipEvent_t ev[4];
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    std::vector<float> t[3];
-    for (uint32_t r = 0; r <= reps && rc == PRT_HIP_OK; r++) { // the first is the warm-up
-        rc = dp_queue(c, 0, 0, c->cam.width - 1, c->cam.height - 1, p, c->fb, d_out, ev);
-        if (rc == PRT_HIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PRT_HIP_ELAUNCH, "display profile: synchronise failed");
-        for (int k = 0; k < 3 && rc == PRT_HIP_OK && r > 0; k++) {
-            float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-            t[k].push_back(ms);
-        }
+    StageTimer tm(3);
+    for (uint32_t r = 0; r <= reps; r++) { // the first is the warm-up
+        if ((rc = dp_queue(c, 0, 0, c->cam.width - 1, c->cam.height - 1, p, c->fb, d_out, &tm))) return rc;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(PRT_HIP_ELAUNCH, "display profile: synchronise failed");
+        HIP_TRY(tm.lap(r == 0));
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    for (int k = 0; k < 3; k++) {
-        std::sort(t[k].begin(), t[k].end());
-        ms3[k] = t[k][t[k].size() / 2];
-    }
+    for (uint32_t k = 0; k < 3; k++) HIP_TRY(tm.median(k, &ms3[k]));
     if (!p->meter) ms3[0] = ms3[1] = 0.0f;
     return PRT_HIP_OK;
 }

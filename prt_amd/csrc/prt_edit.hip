@@ -163,18 +163,18 @@ int env_alloc(EnvBuild& b, int32_t W, int32_t H, hipStream_t s)
     return PRT_HIP_OK;
 }
 
-// the copy of the image and the two kernels on s; ev (optional, 2 events) around the kernels
-int env_queue(const EnvBuild& b, int32_t W, int32_t H, const float* texels, hipStream_t s, hipEvent_t* ev)
+// the copy of the image and the two kernels on s; tm (optional, 2 marks) around the kernels
+int env_queue(const EnvBuild& b, int32_t W, int32_t H, const float* texels, hipStream_t s, StageTimer* tm)
 {
     if (texels) HIP_TRY(hipMemcpyAsync(b.texels, texels, (size_t)W * H * sizeof(float4), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(b.result, 0, 64, s));
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     hipLaunchKernelGGL(env_rows_kernel, dim3((uint32_t)H), dim3(PRT_ENV_CHUNK), 0, s, b.texels, W, H, b.hor, b.vert, b.firstX, b.result);
     int rc = prt_launched("env_rows_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(env_column_kernel, dim3(1), dim3(PRT_ENV_CHUNK), 0, s, b.vert, H, b.result);
     if ((rc = prt_launched("env_column_kernel"))) return rc;
-    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    if (tm) HIP_TRY(tm->mark(s));
     return PRT_HIP_OK;
 }
 
@@ -253,8 +253,8 @@ int check_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u)
     return PRT_HIP_OK;
 }
 
-// the copies of the caller's texels, then the class kernels, on s; ev (optional, 2 events) around the kernels
-int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, hipStream_t s, hipEvent_t* ev)
+// the copies of the caller's texels, then the class kernels, on s; tm (optional, 2 marks) around the kernels
+int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, hipStream_t s, StageTimer* tm)
 {
     const PrtEdit& E = c->ed;
     uint8_t* texels = c->arr.texels;
@@ -262,7 +262,7 @@ int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, 
         const uint4 d = E.texDesc[u[k].texture];
         HIP_TRY(hipMemcpyAsync(texels + d.x, u[k].texels, (size_t)d.y * d.z * d.w, hipMemcpyHostToDevice, s));
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t first = E.classWordOf[u[k].texture];
         if (first == 0xffffffffu) continue; // no alpha-tested material names it
@@ -273,7 +273,7 @@ int queue_textures(prt_hip_ctx* c, uint32_t count, const prt_texture_update* u, 
         int rc = prt_launched("alpha_class_kernel");
         if (rc) return rc;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    if (tm) HIP_TRY(tm->mark(s));
     return PRT_HIP_OK;
 }
 
@@ -431,35 +431,29 @@ int prt_hip_test_edit_profile(prt_hip_ctx* c, uint32_t count, const prt_texture_
     int rc = count ? check_textures(c, count, updates) : PRT_HIP_OK;
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipEvent_t ev[2];
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    std::vector<float> env, cls;
-    EnvBuild b;
-    if (c->sc.hasEnv) rc = env_alloc(b, c->sc.envW, c->sc.envH, c->stream);
-    for (uint32_t r = 0; r < reps && rc == PRT_HIP_OK; r++) {
-        float a = 0.0f, d = 0.0f;
-        if (c->sc.hasEnv) {
-            if (hipMemcpyAsync(b.texels, c->sc.envTexels, (size_t)c->sc.envW * c->sc.envH * sizeof(float4), hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-                rc = fail(PRT_HIP_ENODEVICE, "edit profile: copy failed");
-            if (rc == PRT_HIP_OK) rc = env_queue(b, c->sc.envW, c->sc.envH, nullptr, c->stream, ev);
-            if (rc == PRT_HIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PRT_HIP_ELAUNCH, "edit profile: synchronise failed");
-            if (rc == PRT_HIP_OK) (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+    const hipStream_t s = c->stream;
+    const bool hasEnv = c->sc.hasEnv != 0;
+    StageTimer env(1), cls(1);
+    EnvBuild b; // its buffers go with the scope: every return below follows a synchronisation of what was queued on them
+    if (hasEnv && (rc = env_alloc(b, c->sc.envW, c->sc.envH, s))) return rc;
+    for (uint32_t r = 0; r < reps; r++) {
+        if (hasEnv) {
+            if (hipMemcpyAsync(b.texels, c->sc.envTexels, (size_t)c->sc.envW * c->sc.envH * sizeof(float4), hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return fail(PRT_HIP_ENODEVICE, "edit profile: copy failed");
+            rc = env_queue(b, c->sc.envW, c->sc.envH, nullptr, s, &env);
+            if (hipStreamSynchronize(s) != hipSuccess) return fail(PRT_HIP_ELAUNCH, "edit profile: synchronise failed");
+            if (rc) return rc;
+            HIP_TRY(env.lap());
         }
-        if (rc == PRT_HIP_OK && count) {
-            rc = queue_textures(c, count, updates, c->stream, ev);
-            if (rc == PRT_HIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PRT_HIP_ELAUNCH, "edit profile: synchronise failed");
-            if (rc == PRT_HIP_OK) (void)hipEventElapsedTime(&d, ev[0], ev[1]);
+        if (count) {
+            if ((rc = queue_textures(c, count, updates, s, &cls))) return rc;
+            if (hipStreamSynchronize(s) != hipSuccess) return fail(PRT_HIP_ELAUNCH, "edit profile: synchronise failed");
+            HIP_TRY(cls.lap());
         }
-        env.push_back(a);
-        cls.push_back(d);
     }
-    (void)hipStreamSynchronize(c->stream); // b's buffers go at the end of the scope
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    std::sort(env.begin(), env.end());
-    std::sort(cls.begin(), cls.end());
-    ms2[0] = env[env.size() / 2];
-    ms2[1] = cls[cls.size() / 2];
+    ms2[0] = ms2[1] = 0.0f;
+    if (hasEnv) HIP_TRY(env.median(0, &ms2[0]));
+    if (count) HIP_TRY(cls.median(0, &ms2[1]));
     return count ? prt_hip_update_textures(c, count, updates, nullptr) : PRT_HIP_OK;
 }
 #endif

@@ -9,6 +9,7 @@
 
 #include "../../include/prt_hip.h"
 #include "prt_devbuf.h"
+#include "prt_devres.h"
 #include "prt_device.h"
 #include "prt_batch.h"
 
@@ -71,11 +72,11 @@ struct PrtRefit {
     DevBuf<uint32_t> hotOrder;     // record index of every hot slot
     uint32_t hotCount = 0;
     DevBuf<float> rootOut;         // device: PRT_MAX_BVH x 6 floats, the refitted root boxes
-    float* rootHost = nullptr;     // pinned host copy of it (freed by prt_refit_forget, like vboxHost)
+    HostBuf<float> rootHost;       // pinned host copy of it
     // prt_deform.hip, allocated on first use: the vertex boxes of a call (PRT_MAX_BVH x 6 floats), their pinned host copy, and the
     // per-block partials of the box and SAH reductions
     DevBuf<float> vboxOut;
-    float* vboxHost = nullptr;
+    HostBuf<float> vboxHost;
     DevBuf<float> boxPartial;
     DevBuf<double> sahPartial;
 };
@@ -107,13 +108,15 @@ struct PrtSceneArrays {
     bool anyBump() const { return bump.size() != 0; }
 };
 
+// Every event, device buffer and pinned buffer of the context is a member that owns it (DevEvent, DevBuf, HostBuf) and goes with
+// `delete c`.  The stream alone stays a raw handle: created in prt_hip_create and destroyed in prt_hip_destroy, one place each.
 struct prt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     // Timing: a fixed ring of event pairs, one pair per render launch.  When the ring is full the oldest launches are folded
     // into accMs (they have long finished), so a caller that renders in a loop without reading the stats holds no more than
     // PRT_TIMING_RING pairs.
-    hipEvent_t evT0[PRT_TIMING_RING] = {}, evT1[PRT_TIMING_RING] = {};
+    DevEvent evT0[PRT_TIMING_RING], evT1[PRT_TIMING_RING]; // each created when the ring first reaches it
     uint32_t ringUsed = 0;
     double accMs = 0.0, lastMs = 0.0;
     uint64_t accLaunches = 0;
@@ -131,7 +134,7 @@ struct prt_hip_ctx {
     DevBuf<float> fb;           // the context's own framebuffer, at the size of the camera it was last rendered or uploaded for
     DevBuf<uint32_t> work;      // PRT_WORK_WORDS control words of a launch + PRT_STICKY_WORDS
     DevBuf<unsigned long long> counters;
-    hipEvent_t evIn = nullptr, evOut = nullptr; // order the pipeline against a caller's stream
+    DevEvent evIn, evOut;       // order the pipeline against a caller's stream
     DevBuf<char> wfBuffer;      // the frame kernel's pool state and ray queues
     DevBuf<uint32_t> spill;     // spill columns of the traversal stacks: [entry][thread], two words per entry (prt_launch_resources)
     uint32_t spillThreads() const { return (uint32_t)(spill.size() / (2 * (PRT_STACK_MAX - PRT_STACK_LDS_PACKET))); }
@@ -158,7 +161,7 @@ struct prt_hip_ctx {
     DevBuf<uint8_t> adFlag;      // per work item: 1 = active
     DevBuf<char> adTemp;         // hipcub scratch of the compaction
     DevBuf<uint32_t> adCount;    // active pixels of the last selection
-    uint32_t* adCountHost = nullptr; // pinned host copy of it
+    HostBuf<uint32_t> adCountHost; // pinned host copy of it
     DevBuf<float> adErr;         // prt_hip_accum_error: the rectangle's errors
     // denoised previews (prt_denoise.hip): guide and scratch planes at the camera's size, allocated on first use
     DevBuf<float> dnAlbedo;      // guide planes, 3 floats per pixel: the average of dnGuideK G-buffer launches, or the host's own
@@ -275,22 +278,22 @@ int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std
 void prt_refit_forget(prt_hip_ctx* c);
 // prt_refit.hip, shared with prt_hip_deform_meshes (prt_deform.hip): every refusal of prt_hip_update_meshes; the staging buffers of the
 // named meshes (normals too where `normals` is set); gather, levels and finish of the named meshes queued on s, reading device
-// arrays (ev, optional, 3 events: before the gathers, after them, after the finish kernel); and, once the context's stream has been
+// arrays (tm, optional, 3 marks: before the gathers, after them, after the finish kernel); and, once the context's stream has been
 // synchronised behind the copy of rootOut to rootHost, the root boxes, the radius (0 keeps it) and everything the call invalidates
 int prt_refit_check(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u);
 int prt_refit_staging(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u);
-int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* src, hipStream_t s, hipEvent_t* ev);
+int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* src, hipStream_t s, StageTimer* tm);
 void prt_refit_commit(prt_hip_ctx* c, uint32_t count, const uint32_t* meshes, float radius);
 // prt_deform.hip: the SAH sums of the mesh's tree as uploaded, kept before its first update (PrtRefitMesh::sahUpload)
 int prt_deform_capture_sah(prt_hip_ctx* c, uint32_t mesh);
 // prt_denoise.hip: the view or the scene changed, or the planes are new (guides of either origin are dropped)
 void prt_denoise_forget(prt_hip_ctx* c);
 // prt_denoise.hip, for the temporal stage (prt_temporal.hip), which replaces the prepare step and then runs the same iterations:
-// the checks of prt_hip_accum_denoise; the guide planes for K jitters; the iterations on dnPlane[0] -> d_rgb (ev, optional: one
-// event recorded after every launch)
+// the checks of prt_hip_accum_denoise; the guide planes for K jitters; the iterations on dnPlane[0] -> d_rgb (tm, optional: one
+// mark after every launch)
 int prt_denoise_checks(prt_hip_ctx* c, const prt_denoise_params* d);
 int prt_denoise_guides_ready(prt_hip_ctx* c, uint32_t K);
-int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, hipEvent_t* ev);
+int prt_denoise_iterations(prt_hip_ctx* c, const prt_denoise_params* d, float exposure, float* d_rgb, StageTimer* tm);
 // prt_temporal.hip: the view changes to `next` (pending becomes history when the size stays, else both go; the position guide
 // goes stale); the scene changed or prt_hip_history_reset (both records go)
 void prt_temporal_camera_change(prt_hip_ctx* c, const prt_camera_desc* next);

@@ -459,7 +459,7 @@ static int moments_ready(prt_hip_ctx* c)
 static int adapt_buffers(prt_hip_ctx* c, uint64_t items)
 {
     HIP_TRY(c->adCount.fit(1, c->stream));
-    if (!c->adCountHost) HIP_TRY(hipHostMalloc((void**)&c->adCountHost, sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(c->adCountHost.fit(1));
     const size_t padded = (size_t)((items + PRT_CHUNK - 1) / PRT_CHUNK * PRT_CHUNK);
     HIP_TRY(c->adCode.grow(padded, c->stream));
     HIP_TRY(c->adList.grow(padded, c->stream));

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(PRT_REFIT_BLOCK) void refit_finish_kernel(RootArgs 
 }
 
 // Queues the copies of the caller's host arrays into the staging buffers, then the refit reading them (prt_refit_queue).
-int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipStream_t s, hipEvent_t* ev)
+int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipStream_t s, StageTimer* tm)
 {
     PrtRefit& R = c->rf;
     PrtRefitSrc src[PRT_MAX_BVH];
@@ -167,18 +167,18 @@ int queue_update(prt_hip_ctx* c, uint32_t count, const prt_mesh_update* u, hipSt
         M.vboxValid = false; // (the vertex box of the staged copy is reduced when a later call asks for it: prt_deform.hip)
         src[k] = PrtRefitSrc{u[k].mesh, M.dPos, u[k].normals ? (float*)M.dNrm : nullptr};
     }
-    return prt_refit_queue(c, count, src, s, ev);
+    return prt_refit_queue(c, count, src, s, tm);
 }
 
 } // namespace
 
-int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStream_t s, hipEvent_t* ev)
+int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStream_t s, StageTimer* tm)
 {
     PrtRefit& R = c->rf;
     PrtSceneArrays& A = c->arr; // the writable pointers are the owners'
     float* tris = A.tris;
     float4* wnodes = A.wnodes;
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (tm) HIP_TRY(tm->mark(s));
     for (uint32_t k = 0; k < count; k++) {
         PrtRefitMesh& M = R.meshes[u[k].mesh];
         if (M.slotCount == 0) continue;
@@ -187,7 +187,7 @@ int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStr
         int rc = prt_launched("refit_gather_kernel");
         if (rc) return rc;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    if (tm) HIP_TRY(tm->mark(s));
     RootArgs ra{};
     for (uint32_t k = 0; k < count; k++) {
         const PrtRefitMesh& M = R.meshes[u[k].mesh];
@@ -207,7 +207,7 @@ int prt_refit_queue(prt_hip_ctx* c, uint32_t count, const PrtRefitSrc* u, hipStr
                        R.hotOrder, R.hotCount, A.hotNodes);
     int rc = prt_launched("refit_finish_kernel");
     if (rc) return rc;
-    if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+    if (tm) HIP_TRY(tm->mark(s));
     return PRT_HIP_OK;
 }
 
@@ -303,16 +303,11 @@ int prt_refit_build(prt_hip_ctx* c, const std::vector<float4>& wnodes, const std
     if ((rc = prt_upload(R.levelList, levelList, c->stream))) return rc;
     if ((rc = prt_upload(R.hotOrder, hotOrder, c->stream))) return rc;
     HIP_TRY(R.rootOut.fit(PRT_MAX_BVH * 6, c->stream));
-    HIP_TRY(hipHostMalloc((void**)&R.rootHost, PRT_MAX_BVH * 6 * sizeof(float)));
+    HIP_TRY(R.rootHost.fit(PRT_MAX_BVH * 6));
     return PRT_HIP_OK;
 }
 
-void prt_refit_forget(prt_hip_ctx* c)
-{
-    if (c->rf.rootHost) (void)hipHostFree(c->rf.rootHost);
-    if (c->rf.vboxHost) (void)hipHostFree(c->rf.vboxHost);
-    c->rf = PrtRefit{}; // (the device arrays go with their DevBufs)
-}
+void prt_refit_forget(prt_hip_ctx* c) { c->rf = PrtRefit{}; } // (the device arrays and the pinned copies go with their owners)
 
 extern "C" {
 
@@ -376,26 +371,13 @@ int prt_hip_test_refit_profile(prt_hip_ctx* c, uint32_t count, const prt_mesh_up
     if ((rc = prt_refit_staging(c, count, updates))) return rc;
     for (uint32_t k = 0; k < count; k++)
         if ((rc = prt_deform_capture_sah(c, updates[k].mesh))) return rc;
-    hipEvent_t ev[3];
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    std::vector<float> g, l;
-    for (uint32_t r = 0; r < reps && rc == PRT_HIP_OK; r++) {
-        rc = queue_update(c, count, updates, c->stream, ev);
-        if (rc == PRT_HIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(PRT_HIP_ELAUNCH, "refit profile: synchronise failed");
-        float a = 0.0f, b = 0.0f;
-        if (rc == PRT_HIP_OK) {
-            (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-            (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-            g.push_back(a);
-            l.push_back(b);
-        }
+    StageTimer tm(2);
+    for (uint32_t r = 0; r < reps; r++) {
+        if ((rc = queue_update(c, count, updates, c->stream, &tm))) return rc;
+        if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(PRT_HIP_ELAUNCH, "refit profile: synchronise failed");
+        HIP_TRY(tm.lap());
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    if (rc) return rc;
-    std::sort(g.begin(), g.end());
-    std::sort(l.begin(), l.end());
-    ms2[0] = g[g.size() / 2];
-    ms2[1] = l[l.size() / 2];
+    for (uint32_t k = 0; k < 2; k++) HIP_TRY(tm.median(k, &ms2[k]));
     return prt_hip_update_meshes(c, count, updates, nullptr);
 }
 #endif

@@ -456,35 +456,34 @@ int prt_hip_test_temporal_profile(prt_hip_ctx* c, const prt_denoise_params* d, c
     HIP_TRY(hipSetDevice(c->device));
     float* rgb = nullptr;
     if ((rc = temporal_inputs(c, d)) || (rc = prt_own_framebuffer(c, &rgb))) return rc;
-    hipEvent_t ev[4] = {};
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    StageTimer denoise(2), position(1), gbuffer(1);
     hipStream_t s = c->stream;
-    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(denoise.mark(s));
     if ((rc = run_merge(c, d, t))) return rc;
-    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(denoise.mark(s));
     if ((rc = run_merge(c, d, t)) || (rc = prt_denoise_iterations(c, d, exposure, rgb, nullptr))) return rc;
-    HIP_TRY(hipEventRecord(ev[2], s));
-    HIP_TRY(hipEventSynchronize(ev[2]));
-    HIP_TRY(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[1], ev[1], ev[2]));
-    const bool host = c->tpHostPos;
-    if (!host) { // a host's plane is left alone (ms[2] = 0)
-        HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(denoise.mark(s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(denoise.lap());
+    HIP_TRY(denoise.median(0, &ms[0]));
+    HIP_TRY(denoise.median(1, &ms[1]));
+    ms[2] = 0.0f;
+    if (!c->tpHostPos) { // a host's plane is left alone (ms[2] = 0)
+        HIP_TRY(position.mark(s));
         if ((rc = position_ready(c, true))) return rc;
-        HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms[2], ev[0], ev[1]));
-    } else {
-        ms[2] = 0.0f;
+        HIP_TRY(position.mark(s));
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(position.lap());
+        HIP_TRY(position.median(0, &ms[2]));
     }
     // the G-buffer launch writes the iterations' spare plane, never the image; both figures include the two small memsets of a launch
-    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(gbuffer.mark(s));
     if ((rc = prt_hip_render_gbuffer(c, 0, 0, c->cam.width - 1, c->cam.height - 1, 0, c->accSeed, 1.0f, (float*)(float4*)c->dnPlane[1], nullptr))) return rc;
-    HIP_TRY(hipEventRecord(ev[3], s));
-    HIP_TRY(hipEventSynchronize(ev[3]));
-    HIP_TRY(hipEventElapsedTime(&ms[3], ev[2], ev[3]));
+    HIP_TRY(gbuffer.mark(s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(gbuffer.lap());
+    HIP_TRY(gbuffer.median(0, &ms[3]));
     c->dnLast = -1; // dnPlane[1] was overwritten
-    for (auto& e : ev) (void)hipEventDestroy(e);
     return PRT_HIP_OK;
 }
 
