@@ -824,6 +824,74 @@ int prt_hip_query_get_counts(prt_hip_ctx* ctx, uint64_t* invalidHits); /* synchr
 int prt_hip_query_radiance(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, const prt_render_params* params,
                            float* radiance /* 3*n floats */, uint32_t flags, void* stream);
 
+/* ---- baking: points and direction sets in, weighted radiance sums out.  What every baker writes around prt_hip_query_radiance -- a
+ * tangent frame per probe or texel, K local directions rotated into it, the origin tiled K times, n*K rays up and n*K radiances
+ * down, a weighted mean -- as one call that takes 32 bytes per point and returns C*12 bytes per point: light probes, irradiance
+ * volumes, lightmap texels.  The rays and the per-ray radiances never leave the device.
+ *
+ * A point is {P, bias, N, set}; the table holds nSets direction sets of K local directions (z along the normal) and, per direction,
+ * C weights.  One set with C = 1, cosine-weighted directions and weights pi/K gives irradiance; directions on the sphere with C = 9
+ * and weights 4pi/K * Y_c(d_k) give an SH9 probe (such points have N = 0: the frame is the identity); several sets, each point naming
+ * its own, break up the pattern one shared set leaves across neighbouring texels.
+ *
+ * Definition.  Everything is f32, every product is rounded before the sum that uses it (no FMA).
+ * Ray r = i*K + k of point i, with s = points[i].set and d = dirs[(s*K + k)*3 ..]:
+ *     if all three components of N compare equal to 0:  org = P, dir = d
+ *     otherwise the frame is the bounce loop's own (path_tracer.cpp:147-153):
+ *         u = fabsf(N.x) > 0.1f ? (0,1,0) : (1,0,0)
+ *         T = normalize3(cross3(N, u))
+ *         B = normalize3(cross3(T, N))
+ *         dir = (d.x*B + d.y*T) + d.z*N per component, with N as given and not normalised
+ *         org = P + bias*N per component
+ *     with cross3(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x) and normalize3(v) = (1.0f / sqrtf(v.x*v.x + v.y*v.y
+ *     + v.z*v.z)) * v per component (vecmath.h:1200)
+ *     tMax = 0, pad = 0
+ * Hostile N (NaN, inf, 1e-30, 3e20) is not refused: the arithmetic gives what it gives, and the probe rule of prt_hip_query_radiance
+ * makes a non-finite or unnormalisable direction black.  (Which NaN an invalid operation gives, its sign and payload, is the
+ * processor's choice.)
+ * set >= nSets is never followed: the point's K rays get org = dir = 0.
+ * Radiance L[r] is prt_hip_query_radiance of those n*K rays under params: probe r under seed + r, with all of that call's rules.
+ * Reduce, one wavefront per point, in an order fixed by K alone:
+ *     1. for lane l = 0..63, for channel c and colour component h: a_l = +0
+ *     2. for k = l, l+64, l+128, ... < K: a_l = a_l + (weights[(s*K + k)*C + c] * L[3r + h])
+ *     3. for step = 32, 16, 8, 4, 2, 1, for l < step: a_l = a_l + a_(l+step)
+ *     4. out[(i*C + c)*3 + h] = a_0
+ * A point with set >= nSets writes +0 to all its 3*C floats.  Weights and radiance are taken as given: a NaN weight gives a NaN
+ * output for that point and for no other.
+ *
+ * prt_hip_bake runs the ray kernel, the frame kernel's probe launch and the reduce kernel in order on the context's stream; the rays
+ * and radiances live in buffers the context owns, grown on demand.  It is one persistent frame-kernel launch: prt_hip_get_stats
+ * reports it as prt_hip_query_radiance of n*K probes would (nPx = n*K).  prt_hip_bake_rays and prt_hip_bake_reduce are the two
+ * halves on the caller's arrays: bake_rays needs no scene, and bake_reduce lets a baker who kept the per-ray radiance project it
+ * again under other weights without tracing again; neither is a launch for the statistics.  bake_rays reads no weights and
+ * bake_reduce no directions: that pointer of the table may be NULL there.
+ * Pointers: DEVICE pointers by default, sets->dirs and sets->weights included (the prt_bake_sets record itself is host memory, read
+ * before the call returns); points and rays 16-byte aligned, floats 4-byte aligned; asynchronous, ordered after the work queued on
+ * stream and before what is queued next, as the queries are.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged through
+ * buffers the context owns, and the call returns with the answer.  Other flag bits are refused.
+ * Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the outputs untouched: a NULL pointer; K outside
+ * 1 .. 4096, C outside 1 .. 16, nSets outside 1 .. 1024; reserved != 0; n = 0 or n*K > 2^24; for prt_hip_bake whatever
+ * prt_hip_query_radiance refuses of params.  prt_hip_bake without a scene is PRT_HIP_ESTATE.
+ * State: prt_hip_bake reads the scene and changes nothing else: the camera, the accumulator, the moments, the guides, the history,
+ * the display state and the framebuffer are untouched, and so are the staging buffers of the queries.
+ * Not built: batches beyond 2^24 rays (the caller splits by points and passes seed + i0*K for the part that starts at point i0);
+ * per-point validity or back-face counts; splitting over ranks. ---- */
+typedef struct { float P[3]; float bias; float N[3]; uint32_t set; } prt_bake_point;   /* 32 bytes, 16-byte aligned */
+typedef struct {
+    uint32_t K;           /* directions per point, 1 .. 4096 */
+    uint32_t C;           /* output channels per point, 1 .. 16 */
+    uint32_t nSets;       /* direction sets, 1 .. 1024 */
+    uint32_t reserved;    /* must be 0 */
+    const float* dirs;    /* nSets*K*3: local directions (x, y, z), z along the normal */
+    const float* weights; /* nSets*K*C: weights[(set*K + k)*C + c] */
+} prt_bake_sets;
+int prt_hip_bake_rays(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, prt_ray* rays /* n*K */,
+                      uint32_t flags, void* stream);
+int prt_hip_bake_reduce(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets,
+                        const float* radiance /* 3*n*K */, float* out /* 3*C*n */, uint32_t flags, void* stream);
+int prt_hip_bake(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, const prt_render_params* params,
+                 float* out /* 3*C*n */, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,16 @@ SURFACE_DTYPE = np.dtype([("P", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), (
                           ("meshMaterial", "<u4"), ("uv", "<f4", 2), ("primId", "<u4"), ("meshId", "<u4"), ("diffuse", "<f4", 3),
                           ("pad", "<u4")])
 QUERY_HOST = 1  # PRT_HIP_QUERY_HOST
+# prt_bake_point / prt_bake_sets (include/prt_hip.h "baking")
+BAKE_POINT_DTYPE = np.dtype([("P", "<f4", 3), ("bias", "<f4"), ("N", "<f4", 3), ("set", "<u4")])
+
+
+class BakeSets(C.Structure):
+    """prt_bake_sets: dirs (nSets*K*3 floats) and weights (nSets*K*C floats) are device pointers, or host pointers under QUERY_HOST."""
+    _fields_ = [("K", C.c_uint32), ("C", C.c_uint32), ("nSets", C.c_uint32), ("reserved", C.c_uint32), ("dirs", C.c_void_p),
+                ("weights", C.c_void_p)]
+
+
 NODE_DTYPE = np.dtype([("lower", "<f4", 3), ("upper", "<f4", 3), ("primOrSecondNodeIndex", "<u4"),
                        ("triVectorIndex", "<u4"), ("primCount", "<u4"), ("splitAxis", "<u4")])
 MATERIAL_DTYPE = np.dtype([("diffuse", "<f4", 3), ("emissive", "<f4", 3), ("reflectionType", "<u4"),
@@ -211,6 +221,7 @@ EXPORTS = [
     "prt_hip_display", "prt_hip_download_display", "prt_hip_display_get_state", "prt_hip_display_reset", "prt_hip_upload",
     "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
     "prt_hip_query_radiance",
+    "prt_hip_bake_rays", "prt_hip_bake_reduce", "prt_hip_bake",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -329,6 +340,9 @@ def _load(path, with_test_entry_points):
     L.prt_hip_query_surface.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
     L.prt_hip_query_get_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.prt_hip_query_radiance.argtypes = [vp, C.c_uint32, vp, C.POINTER(RenderParams), vp, C.c_uint32, vp]
+    L.prt_hip_bake_rays.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), vp, C.c_uint32, vp]
+    L.prt_hip_bake_reduce.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), vp, vp, C.c_uint32, vp]
+    L.prt_hip_bake.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), C.POINTER(RenderParams), vp, C.c_uint32, vp]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
@@ -1197,6 +1211,54 @@ class PathTracer:
         self.last_stats = self.stats()  # raises on stack overflow
         return out
 
+    # ---- baking (include/prt_hip.h "baking"): points and direction sets in, weighted radiance sums out
+    def bake_async(self, n, d_points, table, d_out, spp, seed=None, exposure=None, max_depth=None, stream=None):
+        """Queue prt_hip_bake on device arrays: d_points (n prt_bake_point, 16-byte aligned) and d_out (3 * C * n float32) are device
+        pointers (int), table a BakeSets whose dirs and weights are device pointers.  Ray i*K + k is traced under seed + i*K + k."""
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        self._chk(self._L.prt_hip_bake(self._ctx, n, d_points, C.byref(table), C.byref(p), d_out, 0, stream), "prt_hip_bake")
+
+    def bake(self, points, normals, dirs, weights, spp, bias=1e-4, sets=None, seed=None, exposure=None, max_depth=None):
+        """The weighted radiance sums of n points: points, normals (n, 3) float32 (a zero normal: the identity frame), dirs (K, 3) or
+        (nSets, K, 3) local directions with z along the normal, weights (K,), (K, C) or (nSets, K, C), sets None or (n,) the set of
+        each point.  Returns (n, C, 3) float32: out[i, c] = sum over k of weights[set, k, c] * radiance along ray i*K + k, the rays
+        and sums as include/prt_hip.h "baking" defines them; sets last_stats (nPx = n * K).  Needs a scene and no camera."""
+        pts = make_bake_points(points, normals, bias, sets)
+        d, w, table = make_bake_sets(dirs, weights)
+        out = np.zeros((len(pts), table.C, 3), dtype=np.float32)
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        self._chk(self._L.prt_hip_bake(self._ctx, len(pts), pts.ctypes.data_as(C.c_void_p), C.byref(table), C.byref(p),
+                                       out.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_bake")
+        self.last_stats = self.stats()  # raises on stack overflow
+        return out
+
+    def bake_rays(self, points, normals, dirs, bias=1e-4, sets=None):
+        """(n * K,) RAY_DTYPE: the rays bake() traces for these points and directions (prt_hip_bake_rays; needs no scene)."""
+        pts = make_bake_points(points, normals, bias, sets)
+        d, _, table = make_bake_sets(dirs, None)
+        rays = np.zeros(len(pts) * table.K, dtype=RAY_DTYPE)
+        self._chk(self._L.prt_hip_bake_rays(self._ctx, len(pts), pts.ctypes.data_as(C.c_void_p), C.byref(table),
+                                            rays.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_bake_rays")
+        return rays
+
+    def bake_reduce(self, weights, radiance, sets=None):
+        """(n, C, 3) float32: bake()'s sums of per-ray radiance the caller kept -- radiance (n, K, 3) float32, weights (K,), (K, C) or
+        (nSets, K, C) -- under other weights, without tracing again (prt_hip_bake_reduce)."""
+        L = np.ascontiguousarray(radiance, dtype=np.float32)
+        if L.ndim != 3 or L.shape[2] != 3:
+            raise PrtError(f"bake_reduce: radiance must be (n, K, 3), not {L.shape}")
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim < 3:
+            w = w.reshape(1, L.shape[1], -1)
+        _, w, table = make_bake_sets(None, w)
+        if table.K != L.shape[1]:
+            raise PrtError(f"bake_reduce: weights for {table.K} directions, radiance for {L.shape[1]}")
+        pts = make_bake_points(np.zeros((len(L), 3), np.float32), np.zeros((len(L), 3), np.float32), 0.0, sets)
+        out = np.zeros((len(L), table.C, 3), dtype=np.float32)
+        self._chk(self._L.prt_hip_bake_reduce(self._ctx, len(L), pts.ctypes.data_as(C.c_void_p), C.byref(table), L.ctypes.data_as(C.c_void_p),
+                                              out.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_bake_reduce")
+        return out
+
     def pick(self, x, y):
         """What lies under pixel (x, y) of the current camera: the ray through the pixel's centre (the position guide's ray) ->
         (hit, surface), one element of HIT_DTYPE and of SURFACE_DTYPE; hit["t"] == -1 for the background."""
@@ -1357,6 +1419,73 @@ def make_rays(org, dir, t_max):
     rays["org"], rays["dir"] = o, d
     rays["tMax"] = np.asarray(t_max, dtype=np.float32)
     return rays
+
+
+# ----------------------------------------------------------------------------- baking
+def make_bake_points(points, normals, bias=1e-4, sets=None):
+    """(n,) BAKE_POINT_DTYPE from points, normals (n, 3), bias (a scalar or (n,)) and sets (None = set 0, or (n,) uint32)."""
+    P = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    N = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if len(P) != len(N):
+        raise PrtError(f"{len(P)} points for {len(N)} normals")
+    pts = np.zeros(len(P), dtype=BAKE_POINT_DTYPE)
+    pts["P"], pts["N"] = P, N
+    pts["bias"] = np.asarray(bias, dtype=np.float32)
+    if sets is not None:
+        pts["set"] = np.asarray(sets, dtype=np.uint32)
+    return pts
+
+
+def make_bake_sets(dirs, weights):
+    """(dirs (nSets, K, 3) or None, weights (nSets, K, C) or None, BakeSets pointing at the two HOST arrays -- keep them alive) from dirs
+    (K, 3) or (nSets, K, 3) and weights (K,), (K, C) or (nSets, K, C); either may be None (bake_reduce reads no directions, bake_rays no
+    weights)."""
+    d = w = None
+    if dirs is not None:
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        d = d.reshape((1,) + d.shape) if d.ndim == 2 else d
+        if d.ndim != 3 or d.shape[2] != 3:
+            raise PrtError(f"bake: dirs must be (K, 3) or (nSets, K, 3), not {d.shape}")
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim < 3:
+            if d is None:
+                raise PrtError("bake: weights without dirs must be (nSets, K, C)")
+            if w.size % (d.shape[0] * d.shape[1]) == 0:
+                w = w.reshape(d.shape[0], d.shape[1], -1)
+        if w.ndim != 3 or (d is not None and w.shape[:2] != d.shape[:2]):
+            raise PrtError(f"bake: weights {w.shape} do not fit dirs {None if d is None else d.shape}")
+    shape = d.shape if d is not None else w.shape
+    table = BakeSets(K=shape[1], C=1 if w is None else w.shape[2], nSets=shape[0], reserved=0,
+                     dirs=None if d is None else d.ctypes.data, weights=None if w is None else w.ctypes.data)
+    return d, w, table
+
+
+def bake_cosine_set(K, rng):
+    """(dirs (K, 3), weights (K, 1)) float32: K cosine-weighted directions about +z (pdf = cos / pi) and weights pi / K, so that
+    bake() returns irradiance (C = 1).  rng: a numpy Generator."""
+    u1, u2 = rng.random(K), rng.random(K)
+    r, phi = np.sqrt(u1), 2.0 * np.pi * u2
+    dirs = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u1)], axis=1).astype(np.float32)
+    return dirs, np.full((K, 1), np.pi / K, dtype=np.float32)
+
+
+def sh9_basis(d):
+    """(len(d), 9): the real spherical harmonics of bands 0 to 2 at unit directions d (n, 3), in the order
+    1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2."""
+    x, y, z = (np.asarray(d, dtype=np.float64)[:, k] for k in range(3))
+    return np.stack([0.28209479177387814 * np.ones_like(x), 0.4886025119029199 * y, 0.4886025119029199 * z, 0.4886025119029199 * x,
+                     1.0925484305920792 * x * y, 1.0925484305920792 * y * z, 0.31539156525252005 * (3.0 * z * z - 1.0),
+                     1.0925484305920792 * x * z, 0.5462742152960396 * (x * x - y * y)], axis=1)
+
+
+def bake_sh9_set(K, rng):
+    """(dirs (K, 3), weights (K, 9)) float32: K uniform directions on the sphere and weights 4 pi / K * Y_c(d_k), so that bake() at a
+    point with a zero normal returns the SH9 coefficients of the radiance arriving there (C = 9)."""
+    z, phi = rng.uniform(-1.0, 1.0, K), rng.uniform(0.0, 2.0 * np.pi, K)
+    r = np.sqrt(1.0 - z * z)
+    dirs = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(np.float32)
+    return dirs, (4.0 * np.pi / K * sh9_basis(dirs)).astype(np.float32)
 
 
 def pixel_centre_rays(cam, xs, ys):

@@ -23,6 +23,7 @@ SOURCES = [
     "prt_edit.hip",
     "prt_display.hip",
     "prt_query.hip",
+    "prt_bake.hip",
     "prt_rowtests.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",

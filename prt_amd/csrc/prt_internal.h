@@ -193,6 +193,11 @@ struct prt_hip_ctx {
     DevBuf<prt_surface> qSurf;
     DevBuf<uint8_t> qOccl;
     DevBuf<float> qRad;                // prt_hip_query_radiance: 3 floats per probe
+    // baking (prt_bake.hip): allocated on first use
+    DevBuf<prt_ray> bkRays;            // prt_hip_bake: the n*K rays and their radiances, which never leave the device; with
+    DevBuf<float> bkRad;               // PRT_HIP_QUERY_HOST also the staged rays of bake_rays and radiances of bake_reduce
+    DevBuf<prt_bake_point> bkPoints;   // PRT_HIP_QUERY_HOST: the caller's points, table and answer, staged on the device
+    DevBuf<float> bkDirs, bkWeights, bkOut;
 };
 
 
@@ -232,6 +237,10 @@ int prt_batch_end(prt_hip_ctx* c, const BatchLaunch& L, const char* kernel);
 // prt_kernels.hip, for prt_hip_query_radiance (prt_query.hip): one launch of the frame kernel's probe instantiation over n checked
 // probes on the context's stream, timed as a render: d_rays and d_radiance (3 * n floats) are device memory, p has been checked
 int prt_frame_probe(prt_hip_ctx* c, uint32_t n, const prt_ray* d_rays, const prt_render_params* p, float* d_radiance);
+// prt_query.hip, shared with prt_bake.hip: every refusal of prt_hip_query_radiance for n probes under p and flags, under the caller's
+// name; and the answer to a NULL argument (ENODEVICE on a machine without a device, EINVAL otherwise)
+int prt_check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags, const char* what);
+int prt_null_argument(const char* what);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
 // prt_upload.hip, the ONE place that writes a pointer of c->sc: each from its owner in c->arr (null where the owner is empty).  Called

@@ -200,13 +200,6 @@ int check_batch(prt_hip_ctx* c, uint32_t n, uint32_t flags, const char* what)
     return PRT_HIP_OK;
 }
 
-// ENODEVICE on a machine without a device (where no context can exist), EINVAL otherwise
-int null_argument(const char* what)
-{
-    if (prt_hip_device_count() == 0) return fail(PRT_HIP_ENODEVICE, "no HIP device: libprt_hip has no CPU path (the GPU kernels are the product)");
-    return fail(PRT_HIP_EINVAL, std::string(what) + ": NULL argument");
-}
-
 // One launch of a traversal kernel over the batch on the context's stream, timed as a render.
 int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surf, uint8_t* occ, bool any)
 {
@@ -325,21 +318,6 @@ int run_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q, uint32_t flags, void
 // ============================================================================ radiance along the caller's rays
 #define PRT_QUERY_MAX_PROBES (1u << 24)
 
-// What prt_hip_query_radiance asks of its scalar arguments; everything is refused before anything is queued.
-int check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags)
-{
-    const char* what = "query_radiance";
-    if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
-    if (n == 0 || n > PRT_QUERY_MAX_PROBES) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^24");
-    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
-    if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
-        return fail(PRT_HIP_EINVAL, std::string(what) + ": samples must be a multiple of 8 from 8 to 2040");
-    if (p->maxDepth > 255) return fail(PRT_HIP_EINVAL, std::string(what) + ": maxDepth too large");
-    if (p->rank != 0 || p->nranks != 1) return fail(PRT_HIP_EINVAL, std::string(what) + ": probes are not split over ranks (rank 0 of nranks 1)");
-    if (p->countTraffic != 0) return fail(PRT_HIP_EINVAL, std::string(what) + ": countTraffic must be 0 (the probe kernel has no counting build)");
-    return PRT_HIP_OK;
-}
-
 int radiance_staged(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance)
 {
     hipStream_t s = c->stream;
@@ -364,13 +342,35 @@ int radiance_direct(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_r
 
 } // namespace
 
+// ENODEVICE on a machine without a device (where no context can exist), EINVAL otherwise
+int prt_null_argument(const char* what)
+{
+    if (prt_hip_device_count() == 0) return fail(PRT_HIP_ENODEVICE, "no HIP device: libprt_hip has no CPU path (the GPU kernels are the product)");
+    return fail(PRT_HIP_EINVAL, std::string(what) + ": NULL argument");
+}
+
+// What prt_hip_query_radiance asks of its scalar arguments, and prt_hip_bake (prt_bake.hip) of its n*K probes; everything is refused
+// before anything is queued.
+int prt_check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags, const char* what)
+{
+    if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
+    if (n == 0 || n > PRT_QUERY_MAX_PROBES) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^24");
+    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
+        return fail(PRT_HIP_EINVAL, std::string(what) + ": samples must be a multiple of 8 from 8 to 2040");
+    if (p->maxDepth > 255) return fail(PRT_HIP_EINVAL, std::string(what) + ": maxDepth too large");
+    if (p->rank != 0 || p->nranks != 1) return fail(PRT_HIP_EINVAL, std::string(what) + ": probes are not split over ranks (rank 0 of nranks 1)");
+    if (p->countTraffic != 0) return fail(PRT_HIP_EINVAL, std::string(what) + ": countTraffic must be 0 (the probe kernel has no counting build)");
+    return PRT_HIP_OK;
+}
+
 extern "C" {
 
 int prt_hip_query_radiance(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance, uint32_t flags,
                            void* stream)
 {
-    if (!c || !rays || !p || !radiance) return null_argument("query_radiance");
-    int rc = check_radiance(c, n, p, flags);
+    if (!c || !rays || !p || !radiance) return prt_null_argument("query_radiance");
+    int rc = prt_check_radiance(c, n, p, flags, "query_radiance");
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return (flags & PRT_HIP_QUERY_HOST) ? radiance_staged(c, n, rays, p, radiance) : radiance_direct(c, n, rays, p, radiance, stream);
@@ -378,25 +378,25 @@ int prt_hip_query_radiance(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, cons
 
 int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
-    if (!c || !rays || !hits) return null_argument("query_nearest");
+    if (!c || !rays || !hits) return prt_null_argument("query_nearest");
     return run_query(c, n, QueryIO{QUERY_NEAREST, rays, nullptr, hits, surfaces, nullptr}, flags, stream, "query_nearest");
 }
 
 int prt_hip_query_any(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, uint8_t* occluded, uint32_t flags, void* stream)
 {
-    if (!c || !rays || !occluded) return null_argument("query_any");
+    if (!c || !rays || !occluded) return prt_null_argument("query_any");
     return run_query(c, n, QueryIO{QUERY_ANY, rays, nullptr, nullptr, nullptr, occluded}, flags, stream, "query_any");
 }
 
 int prt_hip_query_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
-    if (!c || !rays || !hits || !surfaces) return null_argument("query_surface");
+    if (!c || !rays || !hits || !surfaces) return prt_null_argument("query_surface");
     return run_query(c, n, QueryIO{QUERY_SURFACE, rays, hits, nullptr, surfaces, nullptr}, flags, stream, "query_surface");
 }
 
 int prt_hip_query_get_counts(prt_hip_ctx* c, uint64_t* invalidHits)
 {
-    if (!c || !invalidHits) return null_argument("query_get_counts");
+    if (!c || !invalidHits) return prt_null_argument("query_get_counts");
     *invalidHits = 0;
     if (!c->qCounts) return PRT_HIP_OK; // no query_surface yet
     HIP_TRY(hipSetDevice(c->device));

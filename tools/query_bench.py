@@ -17,6 +17,12 @@ prt_hip_render under seed + q and a download -- timed by the wall clock over 256
 cost 256 times one call: nothing is shared between them).  The 256 probes must agree bit for bit between the two paths.
 
     python tools/query_bench.py --radiance [--reps 7] [--out F]
+
+--bake: prt_hip_bake (include/prt_hip.h "baking").  4096 and 65 536 points (first hits of the same camera's rays) with one cosine set of
+K = 64 and K = 256 directions, 8 spp, depth 8: (a) one prt_hip_bake on device arrays, (b) rays in numpy, query_radiance on host arrays
+and a numpy mean, (c) the frame-kernel launch inside (a); and the two new kernels alone.  The ratio to read is (a) / (c).
+
+    python tools/query_bench.py --bake [--reps 5] [--out F]
 """
 import argparse
 import ctypes as C
@@ -102,16 +108,134 @@ def radiance(args):
     emit(out, args.out)
 
 
+class DeviceArray:
+    """A numpy array's bytes in device memory (hipMalloc through the runtime the library is linked to)."""
+    hip = None
+
+    def __init__(self, a):
+        if DeviceArray.hip is None:
+            h = DeviceArray.hip = C.CDLL("libamdhip64.so")
+            h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+            h.hipFree.argtypes = [C.c_void_p]
+            h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.ptr, self.nbytes = C.c_void_p(), a.nbytes
+        assert self.hip.hipMalloc(C.byref(self.ptr), max(a.nbytes, 64)) == 0, "hipMalloc"
+        assert self.hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, 1) == 0
+
+    def get(self, dtype):
+        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
+        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0
+        return out
+
+    def free(self):
+        self.hip.hipFree(self.ptr)
+
+
+def bake(args):
+    """Points = the first hits of pixel-centre rays at equal strides over the image (position and shading normal from query_nearest's
+    surface records), one cosine set of K directions.  Per (n, K): (a) prt_hip_bake on device arrays, wall time of the call up to
+    the synchronisation behind it; (c) the frame-kernel launch inside (a), kernelMs; the two new kernels alone on device arrays
+    (prt_hip_bake_rays, prt_hip_bake_reduce: wall time up to the synchronisation); (b) the route there was before: rays built in numpy,
+    query_radiance on host arrays, a numpy weighted mean.  The largest difference between the answers of (a) and (b) is reported, not
+    asserted: the host's frame is built in double precision, and a direction that differs in its last bit sends some path elsewhere
+    (equality byte for byte with the same rays is what tests/test_gpu_bake.py holds)."""
+    W, H = (int(v) for v in args.size.split("x"))
+    spp, depth, seed = 8, 8, 12345
+    scene, camera, _ = prt_amd.setup_atrium_standin(W, H, tris=262000, seed=1)
+    t = prt_amd.PathTracer(max_depth=depth, seed=seed)
+    t.upload_scene(scene)
+    out = {"workload": "c3_sponza_standin", "points_from": args.size + " first hits at equal strides", "spp": spp, "max_depth": depth,
+           "reps": args.reps, "device": t.device_info()[0], "compute_units": t.device_info()[1],
+           "source_sha16": prt_amd.loaded_source_sha16(), "bake": {}}
+    sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
+    for n in (4096, 65536):
+        idx = (np.arange(4 * n, dtype=np.uint64) * np.uint64(W * H) // np.uint64(4 * n)).astype(np.uint32)
+        ys, xs = np.divmod(idx, np.uint32(W))
+        r = prt_amd.pixel_centre_rays(camera.desc, xs, ys)
+        hits, surf = t.query_nearest(r["org"], r["dir"], r["tMax"], surface=True)
+        surf = surf[hits["t"] != -1][:n]
+        assert len(surf) == n, "too few first hits"
+        pts = prt_amd.make_bake_points(surf["P"], surf["shadingNormal"], 1e-4)
+        for K in (64, 256):
+            d, w = prt_amd.bake_cosine_set(K, np.random.default_rng(K))
+            bufs = [DeviceArray(a) for a in (pts, d, w, np.zeros(n * 3, np.float32), np.zeros(n * K, prt_amd.RAY_DTYPE),
+                                             np.zeros((n * K, 3), np.float32))]
+            d_pts, d_dirs, d_w, d_out, d_rays, d_rad = (b.ptr.value for b in bufs)
+            table = prt_amd.BakeSets(K=K, C=1, nSets=1, reserved=0, dirs=d_dirs, weights=d_w)
+            p = t._probe_params(spp, None, None, None)
+            times = {k: [] for k in ("a_bake_wall", "c_frame_kernel", "rays_kernel_wall", "reduce_kernel_wall", "b_host_route_wall",
+                                     "b_numpy_rays", "b_query_radiance", "b_numpy_reduce")}
+            host = None
+            for rep in range(2 + args.reps):
+                keep = rep >= 2
+                sync()
+                t0 = time.perf_counter()
+                t.bake_async(n, d_pts, table, d_out, spp)
+                st = t.stats()
+                dt = (time.perf_counter() - t0) * 1e3
+                if keep:
+                    times["a_bake_wall"].append(dt)
+                    times["c_frame_kernel"].append(st["kernelMs"])
+                for name, call in (("rays_kernel_wall", lambda: t._L.prt_hip_bake_rays(t._ctx, n, d_pts, C.byref(table), d_rays, 0, None)),
+                                   ("reduce_kernel_wall", lambda: t._L.prt_hip_bake_reduce(t._ctx, n, d_pts, C.byref(table), d_rad, d_out, 0, None))):
+                    sync()
+                    t0 = time.perf_counter()
+                    assert call() == 0
+                    sync()
+                    if keep:
+                        times[name].append((time.perf_counter() - t0) * 1e3)
+                if rep in (0, 2 + args.reps - 1) or (keep and n * K <= 1 << 20):  # (the host route at 16.8 M rays: once warm, once timed)
+                    t0 = time.perf_counter()
+                    rays = host_rays(pts, d)
+                    t1 = time.perf_counter()
+                    L = t.query_radiance(rays["org"], rays["dir"], spp)
+                    t2 = time.perf_counter()
+                    host = (np.pi * L.reshape(n, K, 3).mean(axis=1, dtype=np.float64)).astype(np.float32)
+                    t3 = time.perf_counter()
+                    if keep:
+                        for k, v in (("b_host_route_wall", t3 - t0), ("b_numpy_rays", t1 - t0), ("b_query_radiance", t2 - t1), ("b_numpy_reduce", t3 - t2)):
+                            times[k].append(v * 1e3)
+            t.bake_async(n, d_pts, table, d_out, spp)
+            rays_traced = t.stats()["raysTraced"]
+            got = bufs[3].get(np.float32).reshape(n, 3)
+            for b in bufs:
+                b.free()
+            a, c = float(np.median(times["a_bake_wall"])), float(np.median(times["c_frame_kernel"]))
+            out["bake"][f"{n}x{K}"] = {
+                "ms": {k: spread(v) for k, v in times.items()}, "rays_traced": rays_traced,
+                "a_over_c": a / c, "b_over_a": float(np.median(times["b_host_route_wall"])) / a,
+                "new_kernels_share_of_a": (float(np.median(times["rays_kernel_wall"])) + float(np.median(times["reduce_kernel_wall"]))) / a,
+                "largest_difference_from_host_route": float(np.abs(got - host).max()), "largest_value": float(np.abs(host).max())}
+    t.close()
+    emit(out, args.out)
+
+
+def host_rays(pts, d):
+    """What a baker wrote in numpy: a tangent frame per point, the K directions rotated into it, the origin tiled."""
+    N = pts["N"].astype(np.float64)
+    N /= np.linalg.norm(N, axis=1, keepdims=True)
+    u = np.where((np.abs(N[:, 0]) > 0.1)[:, None], [0.0, 1.0, 0.0], [1.0, 0.0, 0.0])
+    T = np.cross(N, u)
+    T /= np.linalg.norm(T, axis=1, keepdims=True)
+    B = np.cross(T, N)
+    dirs = d[None, :, 0, None] * B[:, None, :] + d[None, :, 1, None] * T[:, None, :] + d[None, :, 2, None] * N[:, None, :]
+    org = np.repeat(pts["P"] + np.float32(1e-4) * pts["N"], d.shape[0], axis=0)
+    return prt_amd.make_rays(org, dirs.reshape(-1, 3), 0.0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--out", default=None)
     ap.add_argument("--radiance", action="store_true")
+    ap.add_argument("--bake", action="store_true")
     args = ap.parse_args()
     prt_amd.build()
     if args.radiance:
         return radiance(args)
+    if args.bake:
+        return bake(args)
     W, H = (int(v) for v in args.size.split("x"))
     scene, camera, _ = prt_amd.setup_atrium_standin(W, H, tris=262000, seed=1)
     t = prt_amd.PathTracer(max_depth=8, test_entry_points=True)
