@@ -892,6 +892,82 @@ int prt_hip_bake_reduce(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* poin
 int prt_hip_bake(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, const prt_render_params* params,
                  float* out /* 3*C*n */, uint32_t flags, void* stream);
 
+/* ---- lightmap atlases: per-corner lightmap UVs in, a lightmap image out.  prt_hip_bake takes the world position and normal of every
+ * lightmap texel; producing that array means rasterising the meshes in their lightmap UV space, and after the bake the n answers have
+ * to go back into a W x H image whose chart borders are dilated, or bilinear taps bleed black into the charts.  Three calls around
+ * prt_hip_bake, which is used as it stands:
+ *     prt_hip_atlas_rasterize   UV triangles -> the covered texels and, per texel, a hit record of the triangle that owns it
+ *     prt_hip_atlas_points      hit records -> bake points on the scene as it is now
+ *     prt_hip_atlas_resolve     per-point values -> an image with a filled gutter
+ * The UVs are the caller's LIGHTMAP channel, given per corner (texture UVs tile and overlap): 6 floats per triangle, (u, v) of corners
+ * 0, 1, 2, triangles in mesh order.  u runs along x over W texels and v along y over H; texel (x, y) has the index y*W + x and its
+ * centre at u = (x + 0.5) / W, v = (y + 0.5) / H.
+ *
+ * prt_hip_atlas_rasterize.  Integer arithmetic throughout, so it is watertight along shared edges and independent of the order in
+ * which triangles are processed.  It needs no scene.
+ *   Snap.  Corner (u, v) snaps to a 1/256-texel grid: fx = u * (float)(256*W) (one f32 product), X = rint(fx) (ties to even); Y the
+ *     same with H.  A triangle with a corner where !(fabsf(fx) <= 8388608.0f) in either coordinate is not rasterised and counts in
+ *     `rejected`: NaN, infinity and far-off UVs.
+ *   Edge functions, in int64: E(a,b,c) = (b.x-a.x)*(c.y-a.y) - (b.y-a.y)*(c.x-a.x).  A = E(v0,v1,v2); a triangle with A == 0 counts in
+ *     `degenerate` and covers nothing.  For texel (x, y) with c = (256x+128, 256y+128): w0 = E(v1,v2,c), w1 = E(v2,v0,c),
+ *     w2 = E(v0,v1,c).  If A < 0, negate all four.
+ *   Coverage.  The triangle covers the texel iff w0 >= 0 && w1 >= 0 && w2 >= 0: the edges are closed, and w0+w1+w2 == A exactly.
+ *     Every (triangle, texel) pair that passes counts in `pairs`.
+ *   Ownership.  A covered texel belongs to the smallest key (meshId << 28) | primId among its covering triangles.
+ *   Outputs.  n = the number of owned texels; texels[0..n) are their indices y*W + x in ascending order;
+ *     hits[q] = {t = 0, i = (float)w0/(float)A, j = (float)w1/(float)A, k = (float)w2/(float)A, primId, meshId} of the owner of
+ *     texels[q], the int64 to f32 conversions rounding to nearest even and the divisions correctly rounded.  Entries at and beyond n
+ *     are untouched.
+ *   W, H: 1 .. 8192.  count: 1 .. PRT_HIP_MAX_BVH records; meshId below PRT_HIP_MAX_BVH, each at most once; primCount 1 .. 2^28.
+ *   The prt_atlas_mesh records are host memory, read before the call returns; their uv pointers follow the flags.  counts is HOST
+ *   memory and the call returns when it is filled: the one synchronous step (a bake needs n on the host anyway).  texels and hits have
+ *   a capacity of W*H entries.
+ *
+ * prt_hip_atlas_points.  Needs a scene (PRT_HIP_ESTATE without one).  Record q is a hit (primId in mesh order, as the rasteriser and
+ * prt_hip_query_nearest report it) and the texel it is for.  Every index read from caller memory is range-checked on the device as
+ * prt_hip_query_surface checks it: meshId < the scene's mesh count, primId < that mesh's primitive count.
+ *   A valid record gives the point
+ *     P = (i*p0 + j*p1) + k*p2 per component, p0 p1 p2 the triangle's corners as the scene holds them now, every product rounded
+ *         before the sums
+ *     N = the normal of prt_hip_query_surface for that hit: the normalised interpolation of the vertex normals, or the face normal
+ *         of a mesh without them
+ *     bias as given
+ *     set = (x % setTile) + setTile * (y % setTile) with x = texel % W, y = texel / W; setTile 1 .. 32.  A set at or above the
+ *         table's nSets is the caller's business: prt_hip_bake never follows it.
+ *   An invalid record gives the all-zero point with set = 0xffffffff, which prt_hip_bake answers with +0; nothing of the scene is
+ *   read for it.  t of a hit is ignored.
+ *   The call reads the scene as it is at that moment: after prt_hip_update_meshes, prt_hip_deform_meshes or an edit the same hits
+ *   give the moved surface's points without rasterising again, which is why the atlas stores barycentrics and not positions.
+ *   n: 1 .. 2^26 records; W: 1 .. 8192; reserved must be 0.
+ *
+ * prt_hip_atlas_resolve.  Needs no scene.
+ *   Every texel starts at +0 with mask 0.  texels[q] < W*H gets values[q*stride ..] and mask 1; an index at or beyond W*H is ignored;
+ *   with duplicate indices, which the rasteriser never produces, it is unspecified which value is stored.
+ *   Pass g = 1 .. gutter: a texel with mask 0 that has at least one 8-neighbour inside the image with mask in 1 .. g takes, per float,
+ *   the sum over those neighbours in the order dy = -1, 0, 1 outer, dx = -1, 0, 1 inner, starting from +0, divided by (float)count;
+ *   its mask becomes g + 1.  Texels filled in pass g are not read in pass g.  NaN values travel as given.
+ *   stride: 1 .. 48 floats per texel (3*C of the bake); gutter: 0 .. 64; n: 1 .. 2^26; mask may be NULL.
+ *
+ * Pointers, flags and stream as for the queries and the baker: DEVICE pointers by default (points 16-byte aligned, everything else
+ * 4-byte aligned, mask any), ordered after the work queued on stream and before what is queued next; points and resolve are
+ * asynchronous.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged through buffers the context owns, and the call returns
+ * with the answer.  Other flag bits are refused.  Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the
+ * outputs untouched: a NULL pointer, a parameter outside its range, reserved != 0, a misaligned device pointer.
+ * State: the calls read the scene (points only) and change nothing else in the context; none is a launch for prt_hip_get_stats.
+ * Not built: unwrapping or packing charts; conservative rasterisation; supersampled texels; seam stitching; atlases over ranks; a
+ * count of invalid records in atlas_points. ---- */
+typedef struct { uint32_t meshId; uint32_t primCount; const float* uv; /* 6*primCount: (u,v) of corners 0,1,2, mesh order */ } prt_atlas_mesh;
+typedef struct { uint32_t n; uint32_t rejected; uint32_t degenerate; uint32_t reserved; uint64_t pairs; } prt_atlas_counts;
+typedef struct { float bias; uint32_t setTile; uint32_t reserved[2]; } prt_atlas_point_params;
+int prt_hip_atlas_rasterize(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t count, const prt_atlas_mesh* meshes,
+                            uint32_t* texels /* capacity W*H */, prt_hit* hits /* capacity W*H */,
+                            prt_atlas_counts* counts /* HOST */, uint32_t flags, void* stream);
+int prt_hip_atlas_points(prt_hip_ctx* ctx, uint32_t n, uint32_t W, const uint32_t* texels, const prt_hit* hits,
+                         const prt_atlas_point_params* params, prt_bake_point* points, uint32_t flags, void* stream);
+int prt_hip_atlas_resolve(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t n, const uint32_t* texels,
+                          const float* values /* n*stride */, uint32_t stride /* 1 .. 48: 3*C of the bake */, uint32_t gutter /* 0 .. 64 */,
+                          float* image /* W*H*stride */, uint8_t* mask /* W*H, may be NULL */, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,24 @@ class BakeSets(C.Structure):
                 ("weights", C.c_void_p)]
 
 
+# prt_atlas_mesh / prt_atlas_counts / prt_atlas_point_params (include/prt_hip.h "lightmap atlases")
+class AtlasMesh(C.Structure):
+    """prt_atlas_mesh: uv (6 * primCount floats: (u, v) of corners 0, 1, 2, mesh order) is a device pointer, or a host pointer under
+    QUERY_HOST."""
+    _fields_ = [("meshId", C.c_uint32), ("primCount", C.c_uint32), ("uv", C.c_void_p)]
+
+
+class AtlasCounts(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("rejected", C.c_uint32), ("degenerate", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("n", "rejected", "degenerate", "pairs")}
+
+
+class AtlasPointParams(C.Structure):
+    _fields_ = [("bias", C.c_float), ("setTile", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 NODE_DTYPE = np.dtype([("lower", "<f4", 3), ("upper", "<f4", 3), ("primOrSecondNodeIndex", "<u4"),
                        ("triVectorIndex", "<u4"), ("primCount", "<u4"), ("splitAxis", "<u4")])
 MATERIAL_DTYPE = np.dtype([("diffuse", "<f4", 3), ("emissive", "<f4", 3), ("reflectionType", "<u4"),
@@ -222,6 +240,7 @@ EXPORTS = [
     "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
     "prt_hip_query_radiance",
     "prt_hip_bake_rays", "prt_hip_bake_reduce", "prt_hip_bake",
+    "prt_hip_atlas_rasterize", "prt_hip_atlas_points", "prt_hip_atlas_resolve",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -343,6 +362,9 @@ def _load(path, with_test_entry_points):
     L.prt_hip_bake_rays.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), vp, C.c_uint32, vp]
     L.prt_hip_bake_reduce.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), vp, vp, C.c_uint32, vp]
     L.prt_hip_bake.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), C.POINTER(RenderParams), vp, C.c_uint32, vp]
+    L.prt_hip_atlas_rasterize.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtlasMesh), vp, vp, C.POINTER(AtlasCounts), C.c_uint32, vp]
+    L.prt_hip_atlas_points.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AtlasPointParams), vp, C.c_uint32, vp]
+    L.prt_hip_atlas_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
@@ -599,6 +621,7 @@ class PathTracer:
         self._ctx = C.c_void_p()
         self._chk(L.prt_hip_create(device, C.byref(self._ctx)), "prt_hip_create")
         self.max_depth, self.rr_depth, self.seed = max_depth, rr_depth, seed
+        self._device = device
         self._scene = None
         self._camera = None
 
@@ -1259,6 +1282,103 @@ class PathTracer:
                                               out.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_bake_reduce")
         return out
 
+    # ---- lightmap atlases (include/prt_hip.h "lightmap atlases"): per-corner lightmap UVs in, a lightmap image out
+    def atlas_rasterize_device(self, W, H, d_uvs, prim_counts, d_texels, d_hits, stream=None):
+        """prt_hip_atlas_rasterize on device arrays: d_uvs {meshId: device pointer of 6 * primCount float32}, prim_counts {meshId:
+        primCount}, d_texels and d_hits device pointers with room for W * H entries.  Synchronous (the one step that is): returns the
+        counts as a dict, n = the owned texels."""
+        recs = (AtlasMesh * len(d_uvs))(*[AtlasMesh(meshId=m, primCount=prim_counts[m], uv=d_uvs[m]) for m in sorted(d_uvs)])
+        counts = AtlasCounts()
+        self._chk(self._L.prt_hip_atlas_rasterize(self._ctx, W, H, len(recs), recs, d_texels, d_hits, C.byref(counts), 0, stream),
+                  "prt_hip_atlas_rasterize")
+        return counts.as_dict()
+
+    def atlas_rasterize(self, uvs_per_mesh, W, H):
+        """The texels of a W x H atlas the UV triangles cover: uvs_per_mesh is a list by meshId (None: a mesh with no lightmap) or a
+        dict {meshId: uv}, uv (primCount, 3, 2) float32.  Returns (texels (n,) uint32 = y * W + x ascending, hits (n,) HIT_DTYPE with
+        t = 0, the owner's barycentrics at the texel centre, primId, meshId; counts dict).  Needs no scene."""
+        uvs = _atlas_uvs(uvs_per_mesh)
+        recs = (AtlasMesh * len(uvs))(*[AtlasMesh(meshId=m, primCount=len(uv), uv=uv.ctypes.data) for m, uv in sorted(uvs.items())])
+        texels, hits, counts = np.zeros(W * H, dtype=np.uint32), np.zeros(W * H, dtype=HIT_DTYPE), AtlasCounts()
+        self._chk(self._L.prt_hip_atlas_rasterize(self._ctx, W, H, len(recs), recs, texels.ctypes.data_as(C.c_void_p),
+                                                  hits.ctypes.data_as(C.c_void_p), C.byref(counts), QUERY_HOST, None), "prt_hip_atlas_rasterize")
+        return texels[:counts.n].copy(), hits[:counts.n].copy(), counts.as_dict()
+
+    def atlas_points_async(self, n, W, d_texels, d_hits, d_points, bias=1e-4, set_tile=1, stream=None):
+        """Queue prt_hip_atlas_points on device arrays: d_texels (n uint32), d_hits (n prt_hit), d_points (n prt_bake_point, 16-byte
+        aligned) are device pointers (int)."""
+        p = AtlasPointParams(bias=bias, setTile=set_tile)
+        self._chk(self._L.prt_hip_atlas_points(self._ctx, n, W, d_texels, d_hits, C.byref(p), d_points, 0, stream), "prt_hip_atlas_points")
+
+    def atlas_points(self, texels, hits, W, bias=1e-4, set_tile=1):
+        """(n,) BAKE_POINT_DTYPE: the bake points of the hits on the scene as it is now; set = (x % set_tile) + set_tile * (y % set_tile)
+        of the texel.  A hit outside the scene gives the all-zero point with set 0xffffffff, which bake() answers with +0."""
+        t = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+        if len(t) != len(h):
+            raise PrtError(f"atlas_points: {len(t)} texels for {len(h)} hits")
+        pts = np.zeros(len(h), dtype=BAKE_POINT_DTYPE)
+        p = AtlasPointParams(bias=bias, setTile=set_tile)
+        self._chk(self._L.prt_hip_atlas_points(self._ctx, len(h), W, t.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), C.byref(p),
+                                               pts.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_atlas_points")
+        return pts
+
+    def atlas_resolve_async(self, W, H, n, d_texels, d_values, stride, gutter, d_image, d_mask=None, stream=None):
+        """Queue prt_hip_atlas_resolve on device arrays: d_values n * stride float32, d_image W * H * stride float32, d_mask W * H bytes
+        or None."""
+        self._chk(self._L.prt_hip_atlas_resolve(self._ctx, W, H, n, d_texels, d_values, stride, gutter, d_image, d_mask, 0, stream),
+                  "prt_hip_atlas_resolve")
+
+    def atlas_resolve(self, texels, values, W, H, gutter=2):
+        """(image (H, W) + values.shape[1:] float32, mask (H, W) uint8): values (n, ...) at their texels, everything else +0, then
+        `gutter` dilation passes over the 8-neighbourhood; mask 0 = empty, 1 = a value, g + 1 = filled in pass g."""
+        t = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.ndim < 1 or len(v) != len(t):
+            raise PrtError(f"atlas_resolve: {len(t)} texels for values {v.shape}")
+        stride = int(v.size // max(len(t), 1))
+        image, mask = np.zeros((H, W) + v.shape[1:], dtype=np.float32), np.zeros((H, W), dtype=np.uint8)
+        self._chk(self._L.prt_hip_atlas_resolve(self._ctx, W, H, len(t), t.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), stride, gutter,
+                                                image.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), QUERY_HOST, None),
+                  "prt_hip_atlas_resolve")
+        return image, mask
+
+    def lightmap(self, uvs_per_mesh, W, H, dirs, weights, spp, seed=None, bias=1e-4, set_tile=1, gutter=2, exposure=None, max_depth=None):
+        """A baked lightmap of the uploaded scene: rasterise the lightmap UVs (uvs_per_mesh as for atlas_rasterize), make a bake point
+        per owned texel, bake() them under dirs / weights (as for bake(); a point's set is its texel's place in a set_tile x set_tile
+        tile) and resolve with `gutter` dilation passes.  Returns (image (H, W, C, 3) float32, mask (H, W) uint8).  Every array between
+        the four calls stays on the device: only the UVs and the table go up and only the image and the mask come down.  More than
+        2^24 rays are baked in parts of whole points, part i0 under seed + i0 * K, as include/prt_hip.h "baking" says; sets
+        last_atlas_counts and last_stats (of the last part)."""
+        uvs = _atlas_uvs(uvs_per_mesh)
+        d, w, table = make_bake_sets(dirs, weights)
+        K, Cc = table.K, table.C
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        image, mask = np.zeros((H, W, Cc, 3), dtype=np.float32), np.zeros((H, W), dtype=np.uint8)
+        with _DeviceArrays(self._device) as dev:
+            d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
+            d_texels, d_hits = dev.alloc(4 * W * H), dev.alloc(HIT_DTYPE.itemsize * W * H)
+            counts = self.atlas_rasterize_device(W, H, d_uv, {m: len(uv) for m, uv in uvs.items()}, d_texels, d_hits)
+            self.last_atlas_counts = counts
+            n = counts["n"]
+            if n == 0:
+                return image, mask
+            d_points, d_out = dev.alloc(BAKE_POINT_DTYPE.itemsize * n), dev.alloc(12 * Cc * n)
+            self.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias, set_tile=set_tile)
+            table.dirs, table.weights = dev.upload(d), dev.upload(w)
+            part = max(1, (1 << 24) // K)
+            first_seed = p.seed
+            for i0 in range(0, n, part):
+                p.seed = (first_seed + i0 * K) & 0xffffffff
+                self._chk(self._L.prt_hip_bake(self._ctx, min(part, n - i0), d_points + BAKE_POINT_DTYPE.itemsize * i0, C.byref(table), C.byref(p),
+                                               d_out + 12 * Cc * i0, 0, None), "prt_hip_bake")
+            d_image, d_mask = dev.alloc(image.nbytes), dev.alloc(mask.nbytes)
+            self.atlas_resolve_async(W, H, n, d_texels, d_out, 3 * Cc, gutter, d_image, d_mask)
+            self.last_stats = self.stats()  # synchronises the context's stream; raises on stack overflow
+            dev.download(image, d_image)
+            dev.download(mask, d_mask)
+        return image, mask
+
     def pick(self, x, y):
         """What lies under pixel (x, y) of the current camera: the ray through the pixel's centre (the position guide's ray) ->
         (hit, surface), one element of HIT_DTYPE and of SURFACE_DTYPE; hit["t"] == -1 for the background."""
@@ -1459,6 +1579,62 @@ def make_bake_sets(dirs, weights):
     table = BakeSets(K=shape[1], C=1 if w is None else w.shape[2], nSets=shape[0], reserved=0,
                      dirs=None if d is None else d.ctypes.data, weights=None if w is None else w.ctypes.data)
     return d, w, table
+
+
+# ----------------------------------------------------------------------------- lightmap atlases
+def _atlas_uvs(uvs_per_mesh):
+    """{meshId: (primCount, 3, 2) float32} from a list by meshId (None: no lightmap for that mesh) or a dict."""
+    items = uvs_per_mesh.items() if isinstance(uvs_per_mesh, dict) else enumerate(uvs_per_mesh)
+    uvs = {}
+    for m, uv in items:
+        if uv is None:
+            continue
+        a = np.ascontiguousarray(uv, dtype=np.float32)
+        if a.size == 0 or a.size % 6 != 0:
+            raise PrtError(f"atlas: the UVs of mesh {m} must be (primCount, 3, 2), not {a.shape}")
+        uvs[int(m)] = a.reshape(-1, 3, 2)
+    if not uvs:
+        raise PrtError("atlas: no mesh has lightmap UVs")
+    return uvs
+
+
+class _DeviceArrays:
+    """Device memory of one lightmap() call, from the HIP runtime the library is linked to; freed on exit.  The copies run on the
+    null stream, which the context's (blocking) stream is ordered with."""
+
+    def __init__(self, device):
+        h = C.CDLL("libamdhip64.so")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipFree.argtypes = [C.c_void_p]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self._h, self._held, self._device = h, [], device
+
+    def __enter__(self):
+        if self._h.hipSetDevice(self._device) != 0:
+            raise PrtError(f"lightmap: hipSetDevice({self._device}) failed")
+        return self
+
+    def __exit__(self, *exc):
+        for p in self._held:
+            self._h.hipFree(p)
+        self._held = []
+
+    def alloc(self, nbytes):
+        p = C.c_void_p()
+        if self._h.hipMalloc(C.byref(p), max(int(nbytes), 64)) != 0:
+            raise PrtError(f"lightmap: hipMalloc of {nbytes} bytes failed")
+        self._held.append(p)
+        return p.value
+
+    def upload(self, a):
+        p = self.alloc(a.nbytes)
+        if self._h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) != 0:
+            raise PrtError("lightmap: hipMemcpy to the device failed")
+        return p
+
+    def download(self, a, p):
+        if self._h.hipMemcpy(a.ctypes.data, p, a.nbytes, 2) != 0:
+            raise PrtError("lightmap: hipMemcpy from the device failed")
 
 
 def bake_cosine_set(K, rng):

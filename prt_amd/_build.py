@@ -24,6 +24,7 @@ SOURCES = [
     "prt_display.hip",
     "prt_query.hip",
     "prt_bake.hip",
+    "prt_atlas.hip",
     "prt_rowtests.hip",
     "host/prt_host.cpp",
     "host/prt_bvh.cpp",

@@ -198,6 +198,19 @@ struct prt_hip_ctx {
     DevBuf<float> bkRad;               // PRT_HIP_QUERY_HOST also the staged rays of bake_rays and radiances of bake_reduce
     DevBuf<prt_bake_point> bkPoints;   // PRT_HIP_QUERY_HOST: the caller's points, table and answer, staged on the device
     DevBuf<float> bkDirs, bkWeights, bkOut;
+    // lightmap atlases (prt_atlas.hip): allocated on first use
+    DevBuf<uint32_t> atOwner;          // prt_hip_atlas_rasterize: per texel the smallest key (meshId << 28) | primId that covers it,
+    DevBuf<uint8_t> atFlag;            // 1 = the texel is owned, and
+    DevBuf<uint32_t> atIndex;          // its index: what the selection compacts
+    DevBuf<char> atTemp;               // hipcub scratch of the selection
+    DevBuf<unsigned long long> atCounts;    // {pairs, rejected, degenerate, n} of the last rasterise and
+    HostBuf<unsigned long long> atCountsHost; // their pinned host copy
+    DevBuf<float> atUV;                // PRT_HIP_QUERY_HOST: the caller's arrays and the answers, staged on the device
+    DevBuf<uint32_t> atTexels;
+    DevBuf<prt_hit> atHits;
+    DevBuf<prt_bake_point> atPoints;
+    DevBuf<float> atValues, atImage;
+    DevBuf<uint8_t> atMask;            // also the mask of a prt_hip_atlas_resolve on device arrays whose caller wants none
 };
 
 
@@ -241,6 +254,9 @@ int prt_frame_probe(prt_hip_ctx* c, uint32_t n, const prt_ray* d_rays, const prt
 // name; and the answer to a NULL argument (ENODEVICE on a machine without a device, EINVAL otherwise)
 int prt_check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags, const char* what);
 int prt_null_argument(const char* what);
+// prt_query.hip, shared with prt_hip_atlas_points (prt_atlas.hip): the inverse of triPrim for the uploaded scene (prt_hip_ctx::qInv),
+// built on the context's stream by the first use after an upload
+int prt_query_inverse_ready(prt_hip_ctx* c);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
 // prt_upload.hip, the ONE place that writes a pointer of c->sc: each from its owner in c->arr (null where the owner is empty).  Called

@@ -214,37 +214,9 @@ int launch_trace(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits,
     return prt_batch_end(c, L, any ? "query_any_kernel" : "query_nearest_kernel");
 }
 
-// The inverse table of the uploaded scene on the context's stream (first use after an upload).
-int inverse_ready(prt_hip_ctx* c)
-{
-    if (c->qInv) return PRT_HIP_OK;
-    const PrtRefit& R = c->rf;
-    const uint64_t slots = R.slotVtx.size() / 3;
-    if (slots == 0 || slots > 0xffffffffull || !R.slotVtx || R.meshes.size() != c->sc.bvhCount)
-        return fail(PRT_HIP_ESTATE, "query_surface: the scene holds no triangle slots");
-    IndexArgs a{};
-    a.triPrim = c->sc.triPrim;
-    a.slotVtx = R.slotVtx;
-    a.slots = (uint32_t)slots;
-    a.meshes = c->sc.bvhCount;
-    for (uint32_t m = 0; m < a.meshes; m++) {
-        const PrtRefitMesh& rm = R.meshes[m];
-        if ((uint64_t)rm.slotBase + rm.slotCount > slots || rm.slotBase != c->sc.primBase[m])
-            return fail(PRT_HIP_ESTATE, "query_surface: slot range outside the scene");
-        a.slotBase[m] = rm.slotBase;
-        a.slotCount[m] = rm.slotCount;
-    }
-    HIP_TRY(c->qInv.fit(slots, c->stream));
-    a.inv = c->qInv;
-    HIP_TRY(hipMemsetAsync(c->qInv, 0xff, slots * sizeof(uint32_t), c->stream));
-    const uint32_t blocks = std::min<uint32_t>((a.slots + 255u) / 256u, 65535u);
-    hipLaunchKernelGGL(query_index_kernel, dim3(blocks), dim3(256), 0, c->stream, a);
-    return prt_launched("query_index_kernel");
-}
-
 int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surf)
 {
-    int rc = inverse_ready(c);
+    int rc = prt_query_inverse_ready(c);
     if (rc) return rc;
     HIP_TRY(c->qCounts.fit(1, c->stream));
     HIP_TRY(hipMemsetAsync(c->qCounts, 0, sizeof(unsigned long long), c->stream));
@@ -341,6 +313,35 @@ int radiance_direct(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_r
 }
 
 } // namespace
+
+// The inverse table of the uploaded scene on the context's stream (first use after an upload); prt_hip_atlas_points
+// (prt_atlas.hip) needs it too.
+int prt_query_inverse_ready(prt_hip_ctx* c)
+{
+    if (c->qInv) return PRT_HIP_OK;
+    const PrtRefit& R = c->rf;
+    const uint64_t slots = R.slotVtx.size() / 3;
+    if (slots == 0 || slots > 0xffffffffull || !R.slotVtx || R.meshes.size() != c->sc.bvhCount)
+        return fail(PRT_HIP_ESTATE, "query_surface: the scene holds no triangle slots");
+    IndexArgs a{};
+    a.triPrim = c->sc.triPrim;
+    a.slotVtx = R.slotVtx;
+    a.slots = (uint32_t)slots;
+    a.meshes = c->sc.bvhCount;
+    for (uint32_t m = 0; m < a.meshes; m++) {
+        const PrtRefitMesh& rm = R.meshes[m];
+        if ((uint64_t)rm.slotBase + rm.slotCount > slots || rm.slotBase != c->sc.primBase[m])
+            return fail(PRT_HIP_ESTATE, "query_surface: slot range outside the scene");
+        a.slotBase[m] = rm.slotBase;
+        a.slotCount[m] = rm.slotCount;
+    }
+    HIP_TRY(c->qInv.fit(slots, c->stream));
+    a.inv = c->qInv;
+    HIP_TRY(hipMemsetAsync(c->qInv, 0xff, slots * sizeof(uint32_t), c->stream));
+    const uint32_t blocks = std::min<uint32_t>((a.slots + 255u) / 256u, 65535u);
+    hipLaunchKernelGGL(query_index_kernel, dim3(blocks), dim3(256), 0, c->stream, a);
+    return prt_launched("query_index_kernel");
+}
 
 // ENODEVICE on a machine without a device (where no context can exist), EINVAL otherwise
 int prt_null_argument(const char* what)

@@ -23,6 +23,13 @@ K = 64 and K = 256 directions, 8 spp, depth 8: (a) one prt_hip_bake on device ar
 and a numpy mean, (c) the frame-kernel launch inside (a); and the two new kernels alone.  The ratio to read is (a) / (c).
 
     python tools/query_bench.py --bake [--reps 5] [--out F]
+
+--atlas: the lightmap atlas calls (include/prt_hip.h "lightmap atlases").  Every triangle of the scene gets a cell of its own in a grid,
+into a 1024 x 1024 and a 4096 x 4096 atlas; one cosine set of K = 16 directions, 8 spp, depth 8, gutter 2: each of the three new calls
+alone on device arrays, lightmap() end to end against the frame-kernel launches inside it, and ONE run of the route it replaces: the
+numpy rasteriser, points and gutter fill of tests/prt_atlas_ref.py around bake() on host arrays.
+
+    python tools/query_bench.py --atlas [--reps 5] [--out F]
 """
 import argparse
 import ctypes as C
@@ -210,6 +217,95 @@ def bake(args):
     emit(out, args.out)
 
 
+def atlas(args):
+    """Per atlas size: rasterize, points and resolve alone on device arrays (wall time from a synchronised stream to the
+    synchronisation behind the call; rasterize synchronises itself), lightmap() end to end (wall) against kernelMs of the prt_hip_bake
+    launches inside it, and the host route once: numpy rasteriser, numpy points with query_surface's normals, bake() on host arrays in
+    parts of 2^24 rays, numpy gutter fill.  The host route's image must equal lightmap()'s byte for byte."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import prt_atlas_ref as AR
+    spp, depth, seed, K, gutter, bias = 8, 8, 12345, 16, 2, 1e-4
+    scene, _, _ = prt_amd.setup_atrium_standin(64, 64, tris=262000, seed=1)
+    t = prt_amd.PathTracer(max_depth=depth, seed=seed)
+    t.upload_scene(scene)
+    meshes = scene.arrays()["meshes"]
+    prims = [len(m["indices"]) for m in meshes]
+    total = sum(prims)
+    G = int(np.ceil(np.sqrt(total)))
+    cell = np.arange(total)
+    corner = np.array([(0.1, 0.1), (0.9, 0.1), (0.1, 0.9)])
+    uv_all = ((np.stack([cell % G, cell // G], axis=1)[:, None, :] + corner[None]) / G).astype(np.float32)
+    uvs = {m: uv_all[sum(prims[:m]):sum(prims[:m + 1])] for m in range(len(prims))}
+    d, w = prt_amd.bake_cosine_set(K, np.random.default_rng(K))
+    out = {"workload": "c3_sponza_standin", "layout": f"{total} triangles of {len(prims)} meshes, one cell each of a {G} x {G} grid", "K": K,
+           "spp": spp, "max_depth": depth, "gutter": gutter, "reps": args.reps, "device": t.device_info()[0],
+           "compute_units": t.device_info()[1], "source_sha16": prt_amd.loaded_source_sha16(), "atlas": {}}
+    sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
+    for W in (1024, 4096):
+        H = W
+        d_uv = {m: DeviceArray(uv) for m, uv in uvs.items()}
+        bufs = [DeviceArray(np.zeros(W * H, np.uint32)), DeviceArray(np.zeros(W * H, prt_amd.HIT_DTYPE))]
+        d_texels, d_hits = (b.ptr.value for b in bufs)
+        rasterize = lambda: t.atlas_rasterize_device(W, H, {m: b.ptr.value for m, b in d_uv.items()}, dict(enumerate(prims)), d_texels, d_hits)  # noqa: E731
+        counts = rasterize()
+        n = counts["n"]
+        bufs += [DeviceArray(np.zeros(n, prt_amd.BAKE_POINT_DTYPE)), DeviceArray(np.zeros((n, 3), np.float32)),
+                 DeviceArray(np.zeros((W * H, 3), np.float32)), DeviceArray(np.zeros(W * H, np.uint8))]
+        d_points, d_values, d_image, d_mask = (b.ptr.value for b in bufs[2:])
+        times = {k: [] for k in ("rasterize_wall", "points_wall", "resolve_wall", "lightmap_wall", "bake_kernels")}
+        image = mask = None
+        for rep in range(2 + args.reps):
+            keep = rep >= 2
+            for name, call in (("rasterize_wall", rasterize), ("points_wall", lambda: t.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias)),
+                               ("resolve_wall", lambda: t.atlas_resolve_async(W, H, n, d_texels, d_values, 3, gutter, d_image, d_mask))):
+                sync()
+                t0 = time.perf_counter()
+                call()
+                sync()
+                if keep:
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+            sync()
+            t0 = time.perf_counter()
+            image, mask = t.lightmap(uvs, W, H, d, w, spp, bias=bias, gutter=gutter)
+            dt = (time.perf_counter() - t0) * 1e3
+            if keep:
+                times["lightmap_wall"].append(dt)
+                times["bake_kernels"].append(t.last_stats["kernelMsSum"])  # (a bake of more than 2^24 rays is several launches)
+        launches, rays_last = t.last_stats["kernelLaunches"], t.last_stats["raysTraced"]
+        for b in bufs + list(d_uv.values()):
+            b.free()
+        # the route it replaces, once
+        host = {}
+        t0 = time.perf_counter()
+        texels, hits, host_counts = AR.rasterize(uvs, W, H)
+        host["numpy_rasterize"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        zero = np.zeros((len(hits), 3), np.float32)
+        pts = AR.points(texels, hits, W, [(m["indices"], m["positions"]) for m in meshes], t.query_surface(zero, zero, hits)["normal"], bias, 1)
+        host["numpy_points_with_query_surface"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        part = (1 << 24) // K
+        baked = np.concatenate([t.bake(pts["P"][i0:i0 + part], pts["N"][i0:i0 + part], d, w, spp, bias=pts["bias"][i0:i0 + part],
+                                       seed=(seed + i0 * K) & 0xffffffff) for i0 in range(0, len(pts), part)])
+        host["bake_on_host_arrays"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        host_image, host_mask = AR.resolve(texels, baked.reshape(len(texels), -1), W, H, gutter)
+        host["numpy_resolve"] = time.perf_counter() - t0
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        new_calls = med["rasterize_wall"] + med["points_wall"] + med["resolve_wall"]
+        out["atlas"][f"{W}x{H}"] = {
+            "counts": counts, "host_counts_equal": host_counts == counts, "bake_launches": launches, "rays_traced_by_the_last_launch": rays_last,
+            "ms": {k: spread(v) for k, v in times.items()}, "lightmap_over_bake_kernels": med["lightmap_wall"] / med["bake_kernels"],
+            "three_calls_share_of_bake_kernels": new_calls / med["bake_kernels"],
+            "host_route_ms": {k: v * 1e3 for k, v in host.items()}, "host_route_total_ms": sum(host.values()) * 1e3,
+            "host_route_over_lightmap": sum(host.values()) * 1e3 / med["lightmap_wall"],
+            "host_route_without_bake_over_three_calls": (sum(host.values()) - host["bake_on_host_arrays"]) * 1e3 / new_calls,
+            "images_equal": image.tobytes() == host_image.tobytes() and mask.tobytes() == host_mask.tobytes(),
+            "lit_fraction_of_owned": float((image.reshape(-1, 3)[mask.reshape(-1) == 1] != 0).any(axis=1).mean())}
+    t.close()
+    emit(out, args.out)
+
+
 def host_rays(pts, d):
     """What a baker wrote in numpy: a tangent frame per point, the K directions rotated into it, the origin tiled."""
     N = pts["N"].astype(np.float64)
@@ -230,12 +326,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--radiance", action="store_true")
     ap.add_argument("--bake", action="store_true")
+    ap.add_argument("--atlas", action="store_true")
     args = ap.parse_args()
     prt_amd.build()
     if args.radiance:
         return radiance(args)
     if args.bake:
         return bake(args)
+    if args.atlas:
+        return atlas(args)
     W, H = (int(v) for v in args.size.split("x"))
     scene, camera, _ = prt_amd.setup_atrium_standin(W, H, tris=262000, seed=1)
     t = prt_amd.PathTracer(max_depth=8, test_entry_points=True)
