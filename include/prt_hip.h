@@ -771,8 +771,9 @@ int prt_hip_upload(prt_hip_ctx* ctx, const float* rgb_host, uint32_t x0, uint32_
  * n: 1 .. 2^30 rays, any count (PRT_HIP_EINVAL otherwise).  Pointers: DEVICE pointers by default; rays and surfaces must be 16-byte
  * aligned, hits 4-byte aligned, occluded any; anything else is refused with PRT_HIP_EINVAL and a message before anything is launched.
  * stream as in prt_hip_render: the query is ordered after the work queued on it and before what is queued next; asynchronous.  With
- * PRT_HIP_QUERY_HOST in flags all array pointers are HOST pointers: the arrays are staged through buffers the context owns (grown on
- * demand, freed with the context) and the call returns when the answers are in host memory.  Other flag bits are refused.
+ * PRT_HIP_QUERY_HOST in flags all array pointers are HOST pointers: the arrays are staged in the one arena the context owns for the
+ * host arrays of all its calls (grown to the largest call, freed with the context) and the call returns when the answers are in host
+ * memory.  Other flag bits are refused.
  * For prt_hip_get_stats nearest and any are launches like the position pass, timed as a render: kernelMs, raysTraced = n
  * (occludedTraced = n too for any), and a stack overflow is reported there.  query_surface is not a launch for the statistics.
  * One persistent launch per call, a few workgroups per compute unit whatever n is. ---- */
@@ -782,7 +783,7 @@ typedef struct { float P[3]; float t;                /* org + t*dir per componen
                  float shadingNormal[3]; uint32_t meshMaterial; /* Material::sampleBump's normal; index within the mesh */
                  float uv[2]; uint32_t primId, meshId;
                  float diffuse[3]; uint32_t pad; } prt_surface;                        /* 80 bytes */
-#define PRT_HIP_QUERY_HOST 1u  /* all array pointers are HOST pointers: staged through context-owned buffers, the call is synchronous */
+#define PRT_HIP_QUERY_HOST 1u  /* all array pointers are HOST pointers: staged in the context's arena, the call is synchronous */
 
 int prt_hip_query_nearest(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces /* may be NULL */,
                           uint32_t flags, void* stream);
@@ -813,7 +814,7 @@ int prt_hip_query_get_counts(prt_hip_ctx* ctx, uint64_t* invalidHits); /* synchr
  * nranks 1 (probes are not split over ranks); countTraffic must be 0 (the probe kernel has no counting build); tileSize is ignored.
  * n: 1 .. 2^24 probes.  Anything else is PRT_HIP_EINVAL with a message, refused before anything is launched, radiance untouched.
  * Pointers, flags and stream as for the other queries: DEVICE pointers by default, rays 16-byte aligned and radiance 4-byte aligned;
- * with PRT_HIP_QUERY_HOST both are HOST pointers staged through the context's buffers and the call is synchronous; other flag bits
+ * with PRT_HIP_QUERY_HOST both are HOST pointers staged in the context's arena and the call is synchronous; other flag bits
  * are refused; the query is ordered after the work queued on stream and before what is queued next.
  * State: needs a scene and NO camera (PRT_HIP_ESTATE without a scene).  It reads the scene and changes nothing else: the camera, the
  * accumulator, the moments, the guides, the position plane, the history, the display state and the framebuffer are untouched, and so
@@ -867,13 +868,13 @@ int prt_hip_query_radiance(prt_hip_ctx* ctx, uint32_t n, const prt_ray* rays, co
  * bake_reduce no directions: that pointer of the table may be NULL there.
  * Pointers: DEVICE pointers by default, sets->dirs and sets->weights included (the prt_bake_sets record itself is host memory, read
  * before the call returns); points and rays 16-byte aligned, floats 4-byte aligned; asynchronous, ordered after the work queued on
- * stream and before what is queued next, as the queries are.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged through
- * buffers the context owns, and the call returns with the answer.  Other flag bits are refused.
+ * stream and before what is queued next, as the queries are.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged in
+ * the context's arena, and the call returns with the answer.  Other flag bits are refused.
  * Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the outputs untouched: a NULL pointer; K outside
  * 1 .. 4096, C outside 1 .. 16, nSets outside 1 .. 1024; reserved != 0; n = 0 or n*K > 2^24; for prt_hip_bake whatever
  * prt_hip_query_radiance refuses of params.  prt_hip_bake without a scene is PRT_HIP_ESTATE.
  * State: prt_hip_bake reads the scene and changes nothing else: the camera, the accumulator, the moments, the guides, the history,
- * the display state and the framebuffer are untouched, and so are the staging buffers of the queries.
+ * the display state and the framebuffer are untouched, and so is the staging arena of the host-array calls.
  * Not built: batches beyond 2^24 rays (the caller splits by points and passes seed + i0*K for the part that starts at point i0);
  * per-point validity or back-face counts; splitting over ranks. ---- */
 typedef struct { float P[3]; float bias; float N[3]; uint32_t set; } prt_bake_point;   /* 32 bytes, 16-byte aligned */
@@ -950,7 +951,7 @@ int prt_hip_bake(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, con
  *
  * Pointers, flags and stream as for the queries and the baker: DEVICE pointers by default (points 16-byte aligned, everything else
  * 4-byte aligned, mask any), ordered after the work queued on stream and before what is queued next; points and resolve are
- * asynchronous.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged through buffers the context owns, and the call returns
+ * asynchronous.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged in the context's arena, and the call returns
  * with the answer.  Other flag bits are refused.  Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the
  * outputs untouched: a NULL pointer, a parameter outside its range, reserved != 0, a misaligned device pointer.
  * State: the calls read the scene (points only) and change nothing else in the context; none is a launch for prt_hip_get_stats.

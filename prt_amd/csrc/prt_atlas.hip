@@ -285,17 +285,9 @@ __global__ __launch_bounds__(256) void atlas_gutter_kernel(ResolveArgs A, uint32
 }
 
 // ============================================================================ host side
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 uint32_t atlas_blocks(const prt_hip_ctx* c, uint64_t wanted)
 {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(wanted, (uint64_t)std::max(c->computeUnits, 1) * PRT_ATLAS_BLOCKS_PER_CU));
-}
-
-int check_flags(uint32_t flags, const char* what)
-{
-    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
-    return PRT_HIP_OK;
 }
 
 int check_size(uint32_t W, uint32_t H, const char* what)
@@ -368,44 +360,6 @@ void read_counts(const prt_hip_ctx* c, prt_atlas_counts* out)
     out->pairs = h[0];
 }
 
-int rasterize_staged(prt_hip_ctx* c, uint32_t W, uint32_t H, AtlasMeshes M, uint32_t* texels, prt_hit* hits, prt_atlas_counts* counts)
-{
-    hipStream_t s = c->stream;
-    HIP_TRY(c->atUV.grow(6 * (size_t)M.first[PRT_MAX_BVH], s));
-    HIP_TRY(c->atTexels.grow((size_t)W * H, s));
-    HIP_TRY(c->atHits.grow((size_t)W * H, s));
-    for (uint32_t m = 0; m < PRT_MAX_BVH; m++) {
-        if (!M.uv[m]) continue;
-        float* d = c->atUV + 6 * (size_t)M.first[m];
-        HIP_TRY(hipMemcpyAsync(d, M.uv[m], 6 * (size_t)(M.first[m + 1] - M.first[m]) * sizeof(float), hipMemcpyHostToDevice, s));
-        M.uv[m] = d;
-    }
-    int rc = launch_rasterize(c, W, H, M, c->atTexels, c->atHits);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    read_counts(c, counts);
-    if (counts->n) { // entries at and beyond n stay as the caller left them
-        HIP_TRY(hipMemcpyAsync(texels, c->atTexels, (size_t)counts->n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(hits, c->atHits, (size_t)counts->n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return PRT_HIP_OK;
-}
-
-int rasterize_direct(prt_hip_ctx* c, uint32_t W, uint32_t H, const AtlasMeshes& M, uint32_t* texels, prt_hit* hits, prt_atlas_counts* counts,
-                     void* stream)
-{
-    bool ok = aligned(texels, 4) && aligned(hits, 4);
-    for (uint32_t m = 0; m < PRT_MAX_BVH; m++) ok = ok && aligned(M.uv[m], 4);
-    if (!ok) return fail(PRT_HIP_EINVAL, "atlas_rasterize: uv, texels and hits must be 4-byte aligned");
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_rasterize(c, W, H, M, texels, hits))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream)); // the one synchronous step: a bake needs n on the host
-    read_counts(c, counts);
-    return prt_stream_leave(c, caller);
-}
-
 // ---------------------------------------------------------------------------- points
 int launch_points(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels, const prt_hit* hits, const prt_atlas_point_params& p,
                   prt_bake_point* points)
@@ -414,8 +368,7 @@ int launch_points(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels
     if (rc) return rc;
     PointsArgs A{};
     A.sc = c->sc;
-    for (uint32_t m = 0; m < c->sc.bvhCount && m < PRT_MAX_BVH; m++) // (as query_surface's: prt_query.hip query_meshes)
-        A.primCount[m] = m < c->rf.meshes.size() ? std::min(c->rf.meshes[m].primCount, c->rf.meshes[m].slotCount) : 0u;
+    prt_query_prim_counts(c, A.primCount);
     A.n = n;
     A.W = W;
     A.setTile = p.setTile;
@@ -426,33 +379,6 @@ int launch_points(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels
     A.points = (float4*)points;
     hipLaunchKernelGGL(atlas_points_kernel, dim3(atlas_blocks(c, (n + 255u) / 256u)), dim3(256), 0, c->stream, A);
     return prt_launched("atlas_points_kernel");
-}
-
-int points_staged(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels, const prt_hit* hits, const prt_atlas_point_params& p,
-                  prt_bake_point* points)
-{
-    hipStream_t s = c->stream;
-    HIP_TRY(c->atTexels.grow(n, s));
-    HIP_TRY(c->atHits.grow(n, s));
-    HIP_TRY(c->atPoints.grow(n, s));
-    HIP_TRY(hipMemcpyAsync(c->atTexels, texels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->atHits, hits, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
-    int rc = launch_points(c, n, W, c->atTexels, c->atHits, p, c->atPoints);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(points, c->atPoints, (size_t)n * sizeof(prt_bake_point), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PRT_HIP_OK;
-}
-
-int points_direct(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels, const prt_hit* hits, const prt_atlas_point_params& p,
-                  prt_bake_point* points, void* stream)
-{
-    if (!aligned(texels, 4) || !aligned(hits, 4) || !aligned(points, 16))
-        return fail(PRT_HIP_EINVAL, "atlas_points: points must be 16-byte aligned, texels and hits 4-byte aligned");
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_points(c, n, W, texels, hits, p, points))) return rc;
-    return prt_stream_leave(c, caller);
 }
 
 // ---------------------------------------------------------------------------- resolve
@@ -472,42 +398,6 @@ int launch_resolve(prt_hip_ctx* c, const ResolveArgs& A, uint32_t gutter)
     return PRT_HIP_OK;
 }
 
-int resolve_staged(prt_hip_ctx* c, ResolveArgs A, uint32_t gutter, float* image, uint8_t* mask)
-{
-    hipStream_t s = c->stream;
-    const size_t total = (size_t)A.W * A.H, nv = (size_t)A.n * A.stride;
-    HIP_TRY(c->atTexels.grow(A.n, s));
-    HIP_TRY(c->atValues.grow(nv, s));
-    HIP_TRY(c->atImage.grow(total * A.stride, s));
-    HIP_TRY(c->atMask.grow(total, s));
-    HIP_TRY(hipMemcpyAsync(c->atTexels, A.texels, (size_t)A.n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->atValues, A.values, nv * sizeof(float), hipMemcpyHostToDevice, s));
-    A.texels = c->atTexels;
-    A.values = c->atValues;
-    A.image = c->atImage;
-    A.mask = c->atMask;
-    int rc = launch_resolve(c, A, gutter);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(image, c->atImage, total * A.stride * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (mask) HIP_TRY(hipMemcpyAsync(mask, c->atMask, total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PRT_HIP_OK;
-}
-
-int resolve_direct(prt_hip_ctx* c, ResolveArgs A, uint32_t gutter, void* stream)
-{
-    if (!aligned(A.texels, 4) || !aligned(A.values, 4) || !aligned(A.image, 4))
-        return fail(PRT_HIP_EINVAL, "atlas_resolve: texels, values and image must be 4-byte aligned");
-    if (!A.mask) { // the passes need one: the context's
-        HIP_TRY(c->atMask.grow((size_t)A.W * A.H, c->stream));
-        A.mask = c->atMask;
-    }
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_resolve(c, A, gutter))) return rc;
-    return prt_stream_leave(c, caller);
-}
-
 } // namespace
 
 extern "C" {
@@ -518,9 +408,19 @@ int prt_hip_atlas_rasterize(prt_hip_ctx* c, uint32_t W, uint32_t H, uint32_t cou
     if (!c || !meshes || !texels || !hits || !counts) return prt_null_argument("atlas_rasterize");
     AtlasMeshes M;
     int rc;
-    if ((rc = check_flags(flags, "atlas_rasterize")) || (rc = check_size(W, H, "atlas_rasterize")) || (rc = check_meshes(count, meshes, &M))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    return (flags & PRT_HIP_QUERY_HOST) ? rasterize_staged(c, W, H, M, texels, hits, counts) : rasterize_direct(c, W, H, M, texels, hits, counts, stream);
+    if ((rc = prt_check_flags(flags, "atlas_rasterize")) || (rc = check_size(W, H, "atlas_rasterize")) || (rc = check_meshes(count, meshes, &M))) return rc;
+    // texels and hits have room for W*H entries; the per-mesh uv arrays follow, by meshId
+    PrtIoArray io[2 + PRT_MAX_BVH] = {prt_io_out(texels, (size_t)W * H * sizeof(uint32_t), 4), prt_io_out(hits, (size_t)W * H * sizeof(prt_hit), 4)};
+    for (uint32_t m = 0; m < PRT_MAX_BVH; m++) io[2 + m] = prt_io_in(M.uv[m], 6 * (size_t)(M.first[m + 1] - M.first[m]) * sizeof(float), 4);
+    return prt_run_io(c, flags, stream, "atlas_rasterize: uv, texels and hits must be 4-byte aligned", io, 2 + PRT_MAX_BVH, [&]() {
+        for (uint32_t m = 0; m < PRT_MAX_BVH; m++) M.uv[m] = io[2 + m].as<float>();
+        if (int e = launch_rasterize(c, W, H, M, io[0].as<uint32_t>(), io[1].as<prt_hit>())) return e;
+        HIP_TRY(hipStreamSynchronize(c->stream)); // the one synchronous step: a bake needs n on the host
+        read_counts(c, counts);
+        io[0].bytes = (size_t)counts->n * sizeof(uint32_t); // entries at and beyond n stay as the caller left them
+        io[1].bytes = (size_t)counts->n * sizeof(prt_hit);
+        return PRT_HIP_OK;
+    });
 }
 
 int prt_hip_atlas_points(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t* texels, const prt_hit* hits, const prt_atlas_point_params* params,
@@ -528,15 +428,17 @@ int prt_hip_atlas_points(prt_hip_ctx* c, uint32_t n, uint32_t W, const uint32_t*
 {
     if (!c || !texels || !hits || !params || !points) return prt_null_argument("atlas_points");
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, "atlas_points: upload a scene first");
-    int rc = check_flags(flags, "atlas_points");
+    int rc = prt_check_flags(flags, "atlas_points");
     if (rc) return rc;
     if (n < 1 || n > PRT_ATLAS_MAX_RECORDS) return fail(PRT_HIP_EINVAL, "atlas_points: n must be 1 .. 2^26");
     if (W < 1 || W > PRT_ATLAS_MAX_DIM) return fail(PRT_HIP_EINVAL, "atlas_points: W must be 1 .. 8192");
     const prt_atlas_point_params p = *params;
     if (p.setTile < 1 || p.setTile > PRT_ATLAS_MAX_TILE) return fail(PRT_HIP_EINVAL, "atlas_points: setTile must be 1 .. 32");
     if (p.reserved[0] != 0 || p.reserved[1] != 0) return fail(PRT_HIP_EINVAL, "atlas_points: reserved must be 0");
-    HIP_TRY(hipSetDevice(c->device));
-    return (flags & PRT_HIP_QUERY_HOST) ? points_staged(c, n, W, texels, hits, p, points) : points_direct(c, n, W, texels, hits, p, points, stream);
+    PrtIoArray io[3] = {prt_io_in(texels, (size_t)n * sizeof(uint32_t), 4), prt_io_in(hits, (size_t)n * sizeof(prt_hit), 4),
+                        prt_io_out(points, (size_t)n * sizeof(prt_bake_point), 16)};
+    return prt_run_io(c, flags, stream, "atlas_points: points must be 16-byte aligned, texels and hits 4-byte aligned", io, 3,
+                      [&]() { return launch_points(c, n, W, io[0].as<uint32_t>(), io[1].as<prt_hit>(), p, io[2].as<prt_bake_point>()); });
 }
 
 int prt_hip_atlas_resolve(prt_hip_ctx* c, uint32_t W, uint32_t H, uint32_t n, const uint32_t* texels, const float* values, uint32_t stride,
@@ -544,13 +446,21 @@ int prt_hip_atlas_resolve(prt_hip_ctx* c, uint32_t W, uint32_t H, uint32_t n, co
 {
     if (!c || !texels || !values || !image) return prt_null_argument("atlas_resolve");
     int rc;
-    if ((rc = check_flags(flags, "atlas_resolve")) || (rc = check_size(W, H, "atlas_resolve"))) return rc;
+    if ((rc = prt_check_flags(flags, "atlas_resolve")) || (rc = check_size(W, H, "atlas_resolve"))) return rc;
     if (n < 1 || n > PRT_ATLAS_MAX_RECORDS) return fail(PRT_HIP_EINVAL, "atlas_resolve: n must be 1 .. 2^26");
     if (stride < 1 || stride > PRT_ATLAS_MAX_STRIDE) return fail(PRT_HIP_EINVAL, "atlas_resolve: stride must be 1 .. 48");
     if (gutter > PRT_ATLAS_MAX_GUTTER) return fail(PRT_HIP_EINVAL, "atlas_resolve: gutter must be 0 .. 64");
-    HIP_TRY(hipSetDevice(c->device));
-    const ResolveArgs A{W, H, n, stride, texels, values, image, mask};
-    return (flags & PRT_HIP_QUERY_HOST) ? resolve_staged(c, A, gutter, image, mask) : resolve_direct(c, A, gutter, stream);
+    const size_t total = (size_t)W * H;
+    PrtIoArray io[4] = {prt_io_in(texels, (size_t)n * sizeof(uint32_t), 4), prt_io_in(values, (size_t)n * stride * sizeof(float), 4),
+                        prt_io_out(image, total * stride * sizeof(float), 4), prt_io_out(mask, total, 1)};
+    return prt_run_io(c, flags, stream, "atlas_resolve: texels, values and image must be 4-byte aligned", io, 4, [&]() {
+        ResolveArgs A{W, H, n, stride, io[0].as<uint32_t>(), io[1].as<float>(), io[2].as<float>(), io[3].as<uint8_t>()};
+        if (!A.mask) { // the passes need one: the context's
+            HIP_TRY(c->atScratchMask.grow(total, c->stream));
+            A.mask = c->atScratchMask;
+        }
+        return launch_resolve(c, A, gutter);
+    });
 }
 
 } // extern "C"

@@ -149,12 +149,11 @@ __global__ __launch_bounds__(256) void bake_reduce_kernel(BakeReduceArgs A)
 }
 
 // ============================================================================ host side
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // What the three calls ask of n, the table and the flags; *rays = n * K.  Refused before anything is queued.
 int check_bake(uint32_t n, const prt_bake_sets* t, uint32_t flags, const char* what, uint32_t* rays)
 {
-    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    int rc = prt_check_flags(flags, what);
+    if (rc) return rc;
     if (t->K < 1 || t->K > PRT_BAKE_MAX_K) return fail(PRT_HIP_EINVAL, std::string(what) + ": sets->K must be 1 .. 4096");
     if (t->C < 1 || t->C > PRT_BAKE_MAX_C) return fail(PRT_HIP_EINVAL, std::string(what) + ": sets->C must be 1 .. 16");
     if (t->nSets < 1 || t->nSets > PRT_BAKE_MAX_SETS) return fail(PRT_HIP_EINVAL, std::string(what) + ": sets->nSets must be 1 .. 1024");
@@ -184,90 +183,34 @@ int launch_reduce(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, cons
     return prt_launched("bake_reduce_kernel");
 }
 
-// One call's arrays, the caller's or the context's staged copies; null: the call has no such array.
-struct BakeIO {
-    const prt_bake_point* points;
-    const float* dirs;
-    const float* weights;
-    prt_ray* rays;         // bake_rays: written
-    const float* radiance; // bake_reduce: read
-    float* out;
-    const prt_render_params* params; // prt_hip_bake: trace between the two kernels, rays and radiances in the context's buffers
-};
-
-int launch_bake(prt_hip_ctx* c, uint32_t n, const prt_bake_sets& t, const BakeIO& io)
-{
-    int rc;
-    if (io.params) {
-        if ((rc = launch_rays(c, n, io.points, t, io.dirs, c->bkRays)) || (rc = prt_frame_probe(c, n * t.K, c->bkRays, io.params, c->bkRad))) return rc;
-        return launch_reduce(c, n, io.points, t, io.weights, c->bkRad, io.out);
-    }
-    if (io.rays) return launch_rays(c, n, io.points, t, io.dirs, io.rays);
-    return launch_reduce(c, n, io.points, t, io.weights, io.radiance, io.out);
-}
-
-// PRT_HIP_QUERY_HOST: every array is host memory, staged in the context's buffers; the answer is in host memory on return.
-int bake_staged(prt_hip_ctx* c, uint32_t n, const prt_bake_sets& t, const BakeIO& io)
-{
-    hipStream_t s = c->stream;
-    const size_t rays = (size_t)n * t.K, nd = (size_t)t.nSets * t.K * 3, nw = (size_t)t.nSets * t.K * t.C, no = (size_t)n * 3 * t.C;
-    BakeIO d = io;
-    HIP_TRY(c->bkPoints.grow(n, s));
-    HIP_TRY(hipMemcpyAsync(c->bkPoints, io.points, (size_t)n * sizeof(prt_bake_point), hipMemcpyHostToDevice, s));
-    d.points = c->bkPoints;
-    if (io.dirs) {
-        HIP_TRY(c->bkDirs.grow(nd, s));
-        HIP_TRY(hipMemcpyAsync(c->bkDirs, io.dirs, nd * sizeof(float), hipMemcpyHostToDevice, s));
-        d.dirs = c->bkDirs;
-    }
-    if (io.weights) {
-        HIP_TRY(c->bkWeights.grow(nw, s));
-        HIP_TRY(hipMemcpyAsync(c->bkWeights, io.weights, nw * sizeof(float), hipMemcpyHostToDevice, s));
-        d.weights = c->bkWeights;
-    }
-    if (io.rays) {
-        HIP_TRY(c->bkRays.grow(rays, s));
-        d.rays = c->bkRays;
-    }
-    if (io.radiance) {
-        HIP_TRY(c->bkRad.grow(3 * rays, s));
-        HIP_TRY(hipMemcpyAsync(c->bkRad, io.radiance, 3 * rays * sizeof(float), hipMemcpyHostToDevice, s));
-        d.radiance = c->bkRad;
-    }
-    if (io.out) {
-        HIP_TRY(c->bkOut.grow(no, s));
-        d.out = c->bkOut;
-    }
-    int rc = launch_bake(c, n, t, d);
-    if (rc) return rc;
-    if (io.rays) HIP_TRY(hipMemcpyAsync(io.rays, c->bkRays, rays * sizeof(prt_ray), hipMemcpyDeviceToHost, s));
-    if (io.out) HIP_TRY(hipMemcpyAsync(io.out, c->bkOut, no * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PRT_HIP_OK;
-}
-
-// The arrays are device memory: checked for the alignment the kernels load and store with, then queued around the caller's stream.
-int bake_direct(prt_hip_ctx* c, uint32_t n, const prt_bake_sets& t, const BakeIO& io, void* stream, const char* what)
-{
-    if (!aligned(io.points, 16) || !aligned(io.rays, 16) || !aligned(io.dirs, 4) || !aligned(io.weights, 4) || !aligned(io.radiance, 4) ||
-        !aligned(io.out, 4)) // (null is aligned)
-        return fail(PRT_HIP_EINVAL, std::string(what) + ": points and rays must be 16-byte aligned, float arrays 4-byte aligned");
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_bake(c, n, t, io))) return rc;
-    return prt_stream_leave(c, caller);
-}
+// Where the arrays of the three calls stand in the table; an entry a call has no array for stays null.
+enum { B_POINTS, B_DIRS, B_WEIGHTS, B_RAYS /* bake_rays: written */, B_RADIANCE /* bake_reduce: read */, B_OUT, B_ARRAYS };
 
 // What the three calls share behind their checks.  The table is copied: the caller may reuse it as soon as the call returns.
-int run_bake(prt_hip_ctx* c, uint32_t n, const prt_bake_sets* sets, const BakeIO& io, uint32_t flags, void* stream, const char* what)
+// rays: bake_rays; radiance: bake_reduce; params: prt_hip_bake, which traces between the two kernels, its rays and their radiances in
+// the context's buffers.  The directions go to the rays kernel and the weights to the reduce, so a call without one stages neither.
+int run_bake(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, prt_ray* rays, const float* radiance, float* out,
+             const prt_render_params* params, uint32_t flags, void* stream, const char* what)
 {
     const prt_bake_sets t = *sets;
-    HIP_TRY(hipSetDevice(c->device));
-    if (io.params) { // the rays and their radiances stay on the device, in either flavour
-        HIP_TRY(c->bkRays.grow((size_t)n * t.K, c->stream));
-        HIP_TRY(c->bkRad.grow(3 * (size_t)n * t.K, c->stream));
-    }
-    return (flags & PRT_HIP_QUERY_HOST) ? bake_staged(c, n, t, io) : bake_direct(c, n, t, io, stream, what);
+    const size_t nRays = (size_t)n * t.K, entries = (size_t)t.nSets * t.K;
+    PrtIoArray io[B_ARRAYS] = {prt_io_in(points, (size_t)n * sizeof(prt_bake_point), 16),
+                               prt_io_in(rays || params ? t.dirs : nullptr, entries * 3 * sizeof(float), 4),
+                               prt_io_in(out ? t.weights : nullptr, entries * t.C * sizeof(float), 4),
+                               prt_io_out(rays, nRays * sizeof(prt_ray), 16),
+                               prt_io_in(radiance, 3 * nRays * sizeof(float), 4),
+                               prt_io_out(out, (size_t)n * 3 * t.C * sizeof(float), 4)};
+    return prt_run_io(c, flags, stream, std::string(what) + ": points and rays must be 16-byte aligned, float arrays 4-byte aligned", io, B_ARRAYS, [&]() {
+        const prt_bake_point* pts = io[B_POINTS].as<prt_bake_point>();
+        const float *dirs = io[B_DIRS].as<float>(), *weights = io[B_WEIGHTS].as<float>();
+        if (rays) return launch_rays(c, n, pts, t, dirs, io[B_RAYS].as<prt_ray>());
+        if (!params) return launch_reduce(c, n, pts, t, weights, io[B_RADIANCE].as<float>(), io[B_OUT].as<float>());
+        int rc;
+        HIP_TRY(c->bkRays.grow(nRays, c->stream));
+        HIP_TRY(c->bkRad.grow(3 * nRays, c->stream));
+        if ((rc = launch_rays(c, n, pts, t, dirs, c->bkRays)) || (rc = prt_frame_probe(c, (uint32_t)nRays, c->bkRays, params, c->bkRad))) return rc;
+        return launch_reduce(c, n, pts, t, weights, c->bkRad, io[B_OUT].as<float>());
+    });
 }
 
 } // namespace
@@ -281,7 +224,7 @@ int prt_hip_bake_rays(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, 
     uint32_t nRays;
     int rc = check_bake(n, sets, flags, "bake_rays", &nRays);
     if (rc) return rc;
-    return run_bake(c, n, sets, BakeIO{points, sets->dirs, nullptr, rays, nullptr, nullptr, nullptr}, flags, stream, "bake_rays");
+    return run_bake(c, n, points, sets, rays, nullptr, nullptr, nullptr, flags, stream, "bake_rays");
 }
 
 int prt_hip_bake_reduce(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, const float* radiance, float* out,
@@ -291,7 +234,7 @@ int prt_hip_bake_reduce(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points
     uint32_t nRays;
     int rc = check_bake(n, sets, flags, "bake_reduce", &nRays);
     if (rc) return rc;
-    return run_bake(c, n, sets, BakeIO{points, nullptr, sets->weights, nullptr, radiance, out, nullptr}, flags, stream, "bake_reduce");
+    return run_bake(c, n, points, sets, nullptr, radiance, out, nullptr, flags, stream, "bake_reduce");
 }
 
 int prt_hip_bake(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets, const prt_render_params* params, float* out,
@@ -302,7 +245,7 @@ int prt_hip_bake(prt_hip_ctx* c, uint32_t n, const prt_bake_point* points, const
     uint32_t nRays;
     int rc;
     if ((rc = check_bake(n, sets, flags, "bake", &nRays)) || (rc = prt_check_radiance(c, nRays, params, flags, "bake"))) return rc;
-    return run_bake(c, n, sets, BakeIO{points, sets->dirs, sets->weights, nullptr, nullptr, out, params}, flags, stream, "bake");
+    return run_bake(c, n, points, sets, nullptr, nullptr, out, params, flags, stream, "bake");
 }
 
 } // extern "C"

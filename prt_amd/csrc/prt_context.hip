@@ -49,6 +49,34 @@ int prt_stream_leave(prt_hip_ctx* c, hipStream_t caller)
     return PRT_HIP_OK;
 }
 
+// The two halves of prt_run_io around its launch.
+int prt_io_begin(prt_hip_ctx* c, uint32_t flags, void* stream, const std::string& alignmentMessage, PrtIoArray* io, uint32_t count, hipStream_t* caller)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    *caller = nullptr;
+    if (flags & PRT_HIP_QUERY_HOST) {
+        HIP_TRY(c->stage.place(io, count, c->stream));
+        return PRT_HIP_OK;
+    }
+    if (!prt_io_on_device(io, count)) return fail(PRT_HIP_EINVAL, alignmentMessage);
+    return prt_stream_enter(c, stream, caller);
+}
+
+int prt_io_end(prt_hip_ctx* c, uint32_t flags, const PrtIoArray* io, uint32_t count, hipStream_t caller)
+{
+    if (flags & PRT_HIP_QUERY_HOST) {
+        HIP_TRY(c->stage.fetch(io, count, c->stream));
+        return PRT_HIP_OK;
+    }
+    return prt_stream_leave(c, caller);
+}
+
+int prt_check_flags(uint32_t flags, const char* what)
+{
+    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    return PRT_HIP_OK;
+}
+
 int prt_own_framebuffer(prt_hip_ctx* c, float** d_rgb)
 {
     if (*d_rgb) return PRT_HIP_OK;

@@ -10,6 +10,7 @@
 #include "../../include/prt_hip.h"
 #include "prt_devbuf.h"
 #include "prt_devres.h"
+#include "prt_stage.h"
 #include "prt_device.h"
 #include "prt_batch.h"
 
@@ -188,16 +189,10 @@ struct prt_hip_ctx {
     // ray queries (prt_query.hip): allocated on first use
     DevBuf<uint32_t> qInv;             // with the scene: slot base of the mesh + mesh-order primId -> triangle slot (0xffffffff: none)
     DevBuf<unsigned long long> qCounts; // records the last prt_hip_query_surface refused
-    DevBuf<prt_ray> qRays;             // PRT_HIP_QUERY_HOST: the caller's rays and the answers, staged on the device
-    DevBuf<prt_hit> qHits;
-    DevBuf<prt_surface> qSurf;
-    DevBuf<uint8_t> qOccl;
-    DevBuf<float> qRad;                // prt_hip_query_radiance: 3 floats per probe
+    PrtStage stage;                    // PRT_HIP_QUERY_HOST, every family: the caller's arrays and the answers of the call under way
     // baking (prt_bake.hip): allocated on first use
-    DevBuf<prt_ray> bkRays;            // prt_hip_bake: the n*K rays and their radiances, which never leave the device; with
-    DevBuf<float> bkRad;               // PRT_HIP_QUERY_HOST also the staged rays of bake_rays and radiances of bake_reduce
-    DevBuf<prt_bake_point> bkPoints;   // PRT_HIP_QUERY_HOST: the caller's points, table and answer, staged on the device
-    DevBuf<float> bkDirs, bkWeights, bkOut;
+    DevBuf<prt_ray> bkRays;            // prt_hip_bake: the n*K rays and
+    DevBuf<float> bkRad;               // their radiances, which never leave the device, in either flavour
     // lightmap atlases (prt_atlas.hip): allocated on first use
     DevBuf<uint32_t> atOwner;          // prt_hip_atlas_rasterize: per texel the smallest key (meshId << 28) | primId that covers it,
     DevBuf<uint8_t> atFlag;            // 1 = the texel is owned, and
@@ -205,12 +200,7 @@ struct prt_hip_ctx {
     DevBuf<char> atTemp;               // hipcub scratch of the selection
     DevBuf<unsigned long long> atCounts;    // {pairs, rejected, degenerate, n} of the last rasterise and
     HostBuf<unsigned long long> atCountsHost; // their pinned host copy
-    DevBuf<float> atUV;                // PRT_HIP_QUERY_HOST: the caller's arrays and the answers, staged on the device
-    DevBuf<uint32_t> atTexels;
-    DevBuf<prt_hit> atHits;
-    DevBuf<prt_bake_point> atPoints;
-    DevBuf<float> atValues, atImage;
-    DevBuf<uint8_t> atMask;            // also the mask of a prt_hip_atlas_resolve on device arrays whose caller wants none
+    DevBuf<uint8_t> atScratchMask;     // the mask the passes of a prt_hip_atlas_resolve work on when its caller wants none
 };
 
 
@@ -228,6 +218,23 @@ int prt_check_rect(const prt_hip_ctx* c, uint32_t x0, uint32_t y0, uint32_t x1, 
 // stream given, or the context's own).  An error return skips the leave.
 int prt_stream_enter(prt_hip_ctx* c, void* stream, hipStream_t* caller);
 int prt_stream_leave(prt_hip_ctx* c, hipStream_t caller);
+// The scaffold of an entry point whose arrays are host memory under PRT_HIP_QUERY_HOST and device memory otherwise: io lists them
+// (prt_stage.h), launch() queues the work on the context's stream and reads the device pointers out of io[].dev.  Host arrays are
+// staged in the context's arena: copied in, launch(), copied out, and the stream is synchronised.  Device arrays are refused with
+// PRT_HIP_EINVAL and alignmentMessage, before anything is queued or allocated, when a pointer misses its alignment; then launch()
+// runs between prt_stream_enter and prt_stream_leave.  The parts that are no template: prt_context.hip.
+int prt_io_begin(prt_hip_ctx* c, uint32_t flags, void* stream, const std::string& alignmentMessage, PrtIoArray* io, uint32_t count, hipStream_t* caller);
+int prt_io_end(prt_hip_ctx* c, uint32_t flags, const PrtIoArray* io, uint32_t count, hipStream_t caller);
+template <typename Launch>
+int prt_run_io(prt_hip_ctx* c, uint32_t flags, void* stream, const std::string& alignmentMessage, PrtIoArray* io, uint32_t count, Launch launch)
+{
+    hipStream_t caller;
+    int rc;
+    if ((rc = prt_io_begin(c, flags, stream, alignmentMessage, io, count, &caller)) || (rc = launch())) return rc;
+    return prt_io_end(c, flags, io, count, caller);
+}
+// EINVAL "<what>: unknown flag bits" for any bit but PRT_HIP_QUERY_HOST
+int prt_check_flags(uint32_t flags, const char* what);
 // *d_rgb == NULL becomes the context's own framebuffer, (re)allocated at the camera's size and cleared on the context's stream.
 int prt_own_framebuffer(prt_hip_ctx* c, float** d_rgb);
 // After a kernel launch: PRT_HIP_ELAUNCH "<kernel> launch: ..." when the runtime refused it.
@@ -257,6 +264,8 @@ int prt_null_argument(const char* what);
 // prt_query.hip, shared with prt_hip_atlas_points (prt_atlas.hip): the inverse of triPrim for the uploaded scene (prt_hip_ctx::qInv),
 // built on the context's stream by the first use after an upload
 int prt_query_inverse_ready(prt_hip_ctx* c);
+// prt_query.hip, shared with the same: triangles per mesh of the uploaded scene, the range of a caller's primId
+void prt_query_prim_counts(const prt_hip_ctx* c, uint32_t primCount[PRT_MAX_BVH]);
 // prt_upload.hip: frees the scene's device arrays (prt_hip_destroy; a new upload)
 void prt_free_scene(prt_hip_ctx* c);
 // prt_upload.hip, the ONE place that writes a pointer of c->sc: each from its owner in c->arr (null where the owner is empty).  Called

@@ -3,7 +3,7 @@
 // source that reads prt_ray records and a sink that writes prt_hit / prt_surface / one byte; the surface fetch is get_surface,
 // sample_bump and sample_diffuse, unchanged.  In a translation unit of its own, as prt_temporal.hip and prt_display.hip are, so that
 // the code objects of every other kernel -- the frame kernel's above all -- do not move.
-// prt_hip_query_radiance (radiance along the caller's rays) has its checks and its staging here; its kernel is the frame kernel's probe
+// prt_hip_query_radiance (radiance along the caller's rays) has its checks and its array table here; its kernel is the frame kernel's probe
 // instantiation, launched by prt_frame_probe (prt_kernels.hip), which shares the launch code of the renders.
 #include <hip/hip_runtime.h>
 
@@ -183,21 +183,16 @@ __global__ __launch_bounds__(256) void query_surface_kernel(SurfaceArgs A)
 QueryMeshes query_meshes(const prt_hip_ctx* c)
 {
     QueryMeshes qm{};
-    for (uint32_t m = 0; m < c->sc.bvhCount && m < PRT_MAX_BVH; m++) {
-        qm.matBase[m] = m < c->ed.meshes.size() ? c->ed.meshes[m].matBase : 0u;
-        qm.primCount[m] = m < c->rf.meshes.size() ? std::min(c->rf.meshes[m].primCount, c->rf.meshes[m].slotCount) : 0u;
-    }
+    for (uint32_t m = 0; m < c->sc.bvhCount && m < PRT_MAX_BVH; m++) qm.matBase[m] = m < c->ed.meshes.size() ? c->ed.meshes[m].matBase : 0u;
+    prt_query_prim_counts(c, qm.primCount);
     return qm;
 }
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 int check_batch(prt_hip_ctx* c, uint32_t n, uint32_t flags, const char* what)
 {
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
     if (n == 0 || n > PRT_QUERY_MAX_RAYS) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^30");
-    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
-    return PRT_HIP_OK;
+    return prt_check_flags(flags, what);
 }
 
 // One launch of a traversal kernel over the batch on the context's stream, timed as a render.
@@ -226,90 +221,27 @@ int launch_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hi
     return prt_launched("query_surface_kernel");
 }
 
-// One query: what it launches, and its arrays -- the caller's or the context's staged copies; null: the query has no such array.
-// hitsIn: the hits QUERY_SURFACE fetches records of (nothing is traced then).
+// One query: what it launches, and where its arrays stand in the table; an entry the query has no array for stays null.
+// Q_HITS_IN: the hits QUERY_SURFACE fetches records of (nothing is traced then).
 enum QueryKind { QUERY_NEAREST, QUERY_ANY, QUERY_SURFACE };
-struct QueryIO {
-    QueryKind kind;
-    const prt_ray* rays;
-    const prt_hit* hitsIn;
-    prt_hit* hits;
-    prt_surface* surf;
-    uint8_t* occ;
-};
-
-int launch_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q)
-{
-    if (q.kind == QUERY_SURFACE) return launch_surface(c, n, q.rays, q.hitsIn, q.surf);
-    return launch_trace(c, n, q.rays, q.hits, q.surf, q.occ, q.kind == QUERY_ANY);
-}
-
-// PRT_HIP_QUERY_HOST: the arrays are host memory.  They are staged in the context's buffers, and the answers are in them on return.
-int query_staged(prt_hip_ctx* c, uint32_t n, const QueryIO& q)
-{
-    hipStream_t s = c->stream;
-    HIP_TRY(c->qRays.grow(n, s));
-    if (q.hits || q.hitsIn) HIP_TRY(c->qHits.grow(n, s));
-    if (q.surf) HIP_TRY(c->qSurf.grow(n, s));
-    if (q.occ) HIP_TRY(c->qOccl.grow(n, s));
-    HIP_TRY(hipMemcpyAsync(c->qRays, q.rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-    if (q.hitsIn) HIP_TRY(hipMemcpyAsync(c->qHits, q.hitsIn, (size_t)n * sizeof(prt_hit), hipMemcpyHostToDevice, s));
-    const QueryIO d{q.kind, c->qRays, q.hitsIn ? (const prt_hit*)c->qHits : nullptr, q.hits ? (prt_hit*)c->qHits : nullptr,
-                    q.surf ? (prt_surface*)c->qSurf : nullptr, q.occ ? (uint8_t*)c->qOccl : nullptr};
-    int rc = launch_query(c, n, d);
-    if (rc) return rc;
-    if (q.hits) HIP_TRY(hipMemcpyAsync(q.hits, c->qHits, (size_t)n * sizeof(prt_hit), hipMemcpyDeviceToHost, s));
-    if (q.surf) HIP_TRY(hipMemcpyAsync(q.surf, c->qSurf, (size_t)n * sizeof(prt_surface), hipMemcpyDeviceToHost, s));
-    if (q.occ) HIP_TRY(hipMemcpyAsync(q.occ, c->qOccl, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PRT_HIP_OK;
-}
-
-// The arrays are device memory: checked for the alignment the kernels load and store with, then queued around the caller's stream.
-int query_direct(prt_hip_ctx* c, uint32_t n, const QueryIO& q, void* stream, const char* what)
-{
-    const bool records = q.hits || q.hitsIn || q.surf;
-    if (!aligned(q.rays, 16) || !aligned(q.hits, 4) || !aligned(q.hitsIn, 4) || !aligned(q.surf, 16)) // (null is aligned)
-        return fail(PRT_HIP_EINVAL, std::string(what) + (records ? ": rays and surfaces must be 16-byte aligned, hits 4-byte aligned"
-                                                                 : ": rays must be 16-byte aligned"));
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = launch_query(c, n, q))) return rc;
-    return prt_stream_leave(c, caller);
-}
+enum { Q_RAYS, Q_HITS_IN, Q_HITS, Q_SURF, Q_OCC, Q_ARRAYS };
 
 // What the three queries share behind their NULL checks.
-int run_query(prt_hip_ctx* c, uint32_t n, const QueryIO& q, uint32_t flags, void* stream, const char* what)
+int run_query(prt_hip_ctx* c, uint32_t n, QueryKind kind, const prt_ray* rays, const prt_hit* hitsIn, prt_hit* hits, prt_surface* surf, uint8_t* occ,
+              uint32_t flags, void* stream, const char* what)
 {
     int rc = check_batch(c, n, flags, what);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    return (flags & PRT_HIP_QUERY_HOST) ? query_staged(c, n, q) : query_direct(c, n, q, stream, what);
-}
-
-// ============================================================================ radiance along the caller's rays
-#define PRT_QUERY_MAX_PROBES (1u << 24)
-
-int radiance_staged(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance)
-{
-    hipStream_t s = c->stream;
-    HIP_TRY(c->qRays.grow(n, s));
-    HIP_TRY(c->qRad.grow(3 * (size_t)n, s));
-    HIP_TRY(hipMemcpyAsync(c->qRays, rays, (size_t)n * sizeof(prt_ray), hipMemcpyHostToDevice, s));
-    int rc = prt_frame_probe(c, n, c->qRays, p, c->qRad);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(radiance, c->qRad, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PRT_HIP_OK;
-}
-
-int radiance_direct(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_render_params* p, float* radiance, void* stream)
-{
-    if (!aligned(rays, 16) || !aligned(radiance, 4)) return fail(PRT_HIP_EINVAL, "query_radiance: rays must be 16-byte aligned, radiance 4-byte aligned");
-    hipStream_t caller;
-    int rc;
-    if ((rc = prt_stream_enter(c, stream, &caller)) || (rc = prt_frame_probe(c, n, rays, p, radiance))) return rc;
-    return prt_stream_leave(c, caller);
+    PrtIoArray io[Q_ARRAYS] = {prt_io_in(rays, (size_t)n * sizeof(prt_ray), 16), prt_io_in(hitsIn, (size_t)n * sizeof(prt_hit), 4),
+                               prt_io_out(hits, (size_t)n * sizeof(prt_hit), 4), prt_io_out(surf, (size_t)n * sizeof(prt_surface), 16),
+                               prt_io_out(occ, n, 1)};
+    const bool records = hits || hitsIn || surf;
+    return prt_run_io(c, flags, stream, std::string(what) + (records ? ": rays and surfaces must be 16-byte aligned, hits 4-byte aligned"
+                                                                      : ": rays must be 16-byte aligned"), io, Q_ARRAYS, [&]() {
+        if (kind == QUERY_SURFACE) return launch_surface(c, n, io[Q_RAYS].as<prt_ray>(), io[Q_HITS_IN].as<prt_hit>(), io[Q_SURF].as<prt_surface>());
+        return launch_trace(c, n, io[Q_RAYS].as<prt_ray>(), io[Q_HITS].as<prt_hit>(), io[Q_SURF].as<prt_surface>(), io[Q_OCC].as<uint8_t>(),
+                            kind == QUERY_ANY);
+    });
 }
 
 } // namespace
@@ -343,6 +275,12 @@ int prt_query_inverse_ready(prt_hip_ctx* c)
     return prt_launched("query_index_kernel");
 }
 
+void prt_query_prim_counts(const prt_hip_ctx* c, uint32_t primCount[PRT_MAX_BVH])
+{
+    for (uint32_t m = 0; m < PRT_MAX_BVH; m++)
+        primCount[m] = m < c->sc.bvhCount && m < c->rf.meshes.size() ? std::min(c->rf.meshes[m].primCount, c->rf.meshes[m].slotCount) : 0u;
+}
+
 // ENODEVICE on a machine without a device (where no context can exist), EINVAL otherwise
 int prt_null_argument(const char* what)
 {
@@ -350,13 +288,17 @@ int prt_null_argument(const char* what)
     return fail(PRT_HIP_EINVAL, std::string(what) + ": NULL argument");
 }
 
+// ============================================================================ radiance along the caller's rays
+#define PRT_QUERY_MAX_PROBES (1u << 24)
+
 // What prt_hip_query_radiance asks of its scalar arguments, and prt_hip_bake (prt_bake.hip) of its n*K probes; everything is refused
 // before anything is queued.
 int prt_check_radiance(prt_hip_ctx* c, uint32_t n, const prt_render_params* p, uint32_t flags, const char* what)
 {
     if (!c->haveScene) return fail(PRT_HIP_ESTATE, std::string(what) + ": upload a scene first");
     if (n == 0 || n > PRT_QUERY_MAX_PROBES) return fail(PRT_HIP_EINVAL, std::string(what) + ": n must be 1 .. 2^24");
-    if (flags & ~PRT_HIP_QUERY_HOST) return fail(PRT_HIP_EINVAL, std::string(what) + ": unknown flag bits");
+    int rc = prt_check_flags(flags, what);
+    if (rc) return rc;
     if (p->samples < 8 || p->samples % 8 != 0 || p->samples / 8 > 255)
         return fail(PRT_HIP_EINVAL, std::string(what) + ": samples must be a multiple of 8 from 8 to 2040");
     if (p->maxDepth > 255) return fail(PRT_HIP_EINVAL, std::string(what) + ": maxDepth too large");
@@ -373,26 +315,27 @@ int prt_hip_query_radiance(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, cons
     if (!c || !rays || !p || !radiance) return prt_null_argument("query_radiance");
     int rc = prt_check_radiance(c, n, p, flags, "query_radiance");
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    return (flags & PRT_HIP_QUERY_HOST) ? radiance_staged(c, n, rays, p, radiance) : radiance_direct(c, n, rays, p, radiance, stream);
+    PrtIoArray io[2] = {prt_io_in(rays, (size_t)n * sizeof(prt_ray), 16), prt_io_out(radiance, 3 * (size_t)n * sizeof(float), 4)};
+    return prt_run_io(c, flags, stream, "query_radiance: rays must be 16-byte aligned, radiance 4-byte aligned", io, 2,
+                      [&]() { return prt_frame_probe(c, n, io[0].as<prt_ray>(), p, io[1].as<float>()); });
 }
 
 int prt_hip_query_nearest(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
     if (!c || !rays || !hits) return prt_null_argument("query_nearest");
-    return run_query(c, n, QueryIO{QUERY_NEAREST, rays, nullptr, hits, surfaces, nullptr}, flags, stream, "query_nearest");
+    return run_query(c, n, QUERY_NEAREST, rays, nullptr, hits, surfaces, nullptr, flags, stream, "query_nearest");
 }
 
 int prt_hip_query_any(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, uint8_t* occluded, uint32_t flags, void* stream)
 {
     if (!c || !rays || !occluded) return prt_null_argument("query_any");
-    return run_query(c, n, QueryIO{QUERY_ANY, rays, nullptr, nullptr, nullptr, occluded}, flags, stream, "query_any");
+    return run_query(c, n, QUERY_ANY, rays, nullptr, nullptr, nullptr, occluded, flags, stream, "query_any");
 }
 
 int prt_hip_query_surface(prt_hip_ctx* c, uint32_t n, const prt_ray* rays, const prt_hit* hits, prt_surface* surfaces, uint32_t flags, void* stream)
 {
     if (!c || !rays || !hits || !surfaces) return prt_null_argument("query_surface");
-    return run_query(c, n, QueryIO{QUERY_SURFACE, rays, hits, nullptr, surfaces, nullptr}, flags, stream, "query_surface");
+    return run_query(c, n, QUERY_SURFACE, rays, hits, nullptr, surfaces, nullptr, flags, stream, "query_surface");
 }
 
 int prt_hip_query_get_counts(prt_hip_ctx* c, uint64_t* invalidHits)

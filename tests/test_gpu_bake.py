@@ -439,7 +439,7 @@ def test_a_bake_leaves_the_context_alone():
         t.display(prt_amd.DisplayParams.make(meter=True))
         W, H = camera.width, camera.height
         org, d = PR.stage_probes(100, seed=23)
-        probes = t.query_radiance(org, d, 8, seed=5)  # (qRays and qRad hold this batch)
+        probes = t.query_radiance(org, d, 8, seed=5)  # (the staging arena holds this batch)
 
         def snapshot():
             acc = t.accum_export()
