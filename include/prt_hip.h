@@ -969,6 +969,97 @@ int prt_hip_atlas_resolve(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t n, 
                           const float* values /* n*stride */, uint32_t stride /* 1 .. 48: 3*C of the bake */, uint32_t gutter /* 0 .. 64 */,
                           float* image /* W*H*stride */, uint8_t* mask /* W*H, may be NULL */, uint32_t flags, void* stream);
 
+/* ---- lens renders: a camera record in, an image of radiance sums out.  What a caller writes around prt_hip_query_radiance for any
+ * camera the reference lacks -- a ray per pixel and sample built on the host, 32 bytes per ray up and 12 down, a sum, and a splitter for
+ * every image beyond the 2^24 probes of one launch -- as one call that builds the rays on the device, traces them band by band and
+ * adds the K radiances of every pixel into an image that can accumulate over calls: a perspective camera with a thin lens (depth of
+ * field), an orthographic view, a 360 x 180 degree panorama and an equidistant fisheye.  A cube map is six PINHOLE calls with a 90
+ * degree basis (|right| = |up| = |fwd|, width = height); it needs no model of its own.  The rays and the per-ray radiances never
+ * leave the device.
+ *
+ * Definition.  Everything is f32, every product is rounded before the sum that uses it (no FMA), sums go left to right as written.
+ * W = width, H = height.  Ray r = ((y - y0)*W + x)*K + k of pixel (x, y), k = 0 .. K-1, in the band of rows [y0, y1):
+ *   Draws.  mix(v) is the five steps of the frame kernel's pixel seed without its final | 1:
+ *         v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16
+ *     pix = y*W + x, j = pass*K + k (uint32 wrap), s = mix(mix(pix + jitterSeed) + j) | 1; then four times in turn
+ *         s = xorshift32(s) (s ^= s << 13; s ^= s >> 17; s ^= s << 5),  u_i = bits((s & 0x007fffff) | 0x3f800000) - 1.0f,  i = 0 .. 3
+ *     All four draws are always made: the stream does not depend on the model, and pass p with K rays is rays p*K .. p*K + K-1 of the
+ *     pixel's stream, whatever K is.
+ *   Film.  jx = CENTRE ? 0.5f : u0, jy = CENTRE ? 0.5f : u1; invW = 1.0f / (float)W, invH = 1.0f / (float)H;
+ *         sx = ((float)x + jx) * invW,  sy = ((float)y + jy) * invH,  a = 2.0f*sx - 1.0f,  b = 1.0f - 2.0f*sy
+ *     so a runs from -1 at the left edge to +1 at the right, b from +1 at the top edge to -1 at the bottom, and the centre of pixel
+ *     (x, y) sits at ((x + 0.5) / W, (y + 0.5) / H), as a texel's does in the atlas.  This is HALF A PIXEL off the footprint of
+ *     prt_hip_render, which centres pixel x at x / W (camera.cpp:54-55): a PINHOLE record that frames what a prt_camera_desc frames
+ *     has right' = 0.6*aspect*right, up' = 0.6*up and fwd' = dir - right'/W + up'/H.
+ *   PINHOLE.  d = (fwd + a*right) + b*up per component.
+ *     if !(lensRadius > 0):  org = pos, dir = d
+ *     otherwise (a thin lens):
+ *         rl = lensRadius * sqrtf(u2);  (sn, cs) = sincosf(6.28318530717958647692f * u3)
+ *         R = normalize3(right), U = normalize3(up)   (the normalize3 of the baking section)
+ *         org = (pos + (rl*cs)*R) + (rl*sn)*U;  F = pos + focus*d;  dir = F - org
+ *     d is not normalised, so the plane in focus lies at focus * |fwd| along fwd for every pixel.
+ *   ORTHO.  org = (pos + a*right) + b*up, dir = fwd.
+ *   EQUIRECT.  (sp, cp) = sincosf(a * 3.14159265358979323846f), (st, ct) = sincosf(b * 1.57079632679489661923f),
+ *         l = (ct*sp, st, ct*cp);  dir = (l.x*right + l.y*up) + l.z*fwd;  org = pos
+ *   FISHEYE.  rr = sqrtf(a*a + b*b).  if !(rr <= 1.0f): org = pos, dir = 0 (outside the image circle: the probe rule of
+ *     prt_hip_query_radiance answers such a ray black and counts its `samples` primary rays).  Otherwise
+ *         (st, ct) = sincosf(rr * (0.5f*fov)),  q = rr > 0.0f ? st / rr : 0.0f,  l = (a*q, b*q, ct),  dir and org as for EQUIRECT
+ *   All models: tMax = 0, pad = 0.  sincosf is glibc's sinf and cosf of the same argument, as the kernels restate them.  Nothing about
+ *   the basis is checked or normalised beyond what is written: hostile pos, fwd, right, up, fov, lensRadius and focus (NaN, inf, 0,
+ *   1e-30, 3e20, negative) give what the arithmetic gives, and the probe rule handles the rest.  (Which NaN an invalid operation
+ *   gives, its sign and payload, is the processor's choice.)
+ * Probe seeds.  The ray with the global index g = (y*W + x)*K + k is probe g under the seed params->seed + pass*(W*H*K) + g (uint32
+ *   wrap, the product included): the band [y0, y1) is prt_hip_query_radiance of prt_hip_lens_rays(y0, y1) under
+ *   seed + pass*W*H*K + y0*W*K, and the image does not depend on how it is cut into bands.
+ * Accumulate.  For pixel pix of the band, whose first ray in the band is r0, and colour component h: S = +0, then for k = 0 .. K-1 in
+ *   that order S = S + L[3*(r0 + k) + h];  image[3*pix + h] = ACCUMULATE ? image[3*pix + h] + S : S.  Rows outside the band are not
+ *   touched; NaN and infinities travel as given.  The result is a SUM: the mean is sum / (passes*K), taken by the caller or by the
+ *   manual gain of prt_hip_display.
+ *
+ * prt_hip_lens_render runs, for each band of rows in ascending y, on the context's stream: the rays kernel, the frame kernel's probe
+ * launch with the band's seed, the accumulate kernel.  A band holds as many rows as fit the 2^24 probes of one launch, or bandRows
+ * if that is fewer: bandRows caps the scratch (44 bytes per ray, in buffers the context owns and grows on demand).  For
+ * prt_hip_get_stats every band is a render launch: kernelMsSum and kernelLaunches cover them all, the event counters (raysTraced,
+ * nPx ...) are the last band's.  prt_hip_lens_rays and prt_hip_lens_accumulate are the two halves on the caller's arrays; they
+ * need no scene and neither is a launch for the statistics.
+ * Pointers: DEVICE pointers by default (the prt_lens_desc record itself is host memory, read before the call returns); rays 16-byte
+ * aligned, floats 4-byte aligned; asynchronous, ordered after the work queued on stream and before what is queued next, as the
+ * queries are.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged in the context's arena (the image in both directions
+ * under ACCUMULATE), and the call returns with the answer.  Other flag bits are refused.
+ * Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the outputs untouched: a NULL pointer; an unknown
+ * model; width or height outside 1 .. 8192, K outside 1 .. 64, bandRows above height; unknown bits in lens->flags; reserved != 0;
+ * for the two halves y0 >= y1, y1 > height or (y1 - y0)*W*K > 2^24; for prt_hip_lens_render whatever prt_hip_query_radiance
+ * refuses of params.  prt_hip_lens_render without a scene is PRT_HIP_ESTATE.
+ * State: the calls read the scene (the render only) and change nothing else in the context: the camera, the accumulator, the
+ * moments, the guides, the history, the display state and the framebuffer are untouched.
+ * Not built: filters other than the box; motion blur; splitting over ranks; a G-buffer or denoiser guides for lens images; distinct
+ * rays in the eight lanes of a packet, so `samples` per ray stays at least 8. ---- */
+#define PRT_HIP_LENS_PINHOLE  0u  /* perspective; a thin lens when lensRadius > 0 */
+#define PRT_HIP_LENS_ORTHO    1u
+#define PRT_HIP_LENS_EQUIRECT 2u  /* 360 x 180 degree panorama */
+#define PRT_HIP_LENS_FISHEYE  3u  /* equidistant, full angle `fov` in radians across the image circle */
+#define PRT_HIP_LENS_CENTRE     1u /* lens->flags: jx = jy = 0.5 (no pixel jitter; the draws are still made) */
+#define PRT_HIP_LENS_ACCUMULATE 2u /* lens->flags: add to `image` instead of overwriting it */
+typedef struct {
+    uint32_t model, width, height;   /* width, height 1 .. 8192 */
+    uint32_t K;                      /* rays per pixel and pass, 1 .. 64 */
+    uint32_t pass;                   /* which K rays of the pixel's jitter stream, and the probe seeds' offset */
+    uint32_t jitterSeed;
+    uint32_t flags;                  /* PRT_HIP_LENS_CENTRE | PRT_HIP_LENS_ACCUMULATE, other bits refused */
+    uint32_t bandRows;               /* 0: as many rows per frame-kernel launch as fit 2^24 probes; else 1 .. height, capped by that */
+    float pos[3];   float lensRadius;
+    float fwd[3];   float focus;
+    float right[3]; float fov;
+    float up[3];    uint32_t reserved; /* 0 */
+} prt_lens_desc;                     /* 96 bytes, host memory, read before the call returns */
+int prt_hip_lens_rays(prt_hip_ctx* ctx, const prt_lens_desc* lens, uint32_t y0, uint32_t y1 /* rows [y0, y1) */,
+                      prt_ray* rays /* (y1-y0)*W*K */, uint32_t flags, void* stream);
+int prt_hip_lens_accumulate(prt_hip_ctx* ctx, const prt_lens_desc* lens, uint32_t y0, uint32_t y1,
+                            const float* radiance /* 3*(y1-y0)*W*K */, float* image /* 3*W*H, the WHOLE image */, uint32_t flags,
+                            void* stream);
+int prt_hip_lens_render(prt_hip_ctx* ctx, const prt_lens_desc* lens, const prt_render_params* params, float* image /* 3*W*H */,
+                        uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,26 @@ class AtlasPointParams(C.Structure):
     _fields_ = [("bias", C.c_float), ("setTile", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+# prt_lens_desc (include/prt_hip.h "lens renders")
+LENS_PINHOLE, LENS_ORTHO, LENS_EQUIRECT, LENS_FISHEYE = 0, 1, 2, 3
+LENS_CENTRE, LENS_ACCUMULATE = 1, 2
+
+
+class LensDesc(C.Structure):
+    """prt_lens_desc: host memory, read before the call returns.  `pass` is a Python keyword: the field is pass_."""
+    _fields_ = [("model", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("K", C.c_uint32), ("pass_", C.c_uint32),
+                ("jitterSeed", C.c_uint32), ("flags", C.c_uint32), ("bandRows", C.c_uint32),
+                ("pos", C.c_float * 3), ("lensRadius", C.c_float), ("fwd", C.c_float * 3), ("focus", C.c_float),
+                ("right", C.c_float * 3), ("fov", C.c_float), ("up", C.c_float * 3), ("reserved", C.c_uint32)]
+
+    def copy(self, **fields):
+        """A copy of the record with `fields` replaced."""
+        d = LensDesc.from_buffer_copy(self)
+        for k, v in fields.items():
+            setattr(d, k, _f3(v) if k in ("pos", "fwd", "right", "up") else v)
+        return d
+
+
 NODE_DTYPE = np.dtype([("lower", "<f4", 3), ("upper", "<f4", 3), ("primOrSecondNodeIndex", "<u4"),
                        ("triVectorIndex", "<u4"), ("primCount", "<u4"), ("splitAxis", "<u4")])
 MATERIAL_DTYPE = np.dtype([("diffuse", "<f4", 3), ("emissive", "<f4", 3), ("reflectionType", "<u4"),
@@ -241,6 +261,7 @@ EXPORTS = [
     "prt_hip_query_radiance",
     "prt_hip_bake_rays", "prt_hip_bake_reduce", "prt_hip_bake",
     "prt_hip_atlas_rasterize", "prt_hip_atlas_points", "prt_hip_atlas_resolve",
+    "prt_hip_lens_rays", "prt_hip_lens_accumulate", "prt_hip_lens_render",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
     "prt_host_mesh_atrium", "prt_host_mesh_destroy", "prt_host_mesh_transform", "prt_host_mesh_calculate_vertex_normals",
@@ -365,6 +386,9 @@ def _load(path, with_test_entry_points):
     L.prt_hip_atlas_rasterize.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtlasMesh), vp, vp, C.POINTER(AtlasCounts), C.c_uint32, vp]
     L.prt_hip_atlas_points.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AtlasPointParams), vp, C.c_uint32, vp]
     L.prt_hip_atlas_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.prt_hip_lens_rays.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
+    L.prt_hip_lens_accumulate.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.prt_hip_lens_render.argtypes = [vp, C.POINTER(LensDesc), C.POINTER(RenderParams), vp, C.c_uint32, vp]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
@@ -1282,6 +1306,52 @@ class PathTracer:
                                               out.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_bake_reduce")
         return out
 
+    # ---- lens renders (include/prt_hip.h "lens renders"): a camera record in, an image of radiance sums out
+    def lens_rays(self, lens, y0=0, y1=None):
+        """((y1 - y0) * W * K,) RAY_DTYPE: the rays render_lens() traces for rows [y0, y1) of `lens` (a LensDesc), ray
+        ((y - y0)*W + x)*K + k of pixel (x, y) (prt_hip_lens_rays; needs no scene)."""
+        y1 = lens.height if y1 is None else y1
+        rays = np.zeros(max(y1 - y0, 0) * lens.width * lens.K, dtype=RAY_DTYPE)
+        self._chk(self._L.prt_hip_lens_rays(self._ctx, C.byref(lens), y0, y1, rays.ctypes.data_as(C.c_void_p), QUERY_HOST, None),
+                  "prt_hip_lens_rays")
+        return rays
+
+    def lens_accumulate(self, lens, radiance, image=None, y0=0, y1=None):
+        """(H, W, 3) float32: the K radiances of every pixel of rows [y0, y1) summed in order -- radiance ((y1 - y0) * W * K, 3) float32
+        -- into `image` (None: zeros), added to what it holds when lens.flags has LENS_ACCUMULATE and written otherwise; the other
+        rows stay (prt_hip_lens_accumulate; needs no scene).  `image` itself is not changed."""
+        y1 = lens.height if y1 is None else y1
+        L = np.ascontiguousarray(radiance, dtype=np.float32).reshape(-1, 3)
+        if len(L) != max(y1 - y0, 0) * lens.width * lens.K:
+            raise PrtError(f"lens_accumulate: {len(L)} radiances for {max(y1 - y0, 0) * lens.width * lens.K} rays")
+        img = np.zeros((lens.height, lens.width, 3), dtype=np.float32) if image is None else \
+            np.array(image, dtype=np.float32, order="C").reshape(lens.height, lens.width, 3)
+        self._chk(self._L.prt_hip_lens_accumulate(self._ctx, C.byref(lens), y0, y1, L.ctypes.data_as(C.c_void_p),
+                                                  img.ctypes.data_as(C.c_void_p), QUERY_HOST, None), "prt_hip_lens_accumulate")
+        return img
+
+    def render_lens_async(self, lens, d_image, spp, seed=None, exposure=None, max_depth=None, stream=None):
+        """Queue prt_hip_lens_render on device memory: d_image (3 * W * H float32) is a device pointer (int), written, or added to
+        when lens.flags has LENS_ACCUMULATE.  One pass: lens.pass_ picks the K rays of every pixel and the probe seeds."""
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        self._chk(self._L.prt_hip_lens_render(self._ctx, C.byref(lens), C.byref(p), d_image, 0, stream), "prt_hip_lens_render")
+
+    def render_lens(self, lens, spp, passes=1, seed=None, exposure=None, max_depth=None):
+        """(H, W, 3) float32: the mean over passes * K rays per pixel of the radiance along the rays of `lens` (a LensDesc), each ray
+        traced with spp samples (a multiple of 8).  Passes lens.pass_ .. lens.pass_ + passes - 1 accumulate on the device; the one
+        division by passes * K is made here.  Sets last_stats (the last pass's).  Needs a scene and no camera."""
+        p = self._probe_params(spp, seed, exposure, max_depth)
+        n = lens.width * lens.height * 3
+        with _DeviceArrays(self._device) as dev:
+            d_image = dev.alloc(n * 4)
+            for i in range(passes):
+                one = lens.copy(pass_=lens.pass_ + i, flags=(lens.flags | LENS_ACCUMULATE) if i else (lens.flags & ~LENS_ACCUMULATE))
+                self._chk(self._L.prt_hip_lens_render(self._ctx, C.byref(one), C.byref(p), d_image, 0, None), "prt_hip_lens_render")
+            self.last_stats = self.stats()  # synchronises; raises on stack overflow
+            img = np.zeros((lens.height, lens.width, 3), dtype=np.float32)
+            dev.download(img, d_image)
+        return img / np.float32(passes * lens.K)
+
     # ---- lightmap atlases (include/prt_hip.h "lightmap atlases"): per-corner lightmap UVs in, a lightmap image out
     def atlas_rasterize_device(self, W, H, d_uvs, prim_counts, d_texels, d_hits, stream=None):
         """prt_hip_atlas_rasterize on device arrays: d_uvs {meshId: device pointer of 6 * primCount float32}, prim_counts {meshId:
@@ -1579,6 +1649,74 @@ def make_bake_sets(dirs, weights):
     table = BakeSets(K=shape[1], C=1 if w is None else w.shape[2], nSets=shape[0], reserved=0,
                      dirs=None if d is None else d.ctypes.data, weights=None if w is None else w.ctypes.data)
     return d, w, table
+
+
+# ----------------------------------------------------------------------------- lens renders
+def _lens(model, pos, fwd, right, up, W, H, K=1, lens_radius=0.0, focus=1.0, fov=0.0, jitter_seed=0, flags=0, band_rows=0, pass_=0):
+    d = LensDesc(model=model, width=W, height=H, K=K, pass_=pass_, jitterSeed=jitter_seed, flags=flags, bandRows=band_rows,
+                 lensRadius=lens_radius, focus=focus, fov=fov, reserved=0)
+    d.pos, d.fwd, d.right, d.up = _f3(pos), _f3(fwd), _f3(right), _f3(up)
+    return d
+
+
+def _lens_basis(pos, look_at, up):
+    """Unit (fwd, right, up) in float64 of a view from pos towards look_at with `up` roughly upwards (right-handed: right = fwd x up)."""
+    f = np.asarray(look_at, np.float64) - np.asarray(pos, np.float64)
+    f /= np.linalg.norm(f)
+    r = np.cross(f, np.asarray(up, np.float64))
+    r /= np.linalg.norm(r)
+    return f, r, np.cross(r, f)
+
+
+def lens_pinhole(pos, look_at, up, fov_y, W, H, K=1, lens_radius=0.0, focus=1.0, **kw):
+    """A perspective LensDesc: fov_y the full vertical angle in radians, |fwd| = 1 (so `focus` is the distance of the plane in focus
+    along the view direction); lens_radius > 0 makes it a thin lens.  kw: jitter_seed, flags, band_rows, pass_."""
+    f, r, u = _lens_basis(pos, look_at, up)
+    t = np.tan(0.5 * fov_y)
+    return _lens(LENS_PINHOLE, pos, f, t * W / H * r, t * u, W, H, K, lens_radius, focus, **kw)
+
+
+def lens_ortho(pos, look_at, up, half_height, W, H, K=1, **kw):
+    """An orthographic LensDesc: the image spans 2 * half_height vertically around pos."""
+    f, r, u = _lens_basis(pos, look_at, up)
+    return _lens(LENS_ORTHO, pos, f, half_height * W / H * r, half_height * u, W, H, K, **kw)
+
+
+def lens_equirect(pos, W, H, K=1, fwd=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), **kw):
+    """A 360 x 180 degree panorama LensDesc around pos: the image centre looks along fwd, the top row towards up."""
+    f, r, u = _lens_basis(pos, np.asarray(pos, np.float64) + np.asarray(fwd, np.float64), up)
+    return _lens(LENS_EQUIRECT, pos, f, r, u, W, H, K, **kw)
+
+
+def lens_fisheye(pos, look_at, up, fov, W, H, K=1, **kw):
+    """An equidistant fisheye LensDesc: fov the full angle in radians across the image circle (the ellipse inscribed in the image)."""
+    f, r, u = _lens_basis(pos, look_at, up)
+    return _lens(LENS_FISHEYE, pos, f, r, u, W, H, K, fov=fov, **kw)
+
+
+def lens_cube_faces(pos, size, K=1, **kw):
+    """Six size x size pinhole LensDesc with a 90 degree basis, in the order +x, -x, +y, -y, +z, -z (fwd, then up as the cube-map
+    convention of the graphics APIs has them): a cube map needs no model of its own."""
+    faces = [((1, 0, 0), (0, -1, 0)), ((-1, 0, 0), (0, -1, 0)), ((0, 1, 0), (0, 0, 1)), ((0, -1, 0), (0, 0, -1)), ((0, 0, 1), (0, -1, 0)),
+             ((0, 0, -1), (0, -1, 0))]
+    out = []
+    for f, u in faces:
+        f, u = np.array(f, np.float64), np.array(u, np.float64)
+        out.append(_lens(LENS_PINHOLE, pos, f, np.cross(f, u), u, size, size, K, **kw))
+    return out
+
+
+def lens_from_camera(camera, K=1, **kw):
+    """The pinhole LensDesc that frames what prt_hip_render frames for `camera` (a Camera or a CameraDesc).  camera.cpp:54-56 at zero
+    jitter aims pixel (x, y) along dir + nx*right + ny*up with nx = 2*(x/W - 0.5)*0.6*aspect and ny = -2*(y/H - 0.5)*0.6; the
+    lens aims it along fwd' + a*right' + b*up' with a = 2*(x + 0.5)/W - 1 = 2*(x/W - 0.5) + 1/W and b = -2*(y/H - 0.5) - 1/H.
+    With right' = 0.6*aspect*right and up' = 0.6*up the two agree when fwd' = dir - right'/W + up'/H: the last two terms take out
+    the half pixel between the two footprints.  Computed in float64 and rounded once."""
+    c = getattr(camera, "desc", camera)
+    W, H = c.width, c.height
+    pos, d, up, right = (np.array(list(getattr(c, k)), dtype=np.float64) for k in ("pos", "dir", "up", "right"))
+    r2, u2 = 0.6 * (W / H) * right, 0.6 * up
+    return _lens(LENS_PINHOLE, pos, d - r2 / W + u2 / H, r2, u2, W, H, K, **kw)
 
 
 # ----------------------------------------------------------------------------- lightmap atlases

@@ -10,7 +10,7 @@
 
 #include "prt_devbuf.h"
 
-enum PrtIoDir { PRT_IO_IN, PRT_IO_OUT }; // IN: copied to the device before the launch; OUT: copied back after it
+enum PrtIoDir { PRT_IO_IN, PRT_IO_OUT, PRT_IO_INOUT }; // IN: copied to the device before the launch; OUT: copied back after it; INOUT: both
 
 // One array of a call.  p == null: the call has no such array, and every step skips it.
 struct PrtIoArray {
@@ -23,6 +23,8 @@ struct PrtIoArray {
 };
 inline PrtIoArray prt_io_in(const void* p, size_t bytes, uintptr_t align) { return PrtIoArray{const_cast<void*>(p), bytes, align, PRT_IO_IN, nullptr}; }
 inline PrtIoArray prt_io_out(void* p, size_t bytes, uintptr_t align) { return PrtIoArray{p, bytes, align, PRT_IO_OUT, nullptr}; }
+// an array the launch updates in place (an image a lens render adds to): the same slice in both directions
+inline PrtIoArray prt_io_inout(void* p, size_t bytes, uintptr_t align) { return PrtIoArray{p, bytes, align, PRT_IO_INOUT, nullptr}; }
 
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; } // (null is aligned)
 
@@ -42,7 +44,7 @@ public:
     static constexpr size_t SLICE = 256; // every slice starts at a multiple of it: at least the alignment of any record
 
     // One grow to the sum of the sizes (memory that already serves is kept; a regrow synchronises `stream` first: DevBuf), a slice
-    // for every array in table order, and the copies of the IN arrays queued on `stream`.  After an error the arena may be empty.
+    // for every array in table order, and the copies of the IN and INOUT arrays queued on `stream`.  After an error the arena may be empty.
     hipError_t place(PrtIoArray* io, uint32_t count, hipStream_t stream)
     {
         size_t total = 0;
@@ -56,17 +58,17 @@ public:
             if (io[i].p) at += rounded(io[i].bytes);
         }
         for (uint32_t i = 0; i < count; i++)
-            if (io[i].p && io[i].dir == PRT_IO_IN && io[i].bytes) {
+            if (io[i].p && io[i].dir != PRT_IO_OUT && io[i].bytes) {
                 e = hipMemcpyAsync(io[i].dev, io[i].p, io[i].bytes, hipMemcpyHostToDevice, stream);
                 if (e != hipSuccess) return e;
             }
         return hipSuccess;
     }
-    // The copies of the OUT arrays, then the wait for them: the answers are in the caller's memory on return.
+    // The copies of the OUT and INOUT arrays, then the wait for them: the answers are in the caller's memory on return.
     hipError_t fetch(const PrtIoArray* io, uint32_t count, hipStream_t stream)
     {
         for (uint32_t i = 0; i < count; i++)
-            if (io[i].p && io[i].dir == PRT_IO_OUT && io[i].bytes) {
+            if (io[i].p && io[i].dir != PRT_IO_IN && io[i].bytes) {
                 hipError_t e = hipMemcpyAsync(io[i].p, io[i].dev, io[i].bytes, hipMemcpyDeviceToHost, stream);
                 if (e != hipSuccess) return e;
             }

@@ -30,6 +30,14 @@ alone on device arrays, lightmap() end to end against the frame-kernel launches 
 numpy rasteriser, points and gutter fill of tests/prt_atlas_ref.py around bake() on host arrays.
 
     python tools/query_bench.py --atlas [--reps 5] [--out F]
+
+--lens: prt_hip_lens_render (include/prt_hip.h "lens renders") from the bench camera's position, 8 spp, depth 8: a 2048 x 1024 panorama
+with K = 1, a 1920 x 1080 thin-lens pinhole with K = 8 (16.6 M rays, one band) and the same at 3840 x 2160 (four bands).  Per workload:
+(a) one call on device memory, (c) the sum of the frame-kernel launches inside it, the two new kernels alone on one band, and (b) the
+route it replaces: rays in numpy, query_radiance on host arrays in chunks the caller cuts, numpy sums.  The ratio to read is (a) / (c).
+Also the accumulate kernel alone over 2^24 radiances at K = 1, 8 and 64: the layout of its reads is the one thing K changes.
+
+    python tools/query_bench.py --lens [--reps 3] [--out F]
 """
 import argparse
 import ctypes as C
@@ -306,6 +314,125 @@ def atlas(args):
     emit(out, args.out)
 
 
+def lens_host_band(lens, y0, y1, rng):
+    """What a caller wrote in numpy for rows [y0, y1): jittered film coordinates, the model's direction, the
+    thin lens's disc, in double precision with a generator of its own: (org, dir) of (y1 - y0) * W * K rays."""
+    W, H, K = lens.width, lens.height, lens.K
+    pos, fwd, right, up = (np.array(list(getattr(lens, k)), np.float64) for k in ("pos", "fwd", "right", "up"))
+    y, x, _ = np.meshgrid(np.arange(y0, y1), np.arange(W), np.arange(K), indexing="ij")
+    n = x.size
+    a = 2.0 * (x.reshape(-1) + rng.random(n)) / W - 1.0
+    b = 1.0 - 2.0 * (y.reshape(-1) + rng.random(n)) / H
+    org = np.broadcast_to(pos, (n, 3))
+    if lens.model == prt_amd.LENS_EQUIRECT:
+        phi, th = a * np.pi, b * (np.pi / 2)
+        l = np.stack([np.cos(th) * np.sin(phi), np.sin(th), np.cos(th) * np.cos(phi)], axis=1)
+        d = l[:, 0:1] * right + l[:, 1:2] * up + l[:, 2:3] * fwd
+    else:
+        d = fwd + a[:, None] * right + b[:, None] * up
+        if lens.lensRadius > 0:
+            rl, phi = lens.lensRadius * np.sqrt(rng.random(n)), 2 * np.pi * rng.random(n)
+            R, U = right / np.linalg.norm(right), up / np.linalg.norm(up)
+            org = pos + (rl * np.cos(phi))[:, None] * R + (rl * np.sin(phi))[:, None] * U
+            d = pos + lens.focus * d - org
+    return org, d
+
+
+def lens(args):
+    """Per workload: (a) prt_hip_lens_render on device memory, wall time of the call up to the synchronisation behind it; (c) the
+    frame-kernel launches inside (a), kernelMsSum over kernelLaunches; the two new kernels alone on the rows of one band, on device
+    arrays (wall time up to the synchronisation); (b) the route there was before, once: lens_host_band, query_radiance on host
+    arrays per chunk of at most 2^24 rays, a numpy sum over K.  (b) draws other jitter, so its image is compared by its mean only."""
+    spp, depth, seed = 8, 8, 12345
+    scene, camera, _ = prt_amd.setup_atrium_standin(1920, 1080, tris=262000, seed=1)
+    t = prt_amd.PathTracer(max_depth=depth, seed=seed)
+    t.upload_scene(scene)
+    out = {"workload": "c3_sponza_standin", "spp": spp, "max_depth": depth, "reps": args.reps, "device": t.device_info()[0],
+           "compute_units": t.device_info()[1], "source_sha16": prt_amd.loaded_source_sha16(), "lens": {}, "accumulate_alone": {}}
+    c = camera.desc
+    pos = np.array(list(c.pos), np.float64)
+    at, up = pos + np.array(list(c.dir), np.float64), (0.0, 1.0, 0.0)
+    sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
+    scratch = [DeviceArray(np.zeros(1 << 24, prt_amd.RAY_DTYPE)), DeviceArray(np.zeros((1 << 24, 3), np.float32))]
+    d_rays, d_rad = (b.ptr.value for b in scratch)
+    workloads = {"equirect_2048x1024_K1": prt_amd.lens_equirect(pos, 2048, 1024, K=1, fwd=list(c.dir), jitter_seed=1),
+                 "thin_lens_1920x1080_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 1920, 1080, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1),
+                 "thin_lens_3840x2160_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 3840, 2160, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1)}
+    for name, d in workloads.items():
+        W, H, K = d.width, d.height, d.K
+        rows = min(H, (1 << 24) // (W * K))
+        image = DeviceArray(np.zeros(W * H * 3, np.float32))
+        times = {k: [] for k in ("a_lens_render_wall", "c_frame_kernels", "rays_kernel_wall", "accumulate_kernel_wall")}
+        launches = 0
+        for rep in range(1 + args.reps):  # one warm-up round
+            sync()
+            t0 = time.perf_counter()
+            t.render_lens_async(d, image.ptr.value, spp)
+            st = t.stats()
+            dt = (time.perf_counter() - t0) * 1e3
+            launches = st["kernelLaunches"]
+            if rep:
+                times["a_lens_render_wall"].append(dt)
+                times["c_frame_kernels"].append(st["kernelMsSum"])
+            for key, call in (("rays_kernel_wall", lambda: t._L.prt_hip_lens_rays(t._ctx, C.byref(d), 0, rows, d_rays, 0, None)),
+                              ("accumulate_kernel_wall", lambda: t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, rows, d_rad, image.ptr.value, 0, None))):
+                sync()
+                t0 = time.perf_counter()
+                assert call() == 0
+                sync()
+                if rep:
+                    times[key].append((time.perf_counter() - t0) * 1e3)
+        t.render_lens_async(d, image.ptr.value, spp)
+        rays_traced_last_band = t.stats()["raysTraced"]
+        got = image.get(np.float32).reshape(H, W, 3) / np.float32(K)
+        image.free()
+        # (b), once: the chunks are the caller's to cut
+        rng = np.random.default_rng(7)
+        host = np.zeros((H, W, 3), np.float32)
+        tb = {"numpy_rays": 0.0, "query_radiance": 0.0, "numpy_sum": 0.0}
+        t0 = time.perf_counter()
+        for y0 in range(0, H, rows):
+            y1 = min(H, y0 + rows)
+            t1 = time.perf_counter()
+            org, dr = lens_host_band(d, y0, y1, rng)
+            t2 = time.perf_counter()
+            L = t.query_radiance(org, dr, spp, seed=seed + y0 * W * K)
+            t3 = time.perf_counter()
+            host[y0:y1] = L.reshape(y1 - y0, W, K, 3).sum(axis=2) / np.float32(K)
+            t4 = time.perf_counter()
+            tb["numpy_rays"] += (t2 - t1) * 1e3
+            tb["query_radiance"] += (t3 - t2) * 1e3
+            tb["numpy_sum"] += (t4 - t3) * 1e3
+            del org, dr, L
+        b_ms = (time.perf_counter() - t0) * 1e3
+        a, cc = float(np.median(times["a_lens_render_wall"])), float(np.median(times["c_frame_kernels"]))
+        out["lens"][name] = {
+            "rays": W * H * K, "bands": launches, "rows_per_band": rows, "ms": {k: spread(v) for k, v in times.items()},
+            "a_over_c": a / cc, "b_host_route_wall_ms": b_ms, "b_parts_ms": tb, "b_over_a": b_ms / a,
+            "new_kernels_ms_per_call": (float(np.median(times["rays_kernel_wall"])) + float(np.median(times["accumulate_kernel_wall"]))) * launches,
+            "rays_traced_last_band": rays_traced_last_band, "image_mean": float(got.mean(dtype=np.float64)),
+            "host_route_image_mean": float(host.mean(dtype=np.float64))}
+    # the accumulate kernel alone: 2^24 radiances (201 MB read) into 2^24 / K pixels
+    for K, (W, H) in ((1, (4096, 4096)), (8, (2048, 1024)), (64, (512, 512))):
+        d = prt_amd.lens_pinhole(pos, at, up, 0.9, W, H, K=K)
+        image = DeviceArray(np.zeros(W * H * 3, np.float32))
+        ms = []
+        for rep in range(2 + args.reps):
+            sync()
+            t0 = time.perf_counter()
+            assert t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, H, d_rad, image.ptr.value, 0, None) == 0
+            sync()
+            if rep >= 2:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        image.free()
+        nbytes = 12 * (1 << 24) + 12 * W * H
+        out["accumulate_alone"][f"K{K}"] = {"pixels": W * H, "wall_ms": spread(ms), "GB_per_s": nbytes / float(np.median(ms)) / 1e6}
+    for b in scratch:
+        b.free()
+    t.close()
+    emit(out, args.out)
+
+
 def host_rays(pts, d):
     """What a baker wrote in numpy: a tangent frame per point, the K directions rotated into it, the origin tiled."""
     N = pts["N"].astype(np.float64)
@@ -327,6 +454,7 @@ def main():
     ap.add_argument("--radiance", action="store_true")
     ap.add_argument("--bake", action="store_true")
     ap.add_argument("--atlas", action="store_true")
+    ap.add_argument("--lens", action="store_true")
     args = ap.parse_args()
     prt_amd.build()
     if args.radiance:
@@ -335,6 +463,8 @@ def main():
         return bake(args)
     if args.atlas:
         return atlas(args)
+    if args.lens:
+        return lens(args)
     W, H = (int(v) for v in args.size.split("x"))
     scene, camera, _ = prt_amd.setup_atrium_standin(W, H, tris=262000, seed=1)
     t = prt_amd.PathTracer(max_depth=8, test_entry_points=True)
