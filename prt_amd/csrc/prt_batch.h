@@ -15,7 +15,7 @@ struct BatchCtl {
     uint32_t* cursor;            // the claim cursor (the context's control words, cleared for the launch)
     uint32_t* spill;             // spill columns of the traversal stacks
     uint32_t spillStride;        // threads the columns were sized for
-    unsigned long long* counters; // the statistics (cleared for the launch); [7] counts stack overflows
+    unsigned long long* counters; // the statistics (cleared for the launch, prt_stats.h)
 };
 
 // The body of a batch kernel.  Src: count(), cursor() (= ctl.cursor), load(), store_hit(), store_occ() as trace_loop asks for them.
@@ -33,5 +33,5 @@ __device__ __forceinline__ void trace_batch(const DevScene& sc, Src& src, const 
     Traffic tr{};
     uint32_t overflow = 0;
     trace_loop<MODE, false>(sc, src, st, tr, overflow);
-    if (overflow) atomicAdd(&ctl.counters[7], 1ull);
+    if (overflow) atomicAdd(&ctl.counters[PRT_STAT_STACK_OVERFLOW], 1ull);
 }

@@ -318,65 +318,20 @@ int prt_hip_get_stats(prt_hip_ctx* c, prt_hip_stats* st)
     }
     // errors of ANY launch since the last call (the last one included): see prt_sticky_error
     const int sticky = prt_sticky_error(c, true);
-#ifdef PRT_PROFILE
-    if (h[14])
-        fprintf(stderr, "frame profile: waves %llu, per wave: shade %.1f%% (%.0f calls) trace %.1f%% (%.0f calls) idle/decide %.1f%% of %.2f Mcycles\n", h[14],
-                100.0 * h[8] / h[13], (double)h[11] / h[14], 100.0 * h[9] / h[13], (double)h[12] / h[14], 100.0 * h[10] / h[13], h[13] / 1e6 / h[14]);
-    if (h[14]) {
-        for (int m = 0; m < 4; m++)
-            fprintf(stderr, "  trace mode %d: %.1f M loop turns, %.1f lanes with a ray per turn, %.1f Gcycles in the loops => %.0f cycles per turn\n", m, h[16 + 3 * m] / 1e6,
-                    (double)h[17 + 3 * m] / (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1), h[18 + 3 * m] * 1024.0 / 1e9,
-                    h[18 + 3 * m] * 1024.0 / (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1));
-        for (int m = 0; m < 4; m++) {
-            const unsigned long long* q = h + 32 + 8 * m;
-            fprintf(stderr, "  mode %d rounds: node %.1f M with %.1f lanes, leaf %.1f M with %.1f lanes on a leaf (%.1f pair lanes working; serial build: lanes on a second triangle); refills %.1f M with %.1f lanes\n", m,
-                    q[0] / 1e6, (double)q[1] / (double)(q[0] ? q[0] : 1), q[2] / 1e6, (double)q[3] / (double)(q[2] ? q[2] : 1),
-                    (double)q[4] / (double)(q[2] ? q[2] : 1), q[6] / 1e6, (double)q[5] / (double)(q[6] ? q[6] : 1));
-        }
-        for (int m = 0; m < 4; m++) {
-            const unsigned long long* q = h + 32 + 8 * m;
-            const unsigned long long* w = h + 64 + 8 * m;
-            const double nr = (double)(q[0] ? q[0] : 1), lr = (double)(q[2] ? q[2] : 1);
-            fprintf(stderr, "  mode %d lanes sitting out: node rounds %.1f on a leaf, %.1f finished, %.1f without a ray; leaf rounds %.1f on a node, %.1f finished, %.1f without a ray; %.2f hit-update turns per leaf round; %.1f distinct records per node round\n",
-                    m, w[0] / nr, w[1] / nr, w[2] / nr, w[3] / lr, w[4] / lr, w[5] / lr, w[6] / lr, w[7] / nr);
-        }
-        for (int m = 0; m < 4; m++) {
-            const unsigned long long* w = h + 96 + 4 * m;
-            const double turns = (double)(h[16 + 3 * m] ? h[16 + 3 * m] : 1);
-            fprintf(stderr, "  mode %d cycles per loop turn: refill + result hand-off %.0f, entering / leaving BVHs %.0f, step phase %.0f\n", m, w[0] * 1024.0 / turns,
-                    w[1] * 1024.0 / turns, w[2] * 1024.0 / turns);
-        }
-        if (h[112])
-            fprintf(stderr, "  refills that left lanes empty: %.1f M, %.1f lanes each; at that moment %.1f rays in the block's OTHER queues, %.1f groups ready for shading, shade role taken %.2f of the time\n",
-                    h[112] / 1e6, (double)h[113] / h[112], (double)h[114] / h[112], (double)h[115] / h[112], (double)h[116] / h[112]);
-        if (h[118])
-            fprintf(stderr, "  shade passes with a bounce: %.1f M, %.1f of 64 lanes carry a path through it; the shade role is held %.2f of a block's time (sum of its waves' shade shares)\n",
-                    h[118] / 1e6, (double)h[119] / h[118], 4.0 * h[8] / h[13]);
-        fprintf(stderr, "  node steps that leave a lane on an internal record outside the hot set: %.2f G by descending from the parent, %.2f G by a pop (%.2f of them direct)\n",
-                h[120] / 1e9, h[121] / 1e9, (double)h[120] / (double)(h[120] + h[121] ? h[120] + h[121] : 1));
-        fprintf(stderr, "  cooperative leaf rounds in which a candidate of a leaf with alpha-tested triangles came up: %.1f M, %.0f cycles each from the candidate test to the end of the alpha tests = %.1f Gcycles of wave time\n",
-                h[122] / 1e6, h[123] * 1024.0 / (double)(h[122] ? h[122] : 1), h[123] * 1024.0 / 1e9);
-        fprintf(stderr, "  stack pops of modes 1-3: %.1f G, of them from the spill area in HBM: %.2f G\n", (h[32 + 15] + h[32 + 23] + h[32 + 31]) / 1e9, h[39] / 1e9);
-        fprintf(stderr, "  claims %.1f M, empty %.1f M; shade passes %.1f M with %.2f groups each\n", h[28] / 1e6, h[29] / 1e6, h[30] / 1e6, (double)h[31] / (double)(h[30] ? h[30] : 1));
+    prt_profile_report(h); // (the profile build only, prt_stats.h)
+    st->raysTraced = h[PRT_STAT_RAYS];
+    st->occludedTraced = h[PRT_STAT_OCCL];
+    st->nBox = h[PRT_STAT_BOX];
+    st->nTri = h[PRT_STAT_TRI];
+    st->nHit = h[PRT_STAT_HIT];
+    st->nTap = h[PRT_STAT_TAP];
+    st->nPx = h[PRT_STAT_PIXELS];
+    for (int m = 0; m < PRT_STAT_MODES; m++) { // (0 in the profile build, whose loop statistics overlay these words)
+        st->modeBox[m] = prt_stat_mode_words_valid ? h[prt_stat_mode(m, PRT_STAT_MODE_BOX)] : 0;
+        st->modeTri[m] = prt_stat_mode_words_valid ? h[prt_stat_mode(m, PRT_STAT_MODE_TRI)] : 0;
+        st->modeTap[m] = prt_stat_mode_words_valid ? h[prt_stat_mode(m, PRT_STAT_MODE_TAP)] : 0;
     }
-#endif
-    st->raysTraced = h[0];
-    st->occludedTraced = h[1];
-    st->nBox = h[2];
-    st->nTri = h[3];
-    st->nHit = h[4];
-    st->nTap = h[5];
-    st->nPx = h[6];
-    for (int m = 0; m < 4; m++) {
-#ifdef PRT_PROFILE
-        st->modeBox[m] = st->modeTri[m] = st->modeTap[m] = 0; // the words carry the profile build's loop statistics
-#else
-        st->modeBox[m] = h[16 + 3 * m];
-        st->modeTri[m] = h[17 + 3 * m];
-        st->modeTap[m] = h[18 + 3 * m];
-#endif
-    }
-    st->stackOverflow = h[7];
+    st->stackOverflow = h[PRT_STAT_STACK_OVERFLOW];
     fold_timing(c);
     st->kernelMs = c->accLaunches ? c->lastMs : 0.0;
     st->kernelMsSum = c->accMs;
@@ -384,7 +339,7 @@ int prt_hip_get_stats(prt_hip_ctx* c, prt_hip_stats* st)
     c->accMs = c->lastMs = 0.0;
     c->accLaunches = 0;
     if (sticky) return sticky;
-    if (h[7]) return fail(PRT_HIP_ESTACK, "BVH traversal needed more than 64 stack entries (the reference asserts here, bvh.cpp:552)");
+    if (h[PRT_STAT_STACK_OVERFLOW]) return fail(PRT_HIP_ESTACK, "BVH traversal needed more than 64 stack entries (the reference asserts here, bvh.cpp:552)");
     return PRT_HIP_OK;
 }
 

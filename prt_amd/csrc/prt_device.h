@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "prt_devmath.h"
+#include "prt_stats.h"
 
 #define PRT_MAX_BVH 8
 #ifndef PRT_STACK_LDS
@@ -23,9 +24,6 @@
 #define PRT_BLOCK 1024 // threads per workgroup: 16 waves share the frame kernel's pool, queues and hot records (2 workgroups per CU)
 #endif
 #define PRT_MAT_STRIDE 5 // float4 per material record
-#ifndef PRT_TRI2
-#define PRT_TRI2 1 // a leaf step tests two triangles (one: 569 ms against 547 on C3)
-#endif
 #ifndef PRT_IDLE_BREAK
 #define PRT_IDLE_BREAK 24 // finished rays that send the wave back to its refill point (a refill turn costs about four rounds: 8 -> 463, 16 -> 424, 24-32 -> 412-422 ms on C3)
 #endif
@@ -206,15 +204,7 @@ struct DevHit {
 struct Traffic {
     unsigned long long nBox, nTri; // a persistent trace lane can exceed 2^32
     uint32_t nHit, nTap;
-#ifdef PRT_PROFILE
-    // tallies of the profile build: rounds of either kind and the lanes that took part in them (wave-uniform); stack pops
-    // and those that came from the spill area in HBM (per lane)
-    unsigned long long pNodeRounds, pNodeLanes, pLeafRounds, pLeafLanes, pTri2Lanes, pPops, pDeepPops;
-    unsigned long long pNodeWaitLeaf, pNodeDone, pNodeNoRay, pLeafWaitNode, pLeafDone, pLeafNoRay, pLeafUpdates; // lanes that sit a round out, by reason (wave-uniform)
-    unsigned long long pDirectInt, pPopInt; // (per lane) steps that leave the lane on an internal record outside the hot set: reached by descending from its parent / by a pop
-    unsigned long long pAlphaRounds, pAlphaCycles; // (wave-uniform) cooperative leaf rounds in which a candidate looked its alpha record up, and the cycles from the candidate test to the end of the alpha tests
-    unsigned long long pNodeDistinct; // distinct records the lanes of the node rounds asked for (wave-uniform): the coherence of a wave's rays
-#endif
+    [[no_unique_address]] TraceTally prof; // the profile build's tallies (prt_stats.h); empty in the product
 };
 
 // ray.h:26-40: swap axis from the SIGNED components (Vector3f::GetLongestElement, vecmath.h:216)
@@ -687,10 +677,7 @@ __device__ __forceinline__ uint32_t tracer_pop(Tracer& T, const STK& st, Traffic
         return PRT_REF_NONE;
     } else {
         if (T.sp == 0) return PRT_REF_NONE;
-#ifdef PRT_PROFILE
-        tr.pPops++;
-        if (T.sp - 1 >= STK::kLds) tr.pDeepPops++;
-#endif
+        tr.prof.pop(T.sp - 1 >= STK::kLds);
         return st.get(--T.sp);
     }
 }
@@ -873,7 +860,6 @@ __device__ __forceinline__ void tracer_tri(const DevScene& sc, Tracer& T, const 
             return;
         }
     }
-#if PRT_TRI2
     if (left > 1u) {
         if (COUNT) tr.nTri++;
         if (tri_candidate<OCC, PACKET, COUNT>(sc, tri + 1u, hasAlpha, T.m, T.r, OCC ? T.maxT : T.hit.t, T.hit, tr) && OCC) {
@@ -886,10 +872,6 @@ __device__ __forceinline__ void tracer_tri(const DevScene& sc, Tracer& T, const 
     }
     if (left > 2u) T.ref += 30u; // first triangle + 2 (bits 4..), triangles left - 2 (bits 0..2; no borrow: left - 1 >= 2)
     else T.ref = tracer_pop<MODE, COUNT>(T, st, tr);
-#else
-    if (left > 1u) T.ref += 15u; // first triangle + 1 (bit 4), triangles left - 1
-    else T.ref = tracer_pop<MODE, COUNT>(T, st, tr);
-#endif
 }
 
 // ---------------------------------------------------------------------------- cooperative leaf rounds
@@ -906,20 +888,11 @@ __device__ __forceinline__ void tracer_tri(const DevScene& sc, Tracer& T, const 
 //   any hit:     a set bit means occluded.
 // The alpha test of a candidate is a function of (triangle, barycentrics) alone; it is evaluated by the pair's lane.
 // Leaves that do not fit into the 64 pairs of this round keep their lanes waiting for the next one.
-#ifndef PRT_COOP_LEAF
-#define PRT_COOP_LEAF 1
-#endif
 #ifndef PRT_COOP_MIN
 #define PRT_COOP_MIN 9u // leaf lanes that make a round a leaf round whatever the node lanes (9 leaves of 6 = 54 pairs)
 #endif
 #ifndef PRT_COOP_WEIGHT
 #define PRT_COOP_WEIGHT 4u // ... or when leaf lanes x this many >= node lanes
-#endif
-#ifndef PRT_TRI_NT
-#define PRT_TRI_NT 0 // triangle fetches with the non-temporal hint (an experiment for trees far larger than the caches)
-#endif
-#ifndef PRT_COOP_PREPOP
-#define PRT_COOP_PREPOP 1
 #endif
 #define PRT_COOP_TRI_BITS 26 // a table word = triangle index | owner lane << 26
 
@@ -947,9 +920,7 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     const unsigned long long takeMask = __ballot(take);
     const uint32_t last = 63u - (uint32_t)__builtin_clzll(takeMask); // (the first leaf lane always takes: n <= 8)
     const uint32_t pairs = (uint32_t)__builtin_amdgcn_readlane((int)(prefix + n), (int)last);
-#ifdef PRT_PROFILE
-    tr.pTri2Lanes += pairs;
-#endif
+    tr.prof.leaf_pairs(pairs);
     // ---- table: pair p -> (first triangle - prefix) | owner lane << 26, the same word for every pair of a leaf, so that the
     // eight stores need no predicate: store i goes to entry min(i, n - 1), lanes that take no part store to the dump word
     {
@@ -963,26 +934,18 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // (no instruction: LDS operations of one wave complete in order)
     const bool pair = lane < pairs;
     const uint32_t word = st.coop[lane];
-#if PRT_COOP_PREPOP
     // the entry a taker pops when its leaf is done is already known: read it beside the table, not after the round
     const int popAt = T.sp > 0 ? T.sp - 1 : 0;
     uint32_t popped = st.ldsRef[(popAt < STK::kLds ? popAt : 0) * PRT_BLOCK];
-#endif
     const int oaddr = (int)((pair ? (word >> PRT_COOP_TRI_BITS) : lane) << 2);
     const uint32_t tri = (word + lane) & PRT_COOP_TRI_MASK;
     __builtin_amdgcn_sched_barrier(0); // (addresses first: a register of the fetch must not be reused for them while it is in flight)
     prt_f3 a, b, c;
     if (pair) {
         const float* tp = sc.tris + 9 * (size_t)tri;
-#if PRT_TRI_NT
-        a = __builtin_nontemporal_load((const PRT_AS1 prt_f3u*)tp);
-        b = __builtin_nontemporal_load((const PRT_AS1 prt_f3u*)(tp + 3));
-        c = __builtin_nontemporal_load((const PRT_AS1 prt_f3u*)(tp + 6));
-#else
         a = *(const PRT_AS1 prt_f3u*)tp;
         b = *(const PRT_AS1 prt_f3u*)(tp + 3);
         c = *(const PRT_AS1 prt_f3u*)(tp + 6);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0); // the fetch is out before the lane exchanges, which need not wait for it
     // ---- the owner's ray constants (triangle.cpp:118-119 are per ray: prepare_shear)
@@ -999,16 +962,11 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     float t = -1.0f, bi = 0.0f, bj = 0.0f, bk = 0.0f;
     uint32_t primId = 0u;
     bool cand = false;
-#ifdef PRT_PROFILE
-    unsigned long long pAlpha0 = 0;
-#endif
     if (pair) {
         t = tri_intersect(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), bi, bj, bk);
         primId = tri; // the LEAF-ORDER index (tri_candidate)
         cand = t >= 0.0001f && t < limit;
-#ifdef PRT_PROFILE
-        pAlpha0 = __builtin_amdgcn_s_memtime();
-#endif
+        tr.prof.alpha_begin();
         // The alpha test of a candidate (bvh.cpp:336-338, 407-409) is a chain of dependent fetches that one or two lanes of the round walk
         // while the others wait (profile build: a quarter of C3's leaf rounds, a whole round's time each): the record carries its
         // texture's descriptor, and most tests end at the class of the tap's cell -- one word of a map that stays in the L2 -- instead
@@ -1021,12 +979,7 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
             const uint4 d = make_uint4(asu(u2.x), asu(u2.y), asu(u2.z), asu(u2.w));
             cand = alpha_decide<PACKET>(sc, d, u1.w, uv, tr);
         }
-#ifdef PRT_PROFILE
-        if (__ballot(cand && (flags & 4u)) != 0ull) { // (ballot of the lanes inside `if (pair)`: some candidate lies in a leaf with alpha-tested triangles)
-            tr.pAlphaRounds++;
-            tr.pAlphaCycles += __builtin_amdgcn_s_memtime() - pAlpha0;
-        }
-#endif
+        tr.prof.alpha_end(cand, (flags & 4u) != 0u);
     }
     const unsigned long long acc = __ballot(cand);
     // ---- owners
@@ -1039,16 +992,12 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
                 T.sp = 0;
                 T.m = sc.bvhCount; // finished
             } else {
-#if PRT_COOP_PREPOP
                 if (T.sp == 0) T.ref = PRT_REF_NONE;
                 else {
                     if (popAt >= STK::kLds) popped = st.get(popAt);
                     T.sp = popAt;
                     T.ref = popped;
                 }
-#else
-                T.ref = tracer_pop<MODE, false>(T, st, tr);
-#endif
             }
         }
     } else {
@@ -1057,9 +1006,7 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
             // once at the end
             uint32_t win = 0xffffffffu;
             for (;;) {
-#ifdef PRT_PROFILE
-                tr.pLeafUpdates++;
-#endif
+                tr.prof.leaf_update();
                 const bool more = seg != 0u;
                 if (!__any(more)) break;
                 const uint32_t src = more ? prefix + (uint32_t)__builtin_ctz(seg) : lane;
@@ -1085,7 +1032,6 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
                 }
             }
         }
-#if PRT_COOP_PREPOP
         if (take) {
             if (MODE == PRT_MODE_PACKET) T.ref = tracer_pop<MODE, false>(T, st, tr); // (its pop tests the entry distance against the new hit.t)
             else if (T.sp == 0) T.ref = PRT_REF_NONE;
@@ -1095,9 +1041,6 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
                 T.ref = popped;
             }
         }
-#else
-        if (take) T.ref = tracer_pop<MODE, false>(T, st, tr);
-#endif
     }
 }
 
@@ -1107,29 +1050,14 @@ __device__ __forceinline__ bool ref_is_leaf(uint32_t ref) { return (ref & PRT_RE
 // Step phase of the wave loops: a step is one internal node or one triangle.  Each round the larger of the two groups of
 // lanes steps (the other waits: SIMD lanes that cannot share an instruction stream), until PRT_IDLE_BREAK lanes have nothing
 // to step on -- their ray is finished or moves to the next BVH -- and the wave goes back to its refill point to serve them.
-// `queued()` (wave-uniform) tells how many rays wait in the queue the wave refills from: a wave that runs with lanes WITHOUT a
-// ray -- the queue was short when it last refilled -- looks every fourth round and goes back to its refill point as soon as
-// PRT_EMPTY_GAIN rays have arrived, instead of walking its few rays to their end at a fraction of its width.
-#ifndef PRT_EMPTY_BREAK
-#define PRT_EMPTY_BREAK 0u // lanes without a ray (plus finished ones) from which the queue is polled; 0 = never (measured: 16 / 16 costs 2 %, 8 / 8 7 %, 24 / 24 nothing: the refill turn it buys costs what the fuller rounds save)
-#endif
-#ifndef PRT_EMPTY_GAIN
-#define PRT_EMPTY_GAIN 16u
-#endif
 // the refill point of a traversal kind (PRT_MODE_*, defined below: 0 primary packets, 1 scatter rays, 2 / 3 occlusion rays)
 __device__ __forceinline__ constexpr uint32_t idle_break(int mode)
 {
     return mode == 1 ? (uint32_t)(PRT_IDLE_BREAK_SCATTER) : mode >= 2 ? (uint32_t)(PRT_IDLE_BREAK_OCC) : (uint32_t)(PRT_IDLE_BREAK);
 }
-struct NoQueue {
-    __device__ __forceinline__ uint32_t operator()() const { return 0u; }
-};
-template <int MODE, bool COUNT, class STK, class Queued = NoQueue>
-__device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, bool active, const STK& st, Traffic& tr, uint32_t& overflow,
-                                                 const Queued& queued = Queued())
+template <int MODE, bool COUNT, class STK>
+__device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, bool active, const STK& st, Traffic& tr, uint32_t& overflow)
 {
-    const uint32_t empty = 64u - (uint32_t)__popcll(__ballot(active)); // (lanes take rays at the refill point only)
-    uint32_t round = 0;
     for (;;) {
         const bool onNode = active && ref_is_internal(T.ref);
         const bool onLeaf = active && ref_is_leaf(T.ref);
@@ -1137,7 +1065,7 @@ __device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, 
         if (nNode + nLeaf == 0u) break;
         // Which kind steps.  Serial leaf steps (counting build): the larger group.  Cooperative leaf rounds: a leaf lane stands for
         // about six pair lanes, so leaves wait until a round's worth of pairs has gathered or few lanes are left on nodes.
-        const bool doNode = (PRT_COOP_LEAF && !COUNT) ? (nLeaf == 0u || (nLeaf < PRT_COOP_MIN && nLeaf * PRT_COOP_WEIGHT < nNode)) : nNode >= nLeaf;
+        const bool doNode = !COUNT ? (nLeaf == 0u || (nLeaf < PRT_COOP_MIN && nLeaf * PRT_COOP_WEIGHT < nNode)) : nNode >= nLeaf;
 #ifdef PRT_PAD_VALU
         { // sensitivity probe of tools/build_variants.py: PRT_PAD_VALU extra vector instructions per round (never in the product)
             float pad = T.maxT;
@@ -1146,52 +1074,18 @@ __device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, 
             asm volatile("" ::"v"(pad));
         }
 #endif
-#ifdef PRT_PROFILE
+        tr.prof.round(doNode, T.ref, onNode, onLeaf, active && T.ref == PRT_REF_NONE, active, nNode, nLeaf, COUNT);
         if (doNode) {
-            { // distinct records of this round: one per group of lanes that stand on the same node
-                unsigned long long m = __ballot(onNode);
-                while (m) {
-                    const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)T.ref, (int)__builtin_ctzll(m));
-                    m &= ~__ballot(onNode && T.ref == r);
-                    tr.pNodeDistinct++;
-                }
-            }
-            tr.pNodeRounds++;
-            tr.pNodeLanes += nNode;
-            tr.pNodeWaitLeaf += nLeaf;
-            tr.pNodeDone += (unsigned long long)__popcll(__ballot(active && T.ref == PRT_REF_NONE));
-            tr.pNodeNoRay += (unsigned long long)__popcll(__ballot(!active));
-        } else {
-            tr.pLeafRounds++;
-            tr.pLeafLanes += nLeaf;
-            tr.pLeafWaitNode += nNode;
-            tr.pLeafDone += (unsigned long long)__popcll(__ballot(active && T.ref == PRT_REF_NONE));
-            tr.pLeafNoRay += (unsigned long long)__popcll(__ballot(!active));
-            if (!(PRT_COOP_LEAF && !COUNT)) tr.pTri2Lanes += (unsigned long long)__popcll(__ballot(onLeaf && (T.ref & 15u) > 1u));
-        }
-#endif
-        if (doNode) {
-#ifdef PRT_PROFILE
-            const int sp0 = T.sp;
-#endif
+            tr.prof.node_begin(T.sp);
             if (onNode) tracer_node<MODE, COUNT>(sc, T, st, tr, overflow);
-#ifdef PRT_PROFILE
-            if (onNode && ref_is_internal(T.ref) && !(T.ref & PRT_REF_HOT)) {
-                if (T.sp < sp0) tr.pPopInt++;
-                else tr.pDirectInt++;
-            }
-#endif
-        } else if (PRT_COOP_LEAF && !COUNT) {
+            tr.prof.node_end(onNode && ref_is_internal(T.ref) && !(T.ref & PRT_REF_HOT), T.sp);
+        } else if (!COUNT) {
             tracer_leaf_coop<MODE>(sc, T, onLeaf, st, tr);
         } else {
             if (onLeaf) tracer_tri<MODE, COUNT>(sc, T, st, tr);
         }
         const uint32_t done = (uint32_t)__popcll(__ballot(active && T.ref == PRT_REF_NONE));
         if (done >= idle_break(MODE)) break;
-        if (PRT_EMPTY_BREAK && empty + done >= PRT_EMPTY_BREAK && (++round & 3u) == 0u) {
-            const uint32_t gain = empty + done < PRT_EMPTY_GAIN ? empty + done : PRT_EMPTY_GAIN;
-            if (queued() >= gain) break;
-        }
     }
 }
 

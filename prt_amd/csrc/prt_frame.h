@@ -28,7 +28,7 @@
 #include "prt_lanes.h"
 
 #ifndef PRT_POOL_CHUNKS
-#define PRT_POOL_CHUNKS 16 // rows of 64 pixel groups a block keeps in flight (per wave: one row, as with round 2's 4 rows for 4 waves)
+#define PRT_POOL_CHUNKS 16 // rows of 64 pixel groups a block keeps in flight (one row per wave)
 #endif
 #ifndef PRT_FRAME_WAVES
 #define PRT_FRAME_WAVES 8 // waves per SIMD the frame kernel is compiled for: 64 VGPRs, 80 SGPRs, 2 workgroups of 1024 threads per CU (78 KB of LDS each)
@@ -36,20 +36,11 @@
 #ifndef PRT_SHADE_MIN
 #define PRT_SHADE_MIN 192u // ready groups (of the pool's 1024) that make a wave at a decision point take a shade role (48: 392-402 ms, 96: 390, 192: 386 on C3)
 #endif
-#ifndef PRT_HOT_LDS
-#define PRT_HOT_LDS 1 // keep the PRT_HOT_NODES records nearest the roots in LDS (256 records = 16 KB per workgroup of 16 waves)
-#endif
 #ifndef PRT_TRACE_PRIO
 #define PRT_TRACE_PRIO 1
 #endif
 #ifndef PRT_SHADE_PRIO
 #define PRT_SHADE_PRIO 0 // issue priority of the wave that holds the shade role (it PRODUCES the rays the tracing waves wait for)
-#endif
-#ifndef PRT_TRACE_MIN
-#define PRT_TRACE_MIN 0u // a wave at a decision point shades first when the fullest queue holds fewer rays than this and PRT_TRACE_READY groups are ready (0 = rule off)
-#endif
-#ifndef PRT_TRACE_READY
-#define PRT_TRACE_READY 8u
 #endif
 #ifndef PRT_SHADERS
 #define PRT_SHADERS 4 // shade roles per block (a power of two): each owns every PRT_SHADERS-th row of the pool; all append to the block's queues
@@ -58,25 +49,15 @@
 #ifndef PRT_CLAIM
 #define PRT_CLAIM 128u // queue entries a wave reserves at a time
 #endif
-// Which queue a wave at a decision point traces (round 4).  Rounds 2-3: the fullest -- so every wave that came free took the scatter queue
-// and they ran it dry together while hundreds of occlusion and primary rays waited for a wave (profiles/r04_experiments.txt E).  Now
-// the queue with the most rays PER WAVE that would then be on it: score = 1 + len * PRT_BALANCE / (waves on it * PRT_BALANCE_W +
-// PRT_BALANCE); the waves spread over the queues in proportion to their lengths and a queue without a wave gets the next one.
-// C3 370 -> 357 ms; weights 8 .. 64 alike; PRT_BALANCE 0 = the fullest queue.
-#ifndef PRT_BALANCE
-#define PRT_BALANCE 1
-#endif
+// Which queue a wave at a decision point traces: the one with the most rays PER WAVE that would then be on it, score = 1 + len /
+// (waves on it * PRT_BALANCE_W + 1).  The waves spread over the queues in proportion to their lengths and a queue without a wave gets
+// the next one.  (Under "the fullest queue" every wave that came free took the scatter queue and they ran it dry together while
+// hundreds of occlusion and primary rays waited for a wave: C3 370 against 357 ms, profiles/r04_experiments.txt E; weights 8 .. 64 alike.)
 #ifndef PRT_BALANCE_W
 #define PRT_BALANCE_W 16
 #endif
 #ifndef PRT_DRAIN_READY
 #define PRT_DRAIN_READY 1024u // ready groups at which tracing waves stop refilling (so that one of them comes free to shade): the whole pool
-#endif
-#ifndef PRT_SHADE_INLINE
-#define PRT_SHADE_INLINE __noinline__
-#endif
-#ifndef PRT_ROLE_INLINE
-#define PRT_ROLE_INLINE __noinline__
 #endif
 #ifndef PRT_WATCHDOG_TICKS
 #define PRT_WATCHDOG_TICKS 200000000ull // a wave that has found no work for this long gives up: 2 s of s_memrealtime (the constant 100 MHz counter: the
@@ -103,7 +84,7 @@ struct FrameArgs {
     uint32_t rowsPerBlock; // rows a block may hold at a time (<= PRT_POOL_CHUNKS; fewer when the launch is small)
     uint32_t spreadRows;   // rows are 8 clusters of 8 work items spread over the launch instead of 64 consecutive items
     float* rgb;
-    unsigned long long* counters; // PRT_STAT_SHARDS copies of: rays, occl, nBox, nTri, nHit, nTap, nPx, overflow; word PRT_STAT_OCCL_SKIPPED
+    unsigned long long* counters; // PRT_STAT_SHARDS copies of the statistics words (prt_stats.h)
     uint32_t* ctrl;               // row cursors, watchdog flag and report (PRT_CTRL_CURSORS)
     // per pool group (block * PRT_POOL_GROUPS + i)
     uint32_t* gRng;
@@ -136,7 +117,7 @@ struct FrameAccArgs {
     float4* accSum;   // per camera pixel: xyz the colour sum of its packets, w bits(samples so far); 0 = never rendered
 };
 
-// Adaptive sampling (prt_hip_render_adaptive): frame_kernel_adapt's arguments are a FrameAccArgs (so frame_acc_args
+// Adaptive sampling (prt_hip_render_adaptive): frame_kernel_adapt's arguments are a FrameAccArgs (so frame_args<FrameAccArgs>
 // reads them as a prefix) followed by the launch's compacted pixel list and the per-pixel moment records.  Work item w is the pixel
 // list[w] instead of work_item_pixel(w); every packet end folds the packet's mean luminance into the pixel's moment record.
 struct FrameAdaptArgs {
@@ -156,13 +137,13 @@ struct FrameProbeArgs {
 struct __attribute__((aligned(16))) BlockState { // LDS, one per workgroup
     // one stack column per thread: PRT_STACK_LDS (12) references, or 6 (reference, entry distance) pairs for the packet traversal
     uint32_t stack[PRT_STACK_LDS * PRT_BLOCK];
-    float hot[PRT_HOT_LDS ? PRT_HOT_NODES * 16 : 4]; // DevScene::hotNodes (16-byte aligned: read with ds_read_b128)
+    float hot[PRT_HOT_NODES * 16]; // the PRT_HOT_NODES records nearest the roots, DevScene::hotNodes: 256 records = 16 KB per workgroup (16-byte aligned: read with ds_read_b128)
     uint32_t coop[(PRT_BLOCK / 64) * PRT_COOP_STRIDE]; // per wave: the pair table of the cooperative leaf rounds (prt_device.h)
     uint32_t pending[PRT_POOL_GROUPS];
     uint32_t readyList[PRT_POOL_GROUPS]; // the shade role's work list of one sweep
     uint32_t chunkLive[PRT_POOL_CHUNKS]; // groups of the row that are not done; 0 = the row can take new work
     uint32_t qTail[Q_COUNT], qHead[Q_COUNT];
-    uint32_t qWaves[Q_COUNT];      // waves tracing each queue right now (PRT_BALANCE: the decision point shares the waves out by queue length)
+    uint32_t qWaves[Q_COUNT];      // waves tracing each queue right now (the decision point shares the waves out by queue length)
     uint32_t qRes[Q_COUNT];        // PRT_SHADERS shade roles: entries RESERVED behind the tail (published to qTail in reservation order)
     uint32_t lock[PRT_SHADERS];    // shade role(s)
     uint32_t ready[PRT_SHADERS];   // groups with pending == 0, per shade role (a hint for the role decision, not a correctness word)
@@ -247,36 +228,19 @@ __device__ __forceinline__ uint32_t work_item_pixel(const FrameArgs& A, uint32_t
 // function has no kernel-argument pointer of its own): rebuilt from readfirstlane halves it is a uniform pointer into constant
 // memory, so fields arrive by scalar loads where they are used, and the data pointers in them are dereferenced as global
 // addresses (gld / gst / nt_*) with a scalar base -- the code a kernel with by-value arguments gets.
-typedef const __attribute__((address_space(4))) FrameArgs* FrameKernargs;
 __device__ __forceinline__ uint64_t frame_kernarg_bits() { return (uint64_t)(const __attribute__((address_space(4))) void*)__builtin_amdgcn_kernarg_segment_ptr(); }
-__device__ __forceinline__ const FrameArgs& frame_args(uint64_t bits)
+// the segment read as ARGS: FrameArgs, or the kernel's own argument struct, which begins with one (FrameAccArgs, FrameAdaptArgs,
+// FrameProbeArgs)
+template <class ARGS = FrameArgs>
+__device__ __forceinline__ const ARGS& frame_args(uint64_t bits)
 {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
-    return *(const FrameArgs*)(FrameKernargs)(((uint64_t)hi << 32) | lo);
-}
-// frame_kernel_acc only: the same segment read as FrameAccArgs
-__device__ __forceinline__ const FrameAccArgs& frame_acc_args(uint64_t bits)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
-    return *(const FrameAccArgs*)(const __attribute__((address_space(4))) FrameAccArgs*)(((uint64_t)hi << 32) | lo);
-}
-// frame_kernel_adapt only: the same segment read as FrameAdaptArgs
-__device__ __forceinline__ const FrameAdaptArgs& frame_adapt_args(uint64_t bits)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
-    return *(const FrameAdaptArgs*)(const __attribute__((address_space(4))) FrameAdaptArgs*)(((uint64_t)hi << 32) | lo);
-}
-
-// frame_kernel_probe only: the same segment read as FrameProbeArgs
-__device__ __forceinline__ const FrameProbeArgs& frame_probe_args(uint64_t bits)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bits >> 32));
-    return *(const FrameProbeArgs*)(const __attribute__((address_space(4))) FrameProbeArgs*)(((uint64_t)hi << 32) | lo);
+    return *(const ARGS*)(const __attribute__((address_space(4))) ARGS*)(((uint64_t)hi << 32) | lo);
 }
 // PROBE: origin (a = 0) or direction (a = 1) of probe q, one 16-byte load
 __device__ __forceinline__ Vec3 probe_ray_vec(uint64_t kargs, uint32_t q, uint32_t a)
 {
-    const float4 v = gld4((const float4*)frame_probe_args(kargs).rays + 2 * (size_t)q + a);
+    const float4 v = gld4((const float4*)frame_args<FrameProbeArgs>(kargs).rays + 2 * (size_t)q + a);
     return mk3(v.x, v.y, v.z);
 }
 
@@ -498,16 +462,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
     if (needBounce) {
         // ---- one bounce (path_tracer.cpp:131-190 and the Russian roulette of :258-265)
         const bool active = slot < alive;
-#ifdef PRT_PROFILE
-        { // lanes of the pass that carry a path through its bounce (of 64)
-            const unsigned long long carrying = __ballot(slot < alive); // (this branch is per group: the ballot is of the lanes in it)
-            if (lane == (uint32_t)__builtin_ctzll(__ballot(true))) {
-                unsigned long long* C = A.counters + (size_t)(blockIdx.x % PRT_STAT_SHARDS) * PRT_STAT_STRIDE;
-                atomicAdd(&C[118], 1ull);
-                atomicAdd(&C[119], (unsigned long long)__popcll(carrying));
-            }
-        }
-#endif
+        FrameProfile::bounce(A.counters, active);
         uint32_t rtype = 2u;
         if (active) {
             const float4* mp = sc.mats + PRT_MAT_STRIDE * (size_t)material;
@@ -619,7 +574,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         color = add3(color, res);
         if constexpr (ADAPT) { // Welford: m += 1; d = L - mean; mean += d / m; M2 += d * (L - mean), L the packet's mean luminance
             if (slot == 0) {   // (the group owns the pixel for the pass; the hand-off between shade rounds orders the record as gColor)
-                const FrameAdaptArgs& AD = frame_adapt_args(kargs);
+                const FrameAdaptArgs& AD = frame_args<FrameAdaptArgs>(kargs);
                 const size_t pi = (size_t)x + (size_t)y * cam.width;
                 const float L = (0.2126f * res.x + 0.7152f * res.y + 0.0722f * res.z) * 0.125f;
                 const float4 mo = gld4(&AD.accMom[pi]);
@@ -634,7 +589,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         } else {
             uint32_t total = samples;
             if constexpr (ACC) { // the pixel's state and sum go back with its new count; the image is the mean over all of it
-                const FrameAccArgs& AA = frame_acc_args(kargs);
+                const FrameAccArgs& AA = frame_args<FrameAccArgs>(kargs);
                 const size_t pi = (size_t)x + (size_t)y * cam.width;
                 total += gld((const uint32_t*)&AA.accSum[pi] + 3);
                 if (slot == 0) {
@@ -750,7 +705,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
         if (newTail[q] != qBase[q] && lane == 0u) {
             if (PRT_SHADERS > 1) {
                 // in reservation order: the tail moves over this pass's entries only when everything reserved before them is published
-                // (the other shade role publishes its queues in the same ascending order, so the two waits cannot form a cycle);
+                // (every shade role publishes its queues in the same ascending order, so the waits cannot form a cycle);
                 // bounded: a bug here must end as the watchdog's error, never as a hung GPU
                 uint32_t spins = 0;
                 while (lds_ld_acq(&B->qTail[q]) != qBase[q] && ++spins < (1u << 24)) __builtin_amdgcn_s_sleep(1);
@@ -779,7 +734,7 @@ __device__ __noinline__ uint32_t shade_pass(uint64_t kargs, uint32_t P, uint32_t
 // checks of tools/ and tests/ look for, and their code.)
 #define PRT_QUEUE_PROBE 4
 template <int QMODE, bool COUNT>
-__device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
+__device__ __noinline__ void trace_queue(uint64_t kargs)
 {
     constexpr int MODE = QMODE & 3;
     constexpr bool PROBE = (QMODE & PRT_QUEUE_PROBE) != 0;
@@ -791,7 +746,7 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
     const uint32_t slotBase = blockIdx.x * PRT_POOL_SLOTS;
     const uint32_t* blockQ = A.qE + (size_t)blockIdx.x * Q_COUNT * PRT_POOL_SLOTS;
     const StackT<NLDS> st{(lds_u32*)&B->stack[tid], (lds_f32*)&B->stack[NLDS * PRT_BLOCK + tid], A.spill,
-                          A.spillStride, PRT_HOT_LDS ? (const lds_f4*)&B->hot[0] : nullptr, (lds_u32*)&B->coop[(tid >> 6) * PRT_COOP_STRIDE]};
+                          A.spillStride, (const lds_f4*)&B->hot[0], (lds_u32*)&B->coop[(tid >> 6) * PRT_COOP_STRIDE]};
     const DevScene& sc = A.sc;
     const Vec3 camPos = mk3(A.cam.pos[0], A.cam.pos[1], A.cam.pos[2]);
     const Vec3 sceneLight = mk3(sc.lightDir[0], sc.lightDir[1], sc.lightDir[2]);
@@ -813,19 +768,13 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 #pragma unroll
     for (uint32_t j = 0; j < PRT_CLAIM / 64u; j++) held[j] = 0;
     __builtin_amdgcn_s_setprio(PRT_TRACE_PRIO); // tracing waves sit on dependent loads: they issue first, shading fills in
-#ifdef PRT_PROFILE
-    unsigned long long pTurns = 0, pLanes = 0, pClaims = 0, pEmptyClaims = 0, pRefills = 0, pRefillLanes = 0, pT0 = __builtin_amdgcn_s_memtime();
-    unsigned long long pTRefill = 0, pTEnter = 0, pTStep = 0;
-    unsigned long long pShortTurns = 0, pShortLanes = 0, pShortOthers = 0, pShortReady = 0, pShortLock = 0;
-#endif
+    QueueProfile prof = QueueProfile::start();
     for (;;) {
         // ---- 1. refill.  The wave takes PRT_CLAIM entries of the queue at a time and hands them to its lanes as they come
         // free: consecutive entries are rays of neighbouring pixels at the same bounce, and lanes that walk the same part of
         // the tree step together.  The entries are READ when they are claimed and wait in registers (held[]): the ring's
         // capacity argument -- at most one ray per slot and mode is out -- only holds for entries consumed in order.
-#ifdef PRT_PROFILE
-        const unsigned long long pTa = __builtin_amdgcn_s_memtime();
-#endif
+        prof.turn_begin();
         const unsigned long long need = __ballot(!active);
         if (need) {
             const uint32_t k = (uint32_t)__popcll(need);
@@ -883,30 +832,6 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
             } else {
                 heldNext += k;
             }
-#ifdef PRT_PROFILE
-            {   // when lanes stay empty after the refill: where is the block's work?
-                const uint32_t short_ = (uint32_t)__popcll(__ballot(!active && !gotRay));
-                if (short_) {
-                    uint32_t others = 0;
-                    for (int q = 0; q < Q_COUNT; q++)
-                        if (q != MODE) {
-                            const int32_t d = (int32_t)(bcast0(lds_ld(&B->qTail[q])) - bcast0(lds_ld(&B->qHead[q])));
-                            others += d > 0 ? (uint32_t)d : 0u;
-                        }
-                    pShortTurns++;
-                    pShortLanes += short_;
-                    pShortOthers += others;
-                    pShortReady += bcast0(block_ready(B));
-                    pShortLock += bcast0(block_lock_free(B) ? 0u : 1u);
-                }
-            }
-            pClaims++;
-            if (!__any(gotRay)) pEmptyClaims++;
-            else {
-                pRefills++;
-                pRefillLanes += (unsigned long long)__popcll(__ballot(!active && gotRay));
-            }
-#endif
             if (!active && gotRay) {
                 owner = bits & 0x3ffffffu;
                 const uint32_t gs = slotBase + owner;
@@ -945,6 +870,7 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
                     T.m = sc.bvhCount - 1u;
                 active = true;
             }
+            prof.refill<MODE>(B, need, active);
         }
         // ---- 2. rays that finished in the previous turn: their result stores were issued before this turn's refill loads, which
         // the refill has waited for (vector memory operations of a wave retire in order), so the release below is free -> tell the group
@@ -955,19 +881,13 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
                 sig = PRT_NONE;
             }
         }
-#ifdef PRT_PROFILE
-        const unsigned long long pTb = __builtin_amdgcn_s_memtime();
-        pTRefill += pTb - pTa;
-#endif
+        prof.handed_off();
         if (!__any(active)) break;
-#ifdef PRT_PROFILE
-        pTurns++;
-        pLanes += (unsigned long long)__popcll(__ballot(active));
-#endif
+        prof.turn(active);
         // ---- 3. new rays enter their first BVH (one that misses every root box is finished at once), 4. step, 5. rays that have
         // left their last BVH store their result and give the lane up NOW, so that the next turn's refill -- the next thing the
-        // wave does -- hands it a new ray; retiring them behind the refill (as the first version of this loop did) left every
-        // such lane empty for a whole step phase: 18 of 64 lanes in a scatter-ray node round (profiles/r03_experiments.txt).
+        // wave does -- hands it a new ray; retiring them behind the refill would leave every such lane empty for a whole step phase: 18 of
+        // 64 lanes in a scatter-ray node round (profiles/r03_experiments.txt).
 #pragma unroll 1
         for (int pass = 0; pass < 2; pass++) {
             if (active && T.ref == PRT_REF_NONE) {
@@ -984,24 +904,15 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
                     active = false;
                 }
             }
-#ifdef PRT_PROFILE
-            const unsigned long long pTc = __builtin_amdgcn_s_memtime();
-            if (pass == 0) pTEnter += pTc - pTb;
-#endif
-            if (pass == 0)
-                trace_step_phase<MODE, COUNT>(sc, T, active, st, tr, overflow, [&]() -> uint32_t {
-                    const int32_t d = (int32_t)(bcast0(lds_ld(&B->qTail[MODE])) - bcast0(lds_ld(&B->qHead[MODE])));
-                    return (heldEnd - heldNext) + (d > 0 ? (uint32_t)d : 0u);
-                });
-#ifdef PRT_PROFILE
-            if (pass == 0) pTStep += __builtin_amdgcn_s_memtime() - pTc;
-#endif
+            prof.entered(pass);
+            if (pass == 0) trace_step_phase<MODE, COUNT>(sc, T, active, st, tr, overflow);
+            prof.stepped(pass);
         }
     }
     if (overflow) lds_st(&B->overflow, 1u);
     if (COUNT) {
         block_count_traffic(B, tr);
-        // the same events per traversal mode (bench.py splits the algorithmic bytes by them): words 16 + 3 * MODE of the counters
+        // the same events per traversal mode (bench.py splits the algorithmic bytes by them)
         unsigned long long b = tr.nBox, t = tr.nTri, p = tr.nTap;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -1010,66 +921,14 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
             p += (unsigned long long)__shfl_xor((long long)p, o, 64);
         }
         if (lane == 0) {
-            unsigned long long* C = A.counters + (size_t)(blockIdx.x % PRT_STAT_SHARDS) * PRT_STAT_STRIDE;
-            if (b) atomicAdd(&C[16 + MODE * 3], b);
-            if (t) atomicAdd(&C[17 + MODE * 3], t);
-            if (p) atomicAdd(&C[18 + MODE * 3], p);
+            unsigned long long* C = prt_stat_copy(A.counters);
+            if (b) atomicAdd(&C[prt_stat_mode(MODE, PRT_STAT_MODE_BOX)], b);
+            if (t) atomicAdd(&C[prt_stat_mode(MODE, PRT_STAT_MODE_TRI)], t);
+            if (p) atomicAdd(&C[prt_stat_mode(MODE, PRT_STAT_MODE_TAP)], p);
         }
     }
     __builtin_amdgcn_s_setprio(0);
-#ifdef PRT_PROFILE
-    unsigned long long pops = tr.pPops, deepPops = tr.pDeepPops; // per lane: summed over the wave by all its lanes
-    unsigned long long directInt = tr.pDirectInt, popInt = tr.pPopInt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        directInt += (unsigned long long)__shfl_xor((long long)directInt, o, 64);
-        popInt += (unsigned long long)__shfl_xor((long long)popInt, o, 64);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pops += (unsigned long long)__shfl_xor((long long)pops, o, 64);
-        deepPops += (unsigned long long)__shfl_xor((long long)deepPops, o, 64);
-    }
-    if (lane == 0) {
-        unsigned long long* C = A.counters + (size_t)(blockIdx.x % PRT_STAT_SHARDS) * PRT_STAT_STRIDE;
-        if (MODE != PRT_MODE_PACKET) { // (the packet traversal pops in a loop of its own and is not counted; word 39 is its slot)
-            atomicAdd(&C[39 + MODE * 8], pops);
-            atomicAdd(&C[39], deepPops);
-        }
-        atomicAdd(&C[32 + MODE * 8], tr.pNodeRounds);
-        atomicAdd(&C[33 + MODE * 8], tr.pNodeLanes);
-        atomicAdd(&C[34 + MODE * 8], tr.pLeafRounds);
-        atomicAdd(&C[35 + MODE * 8], tr.pLeafLanes);
-        atomicAdd(&C[36 + MODE * 8], tr.pTri2Lanes);
-        atomicAdd(&C[112], pShortTurns);
-        atomicAdd(&C[113], pShortLanes);
-        atomicAdd(&C[114], pShortOthers);
-        atomicAdd(&C[115], pShortReady);
-        atomicAdd(&C[116], pShortLock);
-        atomicAdd(&C[96 + MODE * 4], pTRefill >> 10);
-        atomicAdd(&C[97 + MODE * 4], pTEnter >> 10);
-        atomicAdd(&C[98 + MODE * 4], pTStep >> 10);
-        atomicAdd(&C[64 + MODE * 8], tr.pNodeWaitLeaf);
-        atomicAdd(&C[65 + MODE * 8], tr.pNodeDone);
-        atomicAdd(&C[66 + MODE * 8], tr.pNodeNoRay);
-        atomicAdd(&C[67 + MODE * 8], tr.pLeafWaitNode);
-        atomicAdd(&C[68 + MODE * 8], tr.pLeafDone);
-        atomicAdd(&C[69 + MODE * 8], tr.pLeafNoRay);
-        atomicAdd(&C[70 + MODE * 8], tr.pLeafUpdates);
-        atomicAdd(&C[71 + MODE * 8], tr.pNodeDistinct);
-        atomicAdd(&C[122], tr.pAlphaRounds);
-        atomicAdd(&C[123], tr.pAlphaCycles >> 10);
-        atomicAdd(&C[120], directInt);
-        atomicAdd(&C[121], popInt);
-        atomicAdd(&C[37 + MODE * 8], pRefillLanes);
-        atomicAdd(&C[38 + MODE * 8], pRefills);
-        atomicAdd(&C[16 + MODE * 3], pTurns);
-        atomicAdd(&C[17 + MODE * 3], pLanes);
-        atomicAdd(&C[18 + MODE * 3], (__builtin_amdgcn_s_memtime() - pT0) >> 10);
-        atomicAdd(&C[28], pClaims);
-        atomicAdd(&C[29], pEmptyClaims);
-    }
-#endif
+    prof.flush<MODE>(A.counters, tr.prof);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- roles
@@ -1077,14 +936,14 @@ __device__ PRT_ROLE_INLINE void trace_queue(uint64_t kargs)
 // ACC: a pixel the accumulator has samples of starts from its stored generator state and colour sum instead of its seed.
 // ADAPT: work item w is the pixel of the launch's compacted list, list[w].  PROBE: work item w is probe w, and w is its pixel code.
 template <bool COUNT, bool ENV, bool ACC, bool ADAPT, bool PROBE = false>
-__device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
+__device__ __noinline__ bool shade_role(uint64_t kargs, uint32_t half)
 {
     const FrameArgs& A = frame_args(kargs);
     const BlockLds B = block_lds();
     const uint32_t poolBase = blockIdx.x * PRT_POOL_GROUPS;
     const uint32_t lane = threadIdx.x & 63u;
     half = PRT_SHADERS > 1 ? bcast0(half) : 0u; // this role's rows: half, half + PRT_SHADERS, ... (interleaved: a launch too small to fill
-                                                 // the pools gives every block its FIRST rows, and both roles must get some of them)
+                                                 // the pools gives every block its FIRST rows, and every role must get some of them)
     lds_w* const readyList = (lds_w*)&B->readyList[half * PRT_SHADER_GROUPS];
     bool did = false;
     __builtin_amdgcn_s_setprio(PRT_SHADE_PRIO);
@@ -1118,7 +977,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
         const uint32_t P = poolBase + row * PRT_CHUNK + lane;
         if (valid) {
             uint32_t pixel;
-            if constexpr (ADAPT) pixel = gld(&frame_adapt_args(kargs).list[w]);
+            if constexpr (ADAPT) pixel = gld(&frame_args<FrameAdaptArgs>(kargs).list[w]);
             else if constexpr (PROBE) pixel = w;
             else pixel = work_item_pixel(A, w);
             gst(&A.gPixel[P], pixel);
@@ -1126,7 +985,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
                 uint32_t rng = pixel != 0xffffffffu ? pixel_seed(pixel & 0xffffu, pixel >> 16, A.cam.width, A.p.seed) : 0u;
                 float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (pixel != 0xffffffffu) {
-                    const FrameAccArgs& AA = frame_acc_args(kargs);
+                    const FrameAccArgs& AA = frame_args<FrameAccArgs>(kargs);
                     const size_t pi = (size_t)(pixel & 0xffffu) + (size_t)(pixel >> 16) * A.cam.width;
                     const float4 s = gld4(&AA.accSum[pi]);
                     if (asu(s.w) != 0u) {
@@ -1179,13 +1038,7 @@ __device__ PRT_SHADE_INLINE bool shade_role(uint64_t kargs, uint32_t half)
             if (nDone) lds_sub(&B->live, nDone);
             lds_sub(&B->ready[half], taken - nAgain);
         }
-#ifdef PRT_PROFILE
-        if (lane == 0) {
-            unsigned long long* C = A.counters + (size_t)(blockIdx.x % PRT_STAT_SHARDS) * PRT_STAT_STRIDE;
-            atomicAdd(&C[30], 1ull);
-            atomicAdd(&C[31], (unsigned long long)taken);
-        }
-#endif
+        FrameProfile::shade_pass_done(A.counters, taken);
         did = true;
     }
     __builtin_amdgcn_s_setprio(0);
@@ -1202,7 +1055,7 @@ __device__ __forceinline__ void frame_body()
     const BlockLds B = block_lds();
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t i = tid; i < PRT_POOL_GROUPS; i += PRT_BLOCK) B->pending[i] = PEND_DONE;
-    for (uint32_t i = tid; i < (PRT_HOT_LDS ? PRT_HOT_NODES * 4u : 0u); i += PRT_BLOCK) {
+    for (uint32_t i = tid; i < PRT_HOT_NODES * 4u; i += PRT_BLOCK) {
         const float4 v = gld4(A.sc.hotNodes + i);
         B->hot[4 * i] = v.x;
         B->hot[4 * i + 1] = v.y;
@@ -1229,21 +1082,10 @@ __device__ __forceinline__ void frame_body()
     __syncthreads();
     uint32_t idle = 0;
     unsigned long long idleSince = 0; // s_memrealtime at the first of the current run of idle turns
-#ifdef PRT_PROFILE
-    unsigned long long tShade = 0, tTrace = 0, tIdle = 0, nShade = 0, nTrace = 0, t0 = __builtin_amdgcn_s_memtime(), tStart = t0;
-#define PROF(acc, cnt)                                            \
-    do {                                                          \
-        unsigned long long t1_ = __builtin_amdgcn_s_memtime();    \
-        acc += t1_ - t0;                                          \
-        cnt;                                                      \
-        t0 = t1_;                                                 \
-    } while (0)
-#else
-#define PROF(acc, cnt)
-#endif
+    FrameProfile prof = FrameProfile::start();
     for (;;) {
         bool did = false;
-        PROF(tIdle, (void)0);
+        prof.decided();
         // ---- decision point: this wave holds no rays
         uint32_t total = 0, best = 0, bestLen = 0;
 #pragma unroll
@@ -1251,13 +1093,9 @@ __device__ __forceinline__ void frame_body()
             const int32_t d = (int32_t)(lds_ld_acq(&B->qTail[q]) - lds_ld(&B->qHead[q]));
             const uint32_t len = d > 0 ? (uint32_t)d : 0u;
             total += len;
-#if PRT_BALANCE
             // rays queued per wave that would then be on the queue: waves spread over the queues in proportion to their lengths instead of
             // all taking the fullest one and running it dry together
-            const uint32_t score = len == 0u ? 0u : 1u + (len * PRT_BALANCE) / (lds_ld(&B->qWaves[q]) * PRT_BALANCE_W + PRT_BALANCE);
-#else
-            const uint32_t score = len;
-#endif
+            const uint32_t score = len == 0u ? 0u : 1u + len / (lds_ld(&B->qWaves[q]) * PRT_BALANCE_W + 1u);
             if (score > bestLen) {
                 bestLen = score;
                 best = (uint32_t)q;
@@ -1265,8 +1103,7 @@ __device__ __forceinline__ void frame_body()
         }
         const uint32_t ready = block_ready(B), live = lds_ld(&B->live), exhausted = lds_ld(&B->exhausted);
         const bool roomForRows = exhausted == 0u && live + PRT_CHUNK <= A.rowsPerBlock * PRT_CHUNK;
-        if (ready >= PRT_SHADE_MIN || (ready > 0u && total < 64u) || (roomForRows && total < 64u) || (roomForRows && ready + live == 0u) ||
-            (PRT_TRACE_MIN && ready >= PRT_TRACE_READY && bestLen < PRT_TRACE_MIN)) {
+        if (ready >= PRT_SHADE_MIN || (ready > 0u && total < 64u) || (roomForRows && total < 64u) || (roomForRows && ready + live == 0u)) {
             // which shade role: the one with the most ready groups -- or, with nothing ready, one that has a row to give new work to;
             // if it is taken, the next free one
             uint32_t got = 0, half = 0;
@@ -1301,19 +1138,19 @@ __device__ __forceinline__ void frame_body()
                 wg_acquire();
                 did = shade_role<COUNT, ENV, ACC, ADAPT, PROBE>(kargs, half);
                 if (lane == 0) lds_st_rel(&B->lock[half], 0u);
-                PROF(tShade, nShade++);
+                prof.shaded();
             }
         }
         if (!did && total > 0u) {
             best = bcast0(best);
-            if (PRT_BALANCE && lane == 0) lds_add(&B->qWaves[best], 1u);
+            if (lane == 0) lds_add(&B->qWaves[best], 1u);
             if (best == Q_PRIMARY) trace_queue<PRT_MODE_PACKET | (PROBE ? PRT_QUEUE_PROBE : 0), COUNT>(kargs);
             else if (best == Q_SCATTER) trace_queue<PRT_MODE_SINGLE, COUNT>(kargs);
             else if (best == Q_OCC_PACKET) trace_queue<PRT_MODE_OCC_PACKET, COUNT>(kargs);
             else trace_queue<PRT_MODE_OCC_SINGLE, COUNT>(kargs);
-            if (PRT_BALANCE && lane == 0) lds_sub(&B->qWaves[best], 1u);
+            if (lane == 0) lds_sub(&B->qWaves[best], 1u);
             did = true;
-            PROF(tTrace, nTrace++);
+            prof.traced();
         }
         if (did) {
             idle = 0;
@@ -1355,34 +1192,23 @@ __device__ __forceinline__ void frame_body()
         }
     }
     // ---- statistics: the last wave to leave adds the block's sums to one of PRT_STAT_SHARDS copies of the counters
-    unsigned long long* C = A.counters + (size_t)(blockIdx.x % PRT_STAT_SHARDS) * PRT_STAT_STRIDE;
-#ifdef PRT_PROFILE
-    PROF(tIdle, (void)0);
-    if (lane == 0) {
-        atomicAdd(&C[8], tShade);
-        atomicAdd(&C[9], tTrace);
-        atomicAdd(&C[10], tIdle);
-        atomicAdd(&C[11], nShade);
-        atomicAdd(&C[12], nTrace);
-        atomicAdd(&C[13], t0 - tStart);
-        atomicAdd(&C[14], 1ull);
-    }
-#endif
+    unsigned long long* C = prt_stat_copy(A.counters);
+    prof.flush(C);
     if (lane == 0 && lds_add(&B->exited, 1u) == PRT_BLOCK / 64u - 1u) {
         wg_acquire();
         const uint32_t r = lds_ld(&B->rays), o = lds_ld(&B->occl), px = lds_ld(&B->px);
-        if (r) atomicAdd(&C[0], (unsigned long long)r);
-        if (o) atomicAdd(&C[1], (unsigned long long)o);
-        if (px) atomicAdd(&C[6], (unsigned long long)px);
+        if (r) atomicAdd(&C[PRT_STAT_RAYS], (unsigned long long)r);
+        if (o) atomicAdd(&C[PRT_STAT_OCCL], (unsigned long long)o);
+        if (px) atomicAdd(&C[PRT_STAT_PIXELS], (unsigned long long)px);
         if (const uint32_t sk = lds_ld(&B->occlSkipped)) atomicAdd(&C[PRT_STAT_OCCL_SKIPPED], (unsigned long long)sk);
         if (COUNT) {
-            if (B->nBox) atomicAdd(&C[2], (unsigned long long)B->nBox);
-            if (B->nTri) atomicAdd(&C[3], (unsigned long long)B->nTri);
-            if (B->nHit) atomicAdd(&C[4], (unsigned long long)B->nHit);
-            if (B->nTap) atomicAdd(&C[5], (unsigned long long)B->nTap);
+            if (B->nBox) atomicAdd(&C[PRT_STAT_BOX], (unsigned long long)B->nBox);
+            if (B->nTri) atomicAdd(&C[PRT_STAT_TRI], (unsigned long long)B->nTri);
+            if (B->nHit) atomicAdd(&C[PRT_STAT_HIT], (unsigned long long)B->nHit);
+            if (B->nTap) atomicAdd(&C[PRT_STAT_TAP], (unsigned long long)B->nTap);
         }
         if (lds_ld(&B->overflow)) {
-            atomicAdd(&C[7], 1ull);
+            atomicAdd(&C[PRT_STAT_STACK_OVERFLOW], 1ull);
             atomicOr(&A.ctrl[PRT_WORK_WORDS], 2u); // sticky: survives the next render's clearing of the counters
         }
     }

@@ -17,13 +17,6 @@
 #define PRT_WORK_WORDS 512 // control words of a launch (frame kernel: prt_frame.h PRT_CTRL_CURSORS; claim cursor of the G-buffer kernel)
 #define PRT_STICKY_WORDS 160 // behind the control words and NEVER cleared by a render: [0] error flags of any earlier launch (1 watchdog, 2 stack
                              // overflow), [2] + [8..135] the first watchdog reports; read and cleared by prt_hip_get_stats, read by download / gather
-#define PRT_STAT_SHARDS 64 // copies of the statistics counters, summed on read-back
-#ifdef PRT_PROFILE
-#define PRT_STAT_STRIDE 128 // the profile build appends its lane-utilisation counters (words 32..127)
-#else
-#define PRT_STAT_STRIDE 32 // 64-bit words per copy (256 B apart)
-#endif
-#define PRT_STAT_OCCL_SKIPPED 15 // word of a copy: occlusion rays the frame kernel answered without a walk (prt_frame.h; read by the test build only)
 #define PRT_TIMING_RING 32
 
 // thread-local message behind prt_hip_last_error(); returns `code`

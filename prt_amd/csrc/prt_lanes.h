@@ -107,21 +107,13 @@ enum { PH_START = 0, PH_WAIT_PRIMARY = 1, PH_WAIT_BOUNCE = 2, PH_DONE = 3 };
 typedef float f4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 nt_load4(const float4* p)
 {
-#ifdef PRT_STATE_PLAIN
-    return gld4(p);
-#else
     f4_t v = __builtin_nontemporal_load((const PRT_AS1 f4_t*)p);
     return make_float4(v.x, v.y, v.z, v.w);
-#endif
 }
 __device__ __forceinline__ void nt_store4(float4* p, float4 v)
 {
-#ifdef PRT_STATE_PLAIN
-    gst4(p, v);
-#else
     f4_t w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, (PRT_AS1 f4_t*)p);
-#endif
 }
 __device__ __forceinline__ uint32_t nt_load(const uint32_t* p) { return __builtin_nontemporal_load((const PRT_AS1 uint32_t*)p); }
 __device__ __forceinline__ void nt_store(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, (PRT_AS1 uint32_t*)p); }

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(PRT_BLOCK) void query_nearest_kernel(QueryArgs A)
 {
     QuerySrc<SURFACE> src{&A};
     trace_batch<PRT_MODE_SINGLE>(A.sc, src, A.ctl);
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&A.ctl.counters[0], (unsigned long long)A.n); // raysTraced
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&A.ctl.counters[PRT_STAT_RAYS], (unsigned long long)A.n);
 }
 
 __global__ __launch_bounds__(PRT_BLOCK) void query_any_kernel(QueryArgs A)
@@ -115,8 +115,8 @@ __global__ __launch_bounds__(PRT_BLOCK) void query_any_kernel(QueryArgs A)
     QuerySrc<false> src{&A};
     trace_batch<PRT_MODE_OCC_SINGLE>(A.sc, src, A.ctl);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd(&A.ctl.counters[0], (unsigned long long)A.n); // raysTraced
-        atomicAdd(&A.ctl.counters[1], (unsigned long long)A.n); // occludedTraced
+        atomicAdd(&A.ctl.counters[PRT_STAT_RAYS], (unsigned long long)A.n);
+        atomicAdd(&A.ctl.counters[PRT_STAT_OCCL], (unsigned long long)A.n);
     }
 }
 

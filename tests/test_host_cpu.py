@@ -86,6 +86,16 @@ def test_step_loop_has_no_scratch_access():
     assert 2 * res["LDS Size"] <= 160 * 1024, res
 
 
+def test_profile_build_compiles():
+    """No product or test build compiles the -DPRT_PROFILE side of prt_stats.h (the real hooks of the trace loops and the host report
+    of tools/role_profile.py): this syntax check of the two sources that use it, host and device pass, is its only guard against rot."""
+    from prt_amd import _build as B
+    flags = [f for f in B.FLAGS if f not in ("-shared", "-fPIC", "-pthread", "-ldl")]
+    cmd = [B.hipcc()] + flags + ['-DPRT_SOURCE_SHA16="0"', "-DPRT_PROFILE", "-fsyntax-only"] + [os.path.join(B.CSRC, s) for s in ("prt_kernels.hip", "prt_context.hip")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "error:" not in out.stderr, out.stderr[-4000:]
+
+
 def test_library_carries_the_hash_of_its_sources(L):
     """prt_amd.build() rebuilds when any kernel source or header is newer than the library (the header list is a glob of csrc/),
     and the library is stamped with the hash of what it was built from: bench.py and the counter summaries quote that stamp."""
