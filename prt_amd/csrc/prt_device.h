@@ -315,6 +315,18 @@ __device__ __forceinline__ float slab_entry_select(const Box& b, const DevRay& r
 }
 
 // ---------------------------------------------------------------------------- triangle
+// triangle.cpp:118-131: shear of the three (axis-permuted) vertex differences and the edge functions, shared by both forms of the test
+__device__ __forceinline__ void tri_edges(const DevRay& r, Vec3 v0, Vec3 v1, Vec3 v2, float& e0, float& e1, float& e2)
+{
+    const float idx = r.shearX, idy = r.shearY; // invDzD = inv_dz*d, :119
+    float v0x = v0.x - idx * v0.z, v0y = v0.y - idy * v0.z;
+    float v1x = v1.x - idx * v1.z, v1y = v1.y - idy * v1.z;
+    float v2x = v2.x - idx * v2.z, v2y = v2.y - idy * v2.z;
+    e0 = v1x * v2y - v1y * v2x;
+    e1 = v2x * v0y - v2y * v0x;
+    e2 = v0x * v1y - v0y * v1x;
+}
+
 // triangle.cpp:90-166, one lane.  Returns t, or -1 (kNoIntersection).
 __device__ __forceinline__ float tri_intersect(const DevRay& r, Vec3 p0, Vec3 p1, Vec3 p2, float& bi, float& bj, float& bk)
 {
@@ -332,13 +344,9 @@ __device__ __forceinline__ float tri_intersect(const DevRay& r, Vec3 p0, Vec3 p1
         t = v2.y; v2.y = v2.z; v2.z = t;
     }
     float v0z = v0.z, v1z = v1.z, v2z = v2.z;
-    const float inv_dz = r.invDz, idx = r.shearX, idy = r.shearY; // invDzD = inv_dz*d, :119
-    float v0x = v0.x - idx * v0z, v0y = v0.y - idy * v0z;
-    float v1x = v1.x - idx * v1z, v1y = v1.y - idy * v1z;
-    float v2x = v2.x - idx * v2z, v2y = v2.y - idy * v2z;
-    float e0 = v1x * v2y - v1y * v2x;
-    float e1 = v2x * v0y - v2y * v0x;
-    float e2 = v0x * v1y - v0y * v1x;
+    const float inv_dz = r.invDz;
+    float e0, e1, e2;
+    tri_edges(r, v0, v1, v2, e0, e1, e2);
     bool mask_eb = (e0 < 0.0f || e1 < 0.0f || e2 < 0.0f) && (e0 > 0.0f || e1 > 0.0f || e2 > 0.0f);
     bi = bj = bk = 0.0f;
     if (mask_eb) return -1.0f;
@@ -352,6 +360,32 @@ __device__ __forceinline__ float tri_intersect(const DevRay& r, Vec3 p0, Vec3 p1
     bj = e1 * inv_det;
     bk = e2 * inv_det;
     return mask ? t : -1.0f;
+}
+
+// The same test for a pair lane of the cooperative leaf round (tracer_leaf_coop), as straight-line code: the two axis swaps are
+// selects on the nine differences (x <- swapXZ ? z : x, the z after the first swap zt <- swapXZ ? x : z, then y <- swapYZ ? zt : y,
+// z <- swapYZ ? y : zt: the composition of triangle.cpp:96-116 whatever the two flags), and the division runs in every lane, its
+// result selected afterwards.  Every floating-point operation and operand is tri_intersect's; the barycentrics are those of
+// tri_intersect only where the returned t is not -1, which is the only place the round reads them.
+__device__ __forceinline__ float tri_intersect_pair(const DevRay& r, Vec3 p0, Vec3 p1, Vec3 p2, float& bi, float& bj, float& bk)
+{
+    const Vec3 d0 = sub3(p0, r.org), d1 = sub3(p1, r.org), d2 = sub3(p2, r.org);
+    const bool sxz = r.swapXZ, syz = r.swapYZ;
+    const float z0 = sxz ? d0.x : d0.z, z1 = sxz ? d1.x : d1.z, z2 = sxz ? d2.x : d2.z;
+    const Vec3 v0 = mk3(sxz ? d0.z : d0.x, syz ? z0 : d0.y, syz ? d0.y : z0);
+    const Vec3 v1 = mk3(sxz ? d1.z : d1.x, syz ? z1 : d1.y, syz ? d1.y : z1);
+    const Vec3 v2 = mk3(sxz ? d2.z : d2.x, syz ? z2 : d2.y, syz ? d2.y : z2);
+    float e0, e1, e2;
+    tri_edges(r, v0, v1, v2, e0, e1, e2);
+    const bool neg = (e0 < 0.0f) | (e1 < 0.0f) | (e2 < 0.0f), pos = (e0 > 0.0f) | (e1 > 0.0f) | (e2 > 0.0f);
+    const float det = e0 + e1 + e2;
+    const float inv_det = 1.0f / det;
+    const float t = ((e0 * v0.z + e1 * v1.z + e2 * v2.z) * r.invDz) * inv_det;
+    bi = e0 * inv_det;
+    bj = e1 * inv_det;
+    bk = e2 * inv_det;
+    const bool ok = !(neg & pos) & ((det < 0.0f) | (det > 0.0f)) & (t > 0.0001f);
+    return ok ? t : -1.0f;
 }
 
 // ---------------------------------------------------------------------------- textures (texture.cpp:31-183)
@@ -901,7 +935,11 @@ __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-#define PRT_COOP_STRIDE 72u // words of LDS per wave: 64 table words + a dump word (lanes that write nothing this round)
+// The wave's mask of a predicate.  __ballot() goes through an integer compare: for a predicate that already is a lane mask (an AND of
+// compares) the compiler first turns it into 0 / 1 per lane (v_cndmask) and compares that again; the builtin takes the mask as it is.
+__device__ __forceinline__ unsigned long long wave_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
+#define PRT_COOP_STRIDE 72u // words of LDS per wave: the 64 table words (the eight behind them were the dump word's and stay unused)
 #define PRT_COOP_TRI_MASK ((1u << PRT_COOP_TRI_BITS) - 1u)
 __device__ __forceinline__ float bperm(int byteAddr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(byteAddr, __float_as_int(v))); }
 __device__ __forceinline__ uint32_t bperm(int byteAddr, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute(byteAddr, (int)v); }
@@ -917,19 +955,40 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     const unsigned long long b0 = __ballot((n & 1u) != 0u), b1 = __ballot((n & 2u) != 0u), b2 = __ballot((n & 4u) != 0u), b3 = __ballot((n & 8u) != 0u);
     const uint32_t prefix = mbcnt64(b0) + 2u * mbcnt64(b1) + 4u * mbcnt64(b2) + 8u * mbcnt64(b3);
     const bool take = onLeaf && prefix + n <= 64u; // the prefix sum is monotone: the takers' pairs are 0 .. pairs-1
-    const unsigned long long takeMask = __ballot(take);
+    const unsigned long long takeMask = wave_mask(prefix + n <= 64u) & (b0 | b1 | b2 | b3); // (n != 0: the lane stands on a leaf)
     const uint32_t last = 63u - (uint32_t)__builtin_clzll(takeMask); // (the first leaf lane always takes: n <= 8)
     const uint32_t pairs = (uint32_t)__builtin_amdgcn_readlane((int)(prefix + n), (int)last);
     tr.prof.leaf_pairs(pairs);
-    // ---- table: pair p -> (first triangle - prefix) | owner lane << 26, the same word for every pair of a leaf, so that the
-    // eight stores need no predicate: store i goes to entry min(i, n - 1), lanes that take no part store to the dump word
+    // ---- table: pair p -> (first triangle - prefix) | owner lane << 26, the same word for every pair of a leaf.  Word i of a leaf goes
+    // to entry prefix + i (one base address, immediate offsets) under the mask "takes and n > i".  Those masks are functions of the
+    // four ballots -- n >= 2 is b1|b2|b3, n >= 5 is (b2 & (b0|b1)) | b3, n = 8 is b3 -- and they nest, so each store narrows the
+    // exec mask of the one before it with scalar instructions only; lanes that take no part are masked off from the first store on
+    // (n <= 8 and prefix + n <= 64 for a taker: every store lands inside the wave's 64 words).
     {
         const uint32_t word = (((T.ref >> 4) - prefix) & PRT_COOP_TRI_MASK) | (lane << PRT_COOP_TRI_BITS);
-        lds_u32* q = st.coop + (take ? prefix : 64u);
-        const uint32_t nm1 = take ? n - 1u : 0u;
-        q[0] = word;
-#pragma unroll
-        for (uint32_t i = 1; i < 8u; i++) q[i < nm1 ? i : nm1] = word;
+        lds_u32* q = st.coop + prefix;
+        if (__builtin_amdgcn_inverse_ballot_w64(takeMask)) {
+            q[0] = word;
+            if (__builtin_amdgcn_inverse_ballot_w64(b1 | b2 | b3)) {
+                q[1] = word;
+                if (__builtin_amdgcn_inverse_ballot_w64((b0 & b1) | b2 | b3)) {
+                    q[2] = word;
+                    if (__builtin_amdgcn_inverse_ballot_w64(b2 | b3)) {
+                        q[3] = word;
+                        if (__builtin_amdgcn_inverse_ballot_w64((b2 & (b0 | b1)) | b3)) {
+                            q[4] = word;
+                            if (__builtin_amdgcn_inverse_ballot_w64((b2 & b1) | b3)) {
+                                q[5] = word;
+                                if (__builtin_amdgcn_inverse_ballot_w64((b2 & b1 & b0) | b3)) {
+                                    q[6] = word;
+                                    if (__builtin_amdgcn_inverse_ballot_w64(b3)) q[7] = word;
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // (no instruction: LDS operations of one wave complete in order)
     const bool pair = lane < pairs;
@@ -937,7 +996,9 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     // the entry a taker pops when its leaf is done is already known: read it beside the table, not after the round
     const int popAt = T.sp > 0 ? T.sp - 1 : 0;
     uint32_t popped = st.ldsRef[(popAt < STK::kLds ? popAt : 0) * PRT_BLOCK];
-    const int oaddr = (int)((pair ? (word >> PRT_COOP_TRI_BITS) : lane) << 2);
+    // ds_bpermute takes the source lane from bits 7:2 of its address operand: word >> 24 carries the owner lane there.  A lane that is
+    // no pair reads the ray constants of whatever lane its stale table word names -- defined values (Tracer T{}) that nothing uses
+    const int oaddr = (int)(word >> (PRT_COOP_TRI_BITS - 2));
     const uint32_t tri = (word + lane) & PRT_COOP_TRI_MASK;
     __builtin_amdgcn_sched_barrier(0); // (addresses first: a register of the fetch must not be reused for them while it is in flight)
     prt_f3 a, b, c;
@@ -954,24 +1015,29 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
     r.shearX = bperm(oaddr, T.r.shearX);
     r.shearY = bperm(oaddr, T.r.shearY);
     r.invDz = bperm(oaddr, T.r.invDz);
-    const uint32_t flags = bperm(oaddr, (T.r.swapXZ ? 1u : 0u) | (T.r.swapYZ ? 2u : 0u) | ((T.ref & PRT_LEAF_ALPHA) ? 4u : 0u));
+    // one word for the two swap flags (at most one is set: prepare_single, prepare_soa) and the leaf's alpha bit, laid out so that the
+    // pair lane gets each swap flag from ONE signed compare: -4 x<->z, 4 y<->z, 0 none, bit 0 = alpha-tested leaf
+    const int32_t axes = T.r.swapXZ ? -4 : (T.r.swapYZ ? 4 : 0);
+    const int32_t flags = (int32_t)bperm(oaddr, (uint32_t)(axes | (int32_t)((T.ref / PRT_LEAF_ALPHA) & 1u)));
     const float limit = bperm(oaddr, OCC ? T.maxT : T.hit.t);
     __builtin_amdgcn_sched_barrier(0);
-    r.swapXZ = (flags & 1u) != 0u;
-    r.swapYZ = (flags & 2u) != 0u;
-    float t = -1.0f, bi = 0.0f, bj = 0.0f, bk = 0.0f;
-    uint32_t primId = 0u;
+    r.swapXZ = flags < 0;
+    r.swapYZ = flags > 1;
+    const bool leafAlpha = (flags & 1) != 0;
+    // t and the barycentrics of a lane that is no pair are whatever its registers hold: a defined value (the empty asm is its
+    // definition) that costs no instruction.  No owner ever asks for them: `cand` is false there, and only accepted pairs are read
+    float t, bi, bj, bk;
+    asm volatile("" : "=v"(t), "=v"(bi), "=v"(bj), "=v"(bk));
     bool cand = false;
     if (pair) {
-        t = tri_intersect(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), bi, bj, bk);
-        primId = tri; // the LEAF-ORDER index (tri_candidate)
+        t = tri_intersect_pair(r, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), bi, bj, bk);
         cand = t >= 0.0001f && t < limit;
         tr.prof.alpha_begin();
         // The alpha test of a candidate (bvh.cpp:336-338, 407-409) is a chain of dependent fetches that one or two lanes of the round walk
         // while the others wait (profile build: a quarter of C3's leaf rounds, a whole round's time each): the record carries its
         // texture's descriptor, and most tests end at the class of the tap's cell -- one word of a map that stays in the L2 -- instead
         // of four texel fetches.
-        const uint32_t alphaRef = (cand && (flags & 4u)) ? gld(sc.triAlpha + tri) : 0u;
+        const uint32_t alphaRef = (cand && leafAlpha) ? gld(sc.triAlpha + tri) : 0u;
         if (alphaRef) {
             const float4* ap = sc.alpha + 3 * (size_t)(alphaRef - 1);
             const float4 u0 = gld4(ap), u1 = gld4(ap + 1), u2 = gld4(ap + 2);
@@ -979,67 +1045,59 @@ __device__ __forceinline__ void tracer_leaf_coop(const DevScene& sc, Tracer& T, 
             const uint4 d = make_uint4(asu(u2.x), asu(u2.y), asu(u2.z), asu(u2.w));
             cand = alpha_decide<PACKET>(sc, d, u1.w, uv, tr);
         }
-        tr.prof.alpha_end(cand, (flags & 4u) != 0u);
+        tr.prof.alpha_end(cand, leafAlpha);
     }
-    const unsigned long long acc = __ballot(cand);
-    // ---- owners
+    const unsigned long long acc = wave_mask(cand);
+    // ---- owners.  Every update below is a select on the lane's own predicate, not an assignment inside a divergent branch (which
+    // the compiler lowers to register copies around the branch).  A lane that does not take has seg = 0 and keeps what it has.
     uint32_t seg = take ? ((uint32_t)(acc >> prefix) & ((1u << n) - 1u)) : 0u;
+    // the entry a taker pops: beyond the LDS part of the stack (rare) it comes from the spill area
+    if (MODE != PRT_MODE_PACKET && take && popAt >= STK::kLds) popped = gld(st.deep(popAt, 0));
     if (OCC) {
-        if (take) {
-            if (seg) {
-                T.occ = true;
-                T.ref = PRT_REF_NONE;
-                T.sp = 0;
-                T.m = sc.bvhCount; // finished
-            } else {
-                if (T.sp == 0) T.ref = PRT_REF_NONE;
-                else {
-                    if (popAt >= STK::kLds) popped = st.get(popAt);
-                    T.sp = popAt;
-                    T.ref = popped;
-                }
-            }
-        }
+        const bool hitAny = seg != 0u; // any accepted pair of the leaf: occluded, finished
+        T.occ = T.occ || hitAny;
+        T.ref = take ? ((hitAny || T.sp == 0) ? PRT_REF_NONE : popped) : T.ref;
+        T.sp = take ? (hitAny ? 0 : popAt) : T.sp; // (popAt is 0 for an empty stack)
+        T.m = hitAny ? sc.bvhCount : T.m;
     } else {
-        if (acc != 0ull) {
-            // the owners walk their accepted pairs in ascending order: only t travels per turn, the winner's barycentrics and index
-            // once at the end
-            uint32_t win = 0xffffffffu;
-            for (;;) {
-                tr.prof.leaf_update();
-                const bool more = seg != 0u;
-                if (!__any(more)) break;
-                const uint32_t src = more ? prefix + (uint32_t)__builtin_ctz(seg) : lane;
-                const float t2 = bperm((int)(src << 2), t);
-                if (more) {
-                    if (t2 < T.hit.t) {
-                        T.hit.t = t2;
-                        win = src;
-                    }
-                    seg &= seg - 1u;
-                }
-            }
-            if (__any(win != 0xffffffffu)) {
-                const int waddr = (int)((win != 0xffffffffu ? win : lane) << 2);
-                const float i2 = bperm(waddr, bi), j2 = bperm(waddr, bj), k2 = bperm(waddr, bk);
-                const uint32_t p2 = bperm(waddr, primId);
-                if (win != 0xffffffffu) {
-                    T.hit.i = i2;
-                    T.hit.j = j2;
-                    T.hit.k = k2;
-                    T.hit.primId = p2;
-                    T.hit.meshId = T.m;
-                }
-            }
+        // the owners walk their accepted pairs in ascending order: only t travels per turn, the winner's barycentrics once at the
+        // end.  (A lane with nothing left asks ds_bpermute for some lane's t -- any address names one -- and ignores it.)
+        const uint32_t first = leaf_first(T.ref) - prefix; // pair p of this leaf is triangle first + p
+        uint32_t win = 0xffffffffu;
+        for (;;) {
+            tr.prof.leaf_update();
+            const bool more = seg != 0u;
+            if (wave_mask(more) == 0ull) break;
+            uint32_t low; // v_ffbl_b32: the lowest set bit, -1 for 0 (for which __builtin_ctz is undefined and __ffs adds a select)
+            asm("v_ffbl_b32 %0, %1" : "=v"(low) : "v"(seg));
+            const uint32_t src = prefix + low;
+            const float t2 = bperm((int)(src << 2), t);
+            const bool upd = more && t2 < T.hit.t;
+            T.hit.t = upd ? t2 : T.hit.t;
+            win = upd ? src : win;
+            seg &= seg - 1u; // (0 stays 0)
         }
-        if (take) {
-            if (MODE == PRT_MODE_PACKET) T.ref = tracer_pop<MODE, false>(T, st, tr); // (its pop tests the entry distance against the new hit.t)
-            else if (T.sp == 0) T.ref = PRT_REF_NONE;
-            else {
-                if (popAt >= STK::kLds) popped = st.get(popAt);
-                T.sp = popAt;
-                T.ref = popped;
-            }
+        // only the exchange sits behind the (wave-uniform) "any winner" branch; the selects follow it, so that the hit's old values
+        // need no copies on the way around the branch
+        const bool won = win != 0xffffffffu;
+        float i2, j2, k2;
+        asm volatile("" : "=v"(i2), "=v"(j2), "=v"(k2));
+        if (wave_mask(won) != 0ull) {
+            const int waddr = (int)(win << 2);
+            i2 = bperm(waddr, bi);
+            j2 = bperm(waddr, bj);
+            k2 = bperm(waddr, bk);
+        }
+        T.hit.i = won ? i2 : T.hit.i;
+        T.hit.j = won ? j2 : T.hit.j;
+        T.hit.k = won ? k2 : T.hit.k;
+        T.hit.primId = won ? first + win : T.hit.primId; // the LEAF-ORDER index (tri_candidate), which is the pair lane's `tri`
+        T.hit.meshId = won ? T.m : T.hit.meshId;
+        if (MODE == PRT_MODE_PACKET) {
+            if (take) T.ref = tracer_pop<MODE, false>(T, st, tr); // (its pop tests the entry distance against the new hit.t)
+        } else {
+            T.ref = take ? (T.sp == 0 ? PRT_REF_NONE : popped) : T.ref;
+            T.sp = take ? popAt : T.sp; // (popAt is 0 for an empty stack)
         }
     }
 }
@@ -1058,14 +1116,21 @@ __device__ __forceinline__ constexpr uint32_t idle_break(int mode)
 template <int MODE, bool COUNT, class STK>
 __device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, bool active, const STK& st, Traffic& tr, uint32_t& overflow)
 {
+    // The lanes' kinds as wave masks, from one compare each per round (the leaf bit, and "has nothing" at the end of the round, which
+    // is also the next round's); the per-lane predicates are those masks read back, not compares of their own.
+    const unsigned long long act = wave_mask(active);
+    unsigned long long idle = act & wave_mask(T.ref == PRT_REF_NONE);
     for (;;) {
-        const bool onNode = active && ref_is_internal(T.ref);
-        const bool onLeaf = active && ref_is_leaf(T.ref);
-        const uint32_t nNode = (uint32_t)__popcll(__ballot(onNode)), nLeaf = (uint32_t)__popcll(__ballot(onLeaf));
+        const unsigned long long leafBit = wave_mask((T.ref & PRT_REF_LEAF) != 0u);
+        const unsigned long long nodeMask = act & ~leafBit, leafMask = act & leafBit & ~idle; // ref_is_internal / ref_is_leaf
+        const bool onNode = __builtin_amdgcn_inverse_ballot_w64(nodeMask);
+        const bool onLeaf = __builtin_amdgcn_inverse_ballot_w64(leafMask);
+        const uint32_t nNode = (uint32_t)__popcll(nodeMask), nLeaf = (uint32_t)__popcll(leafMask);
         if (nNode + nLeaf == 0u) break;
         // Which kind steps.  Serial leaf steps (counting build): the larger group.  Cooperative leaf rounds: a leaf lane stands for
         // about six pair lanes, so leaves wait until a round's worth of pairs has gathered or few lanes are left on nodes.
-        const bool doNode = !COUNT ? (nLeaf == 0u || (nLeaf < PRT_COOP_MIN && nLeaf * PRT_COOP_WEIGHT < nNode)) : nNode >= nLeaf;
+        // (one scalar expression, `|` and `&`: a short-circuit form becomes a second branch into the node round)
+        const bool doNode = !COUNT ? ((nLeaf == 0u) | ((nLeaf < PRT_COOP_MIN) & (nLeaf * PRT_COOP_WEIGHT < nNode))) : nNode >= nLeaf;
 #ifdef PRT_PAD_VALU
         { // sensitivity probe of tools/build_variants.py: PRT_PAD_VALU extra vector instructions per round (never in the product)
             float pad = T.maxT;
@@ -1084,7 +1149,8 @@ __device__ __forceinline__ void trace_step_phase(const DevScene& sc, Tracer& T, 
         } else {
             if (onLeaf) tracer_tri<MODE, COUNT>(sc, T, st, tr);
         }
-        const uint32_t done = (uint32_t)__popcll(__ballot(active && T.ref == PRT_REF_NONE));
+        idle = act & wave_mask(T.ref == PRT_REF_NONE);
+        const uint32_t done = (uint32_t)__popcll(idle);
         if (done >= idle_break(MODE)) break;
     }
 }
