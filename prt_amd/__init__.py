@@ -23,6 +23,9 @@ class PrtError(RuntimeError):
     pass
 
 
+from ._hiprt import DeviceArrays, runtime as hip_runtime  # noqa: E402  (after PrtError, which _hiprt raises)
+
+
 # ----------------------------------------------------------------------------- C structs (include/prt_hip.h)
 class Material(C.Structure):
     _fields_ = [("diffuse", C.c_float * 3), ("emissive", C.c_float * 3), ("reflectionType", C.c_uint32),
@@ -1342,7 +1345,7 @@ class PathTracer:
         division by passes * K is made here.  Sets last_stats (the last pass's).  Needs a scene and no camera."""
         p = self._probe_params(spp, seed, exposure, max_depth)
         n = lens.width * lens.height * 3
-        with _DeviceArrays(self._device) as dev:
+        with DeviceArrays(self._device) as dev:
             d_image = dev.alloc(n * 4)
             for i in range(passes):
                 one = lens.copy(pass_=lens.pass_ + i, flags=(lens.flags | LENS_ACCUMULATE) if i else (lens.flags & ~LENS_ACCUMULATE))
@@ -1425,7 +1428,7 @@ class PathTracer:
         K, Cc = table.K, table.C
         p = self._probe_params(spp, seed, exposure, max_depth)
         image, mask = np.zeros((H, W, Cc, 3), dtype=np.float32), np.zeros((H, W), dtype=np.uint8)
-        with _DeviceArrays(self._device) as dev:
+        with DeviceArrays(self._device) as dev:
             d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
             d_texels, d_hits = dev.alloc(4 * W * H), dev.alloc(HIT_DTYPE.itemsize * W * H)
             counts = self.atlas_rasterize_device(W, H, d_uv, {m: len(uv) for m, uv in uvs.items()}, d_texels, d_hits)
@@ -1734,45 +1737,6 @@ def _atlas_uvs(uvs_per_mesh):
     if not uvs:
         raise PrtError("atlas: no mesh has lightmap UVs")
     return uvs
-
-
-class _DeviceArrays:
-    """Device memory of one lightmap() call, from the HIP runtime the library is linked to; freed on exit.  The copies run on the
-    null stream, which the context's (blocking) stream is ordered with."""
-
-    def __init__(self, device):
-        h = C.CDLL("libamdhip64.so")
-        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        h.hipFree.argtypes = [C.c_void_p]
-        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self._h, self._held, self._device = h, [], device
-
-    def __enter__(self):
-        if self._h.hipSetDevice(self._device) != 0:
-            raise PrtError(f"lightmap: hipSetDevice({self._device}) failed")
-        return self
-
-    def __exit__(self, *exc):
-        for p in self._held:
-            self._h.hipFree(p)
-        self._held = []
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        if self._h.hipMalloc(C.byref(p), max(int(nbytes), 64)) != 0:
-            raise PrtError(f"lightmap: hipMalloc of {nbytes} bytes failed")
-        self._held.append(p)
-        return p.value
-
-    def upload(self, a):
-        p = self.alloc(a.nbytes)
-        if self._h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) != 0:
-            raise PrtError("lightmap: hipMemcpy to the device failed")
-        return p
-
-    def download(self, a, p):
-        if self._h.hipMemcpy(a.ctypes.data, p, a.nbytes, 2) != 0:
-            raise PrtError("lightmap: hipMemcpy from the device failed")
 
 
 def bake_cosine_set(K, rng):

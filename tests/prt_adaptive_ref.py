@@ -6,16 +6,14 @@ import itertools
 
 import numpy as np
 
+from prt_testlib import bits  # noqa: F401  (re-exported: the tests of this restatement call it as R.bits)
+
 F32, U32 = np.float32, np.uint32
 FLOOR = 0.01
 EXPOSURES = (1.0, 2.5)  # the exposures the error is checked at; the selection runs at SELECT_EXPOSURE over a fill of FILL_EXPOSURE
 SELECT_EXPOSURE, FILL_EXPOSURE = 2.5, 0.5
 DENORMAL = 1e-40
 TOP = 1 << 24
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F32).view(U32)
 
 
 # ---- comparison

@@ -116,3 +116,7 @@ def denoise(total, count, mom, albedo, normal, iterations=5, normal_power_log2=5
             V = np.where(valid & known, sum_v / (sum_w * sum_w), F(-1)).astype(F)
         image = np.where(valid[..., None], F(exposure) * (C * d), F(0)).astype(F)
     return image, V
+
+
+# the parameters the tests run the filter with unless they say otherwise
+DEFAULTS = dict(iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True)

@@ -143,3 +143,30 @@ def hostile_image():
         img[0, k] = px
     img.setflags(write=False)
     return img
+
+
+# ----------------------------------------------------------------------------- shared by the CPU and the GPU tests
+def assert_state_equal(got, want, what=""):
+    """got: a DisplayState (or its as_dict()); want: the restatement's dict.  Floats are compared as words."""
+    g = got.as_dict() if hasattr(got, "as_dict") else got
+    for k in ("gain", "octaves", "target"):
+        assert F(g[k]).view(np.uint32) == F(want[k]).view(np.uint32), (what, k, g[k], want[k])
+    for k in ("valid", "metered", "ignored"):
+        assert int(g[k]) == int(want[k]), (what, k, g[k], want[k])
+    assert np.array_equal(g["hist"], want["hist"]), (what, "hist")
+
+
+def frame(level, seed, shape=(24, 40)):
+    rng = np.random.default_rng(seed)
+    return (rng.random(shape + (3,)) * level * 10.0 ** rng.uniform(-2, 2, shape + (1,))).astype(F)
+
+
+BAD_FIELDS = [("tonemap", dict(tonemap=2)), ("transfer", dict(transfer=2)), ("format", dict(format=3)), ("meter", dict(meter=2)),
+              ("gain", dict(gain=-1.0)), ("gain", dict(gain=float("nan"))), ("gain", dict(gain=float("inf"))),
+              ("key", dict(meter=1, key=0.0)), ("key", dict(meter=1, key=float("nan"))), ("key", dict(meter=1, key=float("inf"))),
+              ("lowPermille", dict(meter=1, low_permille=1000, high_permille=1000)),
+              ("highPermille", dict(meter=1, low_permille=500, high_permille=500)), ("highPermille", dict(meter=1, low_permille=600, high_permille=500)),
+              ("highPermille", dict(meter=1, high_permille=1001)),
+              ("minGain", dict(meter=1, min_gain=0.0)), ("minGain", dict(meter=1, min_gain=float("nan"))),
+              ("maxGain", dict(meter=1, min_gain=2.0, max_gain=1.0)), ("maxGain", dict(meter=1, max_gain=float("inf"))),
+              ("adaptRate", dict(meter=1, adapt_rate=0.0)), ("adaptRate", dict(meter=1, adapt_rate=1.5)), ("adaptRate", dict(meter=1, adapt_rate=float("nan")))]

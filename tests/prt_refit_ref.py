@@ -4,6 +4,9 @@
 in f32, on a node array in the reference's depth-first order (first child = i + 1, second child = primOrSecondNodeIndex > i)."""
 import numpy as np
 
+import prt_amd
+import prt_testlib as T
+
 
 def refit_nodes(nodes, remap, indices, positions):
     """nodes (NODE_DTYPE) with the same topology and boxes refitted to `positions` ((V, 3) float32); nothing else changes."""
@@ -22,3 +25,30 @@ def refit_nodes(nodes, remap, indices, positions):
             out["lower"][i] = pts.min(axis=0)
             out["upper"][i] = pts.max(axis=0)
     return out
+
+
+# the rigid moves of the teapot for which a REBUILD gives the refit's tree (tests/test_refit_cpu.py checks it; the GPU suite relies on it)
+RIGID_MOVES = {
+    "scale2": lambda P: (np.float32(2.0) * P).astype(np.float32),
+    "scale0.5": lambda P: (np.float32(0.5) * P).astype(np.float32),
+    "shift0.25x": lambda P: (P + np.array([0.25, 0.0, 0.0], dtype=np.float32)).astype(np.float32),
+}
+
+
+def bend(P):
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    return (P + np.float32(0.05) * np.sin(np.float32(6.0) * P[:, [1, 2, 0]], dtype=np.float32)).astype(np.float32)
+
+
+def no_negative_zero(a):
+    a = np.asarray(a, dtype=np.float32)
+    return not np.signbit(a[a == 0]).any()
+
+
+# ----------------------------------------------------------------------------- the scenes the refit and deform tests move
+def teapot_scene(size=64):
+    return prt_amd.setup_cornell_box(size, size, teapot_mesh=T.teapot_product_mesh())
+
+
+def atrium_scene():
+    return prt_amd.setup_atrium_standin(64, 64, tris=4000, emissive_fraction=0.05)

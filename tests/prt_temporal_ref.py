@@ -217,3 +217,9 @@ def denoise_temporal(total, count, mom, albedo, normal, position, history=None, 
     image, var = iterate(m["valid"], C, V, m["N"], m["A"], d, iterations, normal_power_log2, sigma_luminance, sigma_albedo, exposure)
     p = m["pending"]
     return image, var, dict(color_var=p[0], pos_len=p[1], normal=p[2])
+
+
+# the temporal parameters the tests run the stage with unless they say otherwise, and the three sets the sweeps use
+TDEFAULTS = dict(position_tolerance=0.01, normal_cos=0.9, max_history=256.0)
+PARAMETER_SETS = (TDEFAULTS, dict(position_tolerance=0.05, normal_cos=0.5, max_history=32.0),
+                  dict(position_tolerance=0.02, normal_cos=-1.0, max_history=1e6))

@@ -586,3 +586,15 @@ def build_fake_rccl():
                                f"-L{rocm}/lib", "-lamdhip64", "-pthread", f"-Wl,-rpath,{rocm}/lib"])
         os.replace(out + ".tmp", out)
     return out
+
+
+# ----------------------------------------------------------------------------- comparisons on bit patterns
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_bits_equal(a, b, what=""):
+    a, b = bits(a), bits(b)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    bad = np.nonzero(a != b)
+    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"

@@ -44,7 +44,7 @@ def in_threads(fns):
 
 def main():
     fake = C.CDLL(os.environ["PRT_RCCL_LIB"])  # the same loaded object the product binds
-    hip = C.CDLL("libamdhip64.so")
+    hip = prt_amd.hip_runtime()
     fake.fake_rccl_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
     cases = 0
     # (width, height, ranks, root, tile): ragged right/bottom tiles, a root that is not rank 0, more ranks than tiles, another tile size

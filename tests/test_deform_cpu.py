@@ -12,7 +12,7 @@ import pytest
 import prt_amd
 import prt_deform_ref as D
 import prt_testlib as T
-from test_refit_cpu import RIGID_MOVES, atrium_scene, bend, teapot_scene
+from prt_refit_ref import RIGID_MOVES, atrium_scene, bend, teapot_scene
 
 F = np.float32
 

@@ -11,6 +11,7 @@ import pytest
 import prt_amd
 import prt_display_ref as R
 import prt_testlib as T
+from prt_display_ref import BAD_FIELDS, assert_state_equal, frame
 
 P = prt_amd.DisplayParams.make
 F = np.float32
@@ -19,16 +20,6 @@ F = np.float32
 @pytest.fixture(scope="module", autouse=True)
 def built():
     prt_amd.build()
-
-
-def assert_state_equal(got, want, what=""):
-    """got: a DisplayState (or its as_dict()); want: the restatement's dict.  Floats are compared as words."""
-    g = got.as_dict() if hasattr(got, "as_dict") else got
-    for k in ("gain", "octaves", "target"):
-        assert F(g[k]).view(np.uint32) == F(want[k]).view(np.uint32), (what, k, g[k], want[k])
-    for k in ("valid", "metered", "ignored"):
-        assert int(g[k]) == int(want[k]), (what, k, g[k], want[k])
-    assert np.array_equal(g["hist"], want["hist"]), (what, "hist")
 
 
 def state_struct(d):
@@ -98,11 +89,6 @@ int main(){ long bad=0; const float es[2] = {1/2.2f, 1/2.4f};
     assert subprocess.check_output([str(exe)]).decode().strip() == "0"
 
 
-def frame(level, seed, shape=(24, 40)):
-    rng = np.random.default_rng(seed)
-    return (rng.random(shape + (3,)) * level * 10.0 ** rng.uniform(-2, 2, shape + (1,))).astype(F)
-
-
 def test_metering_special_cases():
     p = P(meter=True, adapt_rate=0.25)
     # an all-black image (and black with NaN, negatives, -inf) leaves the state as it is
@@ -158,17 +144,6 @@ def test_adaptation_sequence_word_for_word():
     _, lo = prt_amd.display_host(frame(1e4, 4), P(meter=True, min_gain=0.5, max_gain=2.0))
     _, hi = prt_amd.display_host(frame(1e-4, 5), P(meter=True, min_gain=0.5, max_gain=2.0))
     assert lo.gain == 0.5 and hi.gain == 2.0
-
-
-BAD_FIELDS = [("tonemap", dict(tonemap=2)), ("transfer", dict(transfer=2)), ("format", dict(format=3)), ("meter", dict(meter=2)),
-              ("gain", dict(gain=-1.0)), ("gain", dict(gain=float("nan"))), ("gain", dict(gain=float("inf"))),
-              ("key", dict(meter=1, key=0.0)), ("key", dict(meter=1, key=float("nan"))), ("key", dict(meter=1, key=float("inf"))),
-              ("lowPermille", dict(meter=1, low_permille=1000, high_permille=1000)),
-              ("highPermille", dict(meter=1, low_permille=500, high_permille=500)), ("highPermille", dict(meter=1, low_permille=600, high_permille=500)),
-              ("highPermille", dict(meter=1, high_permille=1001)),
-              ("minGain", dict(meter=1, min_gain=0.0)), ("minGain", dict(meter=1, min_gain=float("nan"))),
-              ("maxGain", dict(meter=1, min_gain=2.0, max_gain=1.0)), ("maxGain", dict(meter=1, max_gain=float("inf"))),
-              ("adaptRate", dict(meter=1, adapt_rate=0.0)), ("adaptRate", dict(meter=1, adapt_rate=1.5)), ("adaptRate", dict(meter=1, adapt_rate=float("nan")))]
 
 
 def test_host_entry_refuses_every_field_by_name():

@@ -10,38 +10,11 @@ import pytest
 import prt_amd
 import prt_testlib as T
 from prt_adaptive_ref import active_set, luminance, np_error
+from prt_gpukit import assert_bits_equal, upload
+from prt_gpukit import c1_scene, tracer  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 EXPOSURE, FLOOR = 1.0, 0.01
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_bits_equal(a, b, what=""):
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.nonzero(a != b)
-    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-def upload(tracer, scene, camera):
-    tracer.upload_scene(scene)
-    tracer.set_camera(camera)
-
-
-@pytest.fixture(scope="module")
-def c1_scene():
-    return prt_amd.setup_cornell_box(512, 512, teapot_mesh=T.teapot_product_mesh())
 
 
 def run_passes(t, passes, adaptive, **kw):

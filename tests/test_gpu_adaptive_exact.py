@@ -12,6 +12,7 @@ import pytest
 import prt_adaptive_ref as R
 import prt_amd
 import prt_testlib as T
+from prt_gpukit import tracer  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 F32, U32 = np.float32, np.uint32
@@ -22,14 +23,6 @@ SW, SH, SEED = 67, 61, 14  # C: 4087 pixels, the last block of 256 is ragged
 SUB = (3, 5, 60, 50)
 
 
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
 @pytest.fixture(autouse=True)
 def tally(request):
     """Prints what a test compared and how long it took (-s shows it)."""
@@ -38,6 +31,7 @@ def tally(request):
     print(f"\n[{request.node.name}] {R.words_compared - before} words compared, {time.perf_counter() - t0:.2f} s")
 
 
+# (differs from prt_gpukit.upload: takes the (scene, camera, exposure) tuple)
 def upload(tracer, scene_camera):
     scene, camera, _ = scene_camera
     tracer.upload_scene(scene)
@@ -59,6 +53,7 @@ def m_of(mom):
 
 
 # ---- A. exact packet sums
+# (differs from prt_refit_ref.teapot_scene: a fixture, made once)
 @pytest.fixture(scope="module")
 def teapot_scene():
     return prt_amd.setup_cornell_box(W, H, teapot_mesh=T.teapot_product_mesh())

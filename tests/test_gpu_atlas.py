@@ -13,79 +13,25 @@ import prt_atlas_ref as AR
 import prt_bake_ref as BR
 import prt_hostile_shade as HS
 import prt_testlib as T
+from prt_gpukit import SENTINEL, TAIL, fetch, ptr, sentinel, stage_tracers
+from prt_gpukit import dev  # noqa: F401  (fixture: device memory and streams for one test)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 U = np.uint32
 DEPTH = 8
-SENTINEL = 0xffc0bad1   # a NaN no kernel here produces
-TAIL = 16               # sentinel words behind every output
-H2D, D2H = 1, 2
 HOST = prt_amd.QUERY_HOST
 BLOCKS_PER_CU = 8       # PRT_ATLAS_BLOCKS_PER_CU (prt_atlas.hip): four waves a block, one triangle a wave
 
 
-@pytest.fixture(scope="module")
-def hip():
-    h = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipFree.argtypes = [C.c_void_p]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return h
-
-
-class Dev:
-    """A numpy array's bytes in device memory (hipMalloc), 16-byte aligned."""
-
-    def __init__(self, hip, a):
-        self.hip, self.ptr, self.nbytes = hip, C.c_void_p(), a.nbytes
-        assert hip.hipMalloc(C.byref(self.ptr), max(a.nbytes, 64)) == 0 and self.ptr.value % 16 == 0
-        assert hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, H2D) == 0
-
-    def get(self, dtype):
-        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, D2H) == 0  # (the null stream: behind the context's blocking stream)
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
-
-
+# (differs from prt_refit_ref.teapot_scene: 8 x 8, and the Scene alone)
 def teapot_scene():
     """The Cornell box (no vertex normals) and the teapot of tests/golden/teapot_mesh.npz with computed vertex normals."""
     return prt_amd.setup_cornell_box(8, 8, teapot_mesh=T.teapot_product_mesh())[0]
 
 
 SCENES = {"plain": lambda: HS.scene("plain")[0], "box_rr": lambda: HS.scene("box_rr")[0], "teapot": teapot_scene}
-
-
-@pytest.fixture(scope="module")
-def tracers():
-    """Per scene (PathTracer with the scene uploaded and no camera, the scene's arrays); "none": a context without a scene."""
-    prt_amd.build()
-    made = {}
-
-    def get(name):
-        if name not in made:
-            t = prt_amd.PathTracer(max_depth=DEPTH)
-            arrays = None
-            if name != "none":
-                scene = SCENES[name]()
-                t.upload_scene(scene)
-                arrays = scene.arrays()["meshes"]
-            made[name] = (t, arrays)
-        return made[name]
-    yield get
-    for t, _ in made.values():
-        t.close()
-
-
-def sentinel(words):
-    return np.full(words, SENTINEL, dtype=U)
-
-
-def ptr(a):
-    return a if a is None or isinstance(a, int) else a.ctypes.data
+tracers = stage_tracers(SCENES, arrays=True, max_depth=DEPTH)  # tracers(name) -> (context, the scene's mesh arrays)
 
 
 def grid_uvs(prims, inset=0.1):
@@ -98,7 +44,7 @@ def grid_uvs(prims, inset=0.1):
 
 
 # ----------------------------------------------------------------------------- 1. the rasteriser
-def run_rasterize(t, hip, meshes, W, H, device, order=None):
+def run_rasterize(t, dev, meshes, W, H, device, order=None):
     """prt_hip_atlas_rasterize of {meshId: uv} on host or device arrays: (counts dict, texels and hits, each followed by sentinel
     words).  order: the meshIds in the order of the caller's records."""
     order = sorted(meshes) if order is None else order
@@ -109,15 +55,11 @@ def run_rasterize(t, hip, meshes, W, H, device, order=None):
         rc = t._L.prt_hip_atlas_rasterize(t._ctx, W, H, len(order), recs, ptr(texels), ptr(hits), C.byref(counts), HOST, None)
         assert rc == 0, t._L.prt_hip_last_error()
         return counts.as_dict(), texels, hits
-    bufs = [Dev(hip, uvs[m]) for m in order] + [Dev(hip, texels), Dev(hip, hits)]
-    try:
-        recs = (prt_amd.AtlasMesh * len(order))(*[prt_amd.AtlasMesh(meshId=m, primCount=len(uvs[m]), uv=b.ptr.value) for m, b in zip(order, bufs)])
-        rc = t._L.prt_hip_atlas_rasterize(t._ctx, W, H, len(order), recs, bufs[-2].ptr, bufs[-1].ptr, C.byref(counts), 0, None)
-        assert rc == 0, t._L.prt_hip_last_error()
-        return counts.as_dict(), bufs[-2].get(U), bufs[-1].get(U)
-    finally:
-        for b in bufs:
-            b.free()
+    d_uvs, d_texels, d_hits = [dev.upload(uvs[m]) for m in order], dev.upload(texels), dev.upload(hits)
+    recs = (prt_amd.AtlasMesh * len(order))(*[prt_amd.AtlasMesh(meshId=m, primCount=len(uvs[m]), uv=d) for m, d in zip(order, d_uvs)])
+    rc = t._L.prt_hip_atlas_rasterize(t._ctx, W, H, len(order), recs, d_texels, d_hits, C.byref(counts), 0, None)
+    assert rc == 0, t._L.prt_hip_last_error()
+    return counts.as_dict(), fetch(dev, d_texels, texels.size), fetch(dev, d_hits, hits.size)
 
 
 def check_rasterize(got, meshes, W, H, what):
@@ -157,34 +99,34 @@ def soup():
     return {0: np.array(m0, F), 5: np.array(m5, F)}
 
 
-def test_the_soup_equals_the_restatement(tracers, hip):
+def test_the_soup_equals_the_restatement(tracers, dev):
     t, _ = tracers("none")  # prt_hip_atlas_rasterize needs no scene
     meshes, W, H = soup(), 64, 48
-    host = run_rasterize(t, hip, meshes, W, H, device=False, order=[5, 0])  # (the lower key later in memory)
+    host = run_rasterize(t, dev, meshes, W, H, device=False, order=[5, 0])  # (the lower key later in memory)
     texels, hits, counts = check_rasterize(host, meshes, W, H, "the soup, host arrays")
     assert counts["rejected"] == 8 and counts["degenerate"] == 3 and counts["pairs"] > counts["n"] > 1024
     owner = {int(tx): (int(m), int(p)) for tx, m, p in zip(texels, hits["meshId"], hits["primId"])}
     assert owner[36 * 64 + 42] == (0, 4), "the triangle both meshes hold belongs to the lower meshId"
     assert owner[2 * 64 + 4] == (0, 0) and owner[2 * 64 + 2] == (0, 1) and owner[41 * 64 + 55] == (5, 1)
     assert set(p for m, p in owner.values() if m == 0) == {0, 1, 2, 3, 4, 5, 6, 7, 10, 22}, "the triangles that cover a centre no lower key covers"
-    dev = run_rasterize(t, hip, meshes, W, H, device=True, order=[5, 0])
-    for a, b, name in zip(host, dev, ("counts", "texels", "hits")):
+    on_device = run_rasterize(t, dev, meshes, W, H, device=True, order=[5, 0])
+    for a, b, name in zip(host, on_device, ("counts", "texels", "hits")):
         assert a == b if name == "counts" else a.tobytes() == b.tobytes(), f"device and host pointers give different {name}"
-    again = run_rasterize(t, hip, meshes, W, H, device=True, order=[0, 5])
-    assert again[0] == dev[0] and again[1].tobytes() == dev[1].tobytes() and again[2].tobytes() == dev[2].tobytes(), "a second run differs"
-    swapped = run_rasterize(t, hip, meshes, H, W, device=False)
+    again = run_rasterize(t, dev, meshes, W, H, device=True, order=[0, 5])
+    assert again[0] == on_device[0] and again[1].tobytes() == on_device[1].tobytes() and again[2].tobytes() == on_device[2].tobytes(), "a second run differs"
+    swapped = run_rasterize(t, dev, meshes, H, W, device=False)
     check_rasterize(swapped, meshes, H, W, "the soup in a 48 x 64 atlas")
 
 
 @pytest.mark.parametrize("W,H", [(1, 1), (8192, 1), (1, 8192)])
-def test_the_smallest_and_the_widest_atlas(tracers, hip, W, H):
+def test_the_smallest_and_the_widest_atlas(tracers, dev, W, H):
     t, _ = tracers("none")
     meshes = {2: np.array([[(0, 0), (1, 0), (0, 1)], [(0.25, 0.0), (0.75, 0.0), (0.5, 1.0)], [(0.9, 0.2), (0.95, 0.9), (0.2, 0.95)]], F)}
-    _, _, counts = check_rasterize(run_rasterize(t, hip, meshes, W, H, device=False), meshes, W, H, f"{W} x {H}")
+    _, _, counts = check_rasterize(run_rasterize(t, dev, meshes, W, H, device=False), meshes, W, H, f"{W} x {H}")
     assert counts["n"] == 1 if W * H == 1 else counts["n"] > 4096
 
 
-def test_a_fan_beyond_one_trip_of_the_persistent_grid(tracers, hip):
+def test_a_fan_beyond_one_trip_of_the_persistent_grid(tracers, dev):
     t, _ = tracers("none")
     prims = 20000
     assert prims > t.device_info()[1] * BLOCKS_PER_CU * 4 + 256
@@ -192,7 +134,7 @@ def test_a_fan_beyond_one_trip_of_the_persistent_grid(tracers, hip):
     rim = 0.5 + 0.45 * np.stack([np.cos(a), np.sin(a)], axis=1)
     fan = np.stack([np.broadcast_to([0.5, 0.5], (prims, 2)), rim[:-1], rim[1:]], axis=1).astype(F)
     meshes, W, H = {1: fan}, 64, 64
-    _, hits, counts = check_rasterize(run_rasterize(t, hip, meshes, W, H, device=False), meshes, W, H, "the fan")
+    _, hits, counts = check_rasterize(run_rasterize(t, dev, meshes, W, H, device=False), meshes, W, H, "the fan")
     assert counts["n"] > 2000 and len(np.unique(hits["primId"])) > 1500
 
 
@@ -210,7 +152,7 @@ def scene_atlas(t, arrays, W, H):
     return uvs, texels, hits
 
 
-def run_points(t, hip, texels, hits, W, bias, tile, device=False, flags=HOST, n=None, reserved=(0, 0), out=None):
+def run_points(t, dev, texels, hits, W, bias, tile, device=False, flags=HOST, n=None, reserved=(0, 0), out=None):
     """prt_hip_atlas_points itself: (code, the points as words followed by sentinel words)."""
     n = len(hits) if n is None else n
     out = sentinel(len(hits) * 8 + TAIL) if out is None else out
@@ -218,13 +160,9 @@ def run_points(t, hip, texels, hits, W, bias, tile, device=False, flags=HOST, n=
     p.reserved[0], p.reserved[1] = reserved
     if not device:
         return t._L.prt_hip_atlas_points(t._ctx, n, W, ptr(texels), ptr(hits), C.byref(p), ptr(out), flags, None), out
-    bufs = [Dev(hip, a) for a in (texels, hits, out)]
-    try:
-        rc = t._L.prt_hip_atlas_points(t._ctx, n, W, bufs[0].ptr, bufs[1].ptr, C.byref(p), bufs[2].ptr, 0, None)
-        return rc, bufs[2].get(U)
-    finally:
-        for b in bufs:
-            b.free()
+    d_texels, d_hits, d_out = (dev.upload(a) for a in (texels, hits, out))
+    rc = t._L.prt_hip_atlas_points(t._ctx, n, W, d_texels, d_hits, C.byref(p), d_out, 0, None)
+    return rc, fetch(dev, d_out, out.size)
 
 
 def surface_normals(t, hits):
@@ -233,9 +171,9 @@ def surface_normals(t, hits):
     return t.query_surface(z, z, hits)["normal"]
 
 
-def check_points(t, hip, arrays, texels, hits, W, bias, tile, what, device=False):
+def check_points(t, dev, arrays, texels, hits, W, bias, tile, what, device=False):
     want = AR.points(texels, hits, W, [(m["indices"], m["positions"]) for m in arrays], surface_normals(t, hits), bias, tile)
-    rc, got = run_points(t, hip, texels, hits, W, bias, tile, device=device)
+    rc, got = run_points(t, dev, texels, hits, W, bias, tile, device=device)
     assert rc == 0, t._L.prt_hip_last_error()
     words = 8 * len(hits)
     g = got[:words].view(AR.POINT_DTYPE)
@@ -248,11 +186,11 @@ def check_points(t, hip, arrays, texels, hits, W, bias, tile, what, device=False
 
 @pytest.mark.parametrize("tile", [1, 4, 32])
 @pytest.mark.parametrize("name", ["plain", "box_rr", "teapot"])
-def test_points_equal_the_restatement(tracers, hip, name, tile):
+def test_points_equal_the_restatement(tracers, dev, name, tile):
     t, arrays = tracers(name)
     W, H = (160, 144) if name == "teapot" else (45, 37)
     _, texels, hits = scene_atlas(t, arrays, W, H)
-    want = check_points(t, hip, arrays, texels, hits, W, F(1e-3), tile, f"{name} setTile={tile}", device=(tile == 4))
+    want = check_points(t, dev, arrays, texels, hits, W, F(1e-3), tile, f"{name} setTile={tile}", device=(tile == 4))
     assert (want["set"] != AR.NEVER).all() and want["set"].max() == (tile * tile - 1 if tile < 32 else want["set"].max())
     assert len(np.unique(hits["meshId"])) == len(arrays), "every mesh of the scene owns texels"
     if name == "teapot":  # interpolated vertex normals beside face normals
@@ -261,7 +199,7 @@ def test_points_equal_the_restatement(tracers, hip, name, tile):
     print(f"{name}: {len(hits)} points, sets up to {want['set'].max()}")
 
 
-def test_hits_outside_the_scene_give_the_point_never_followed(tracers, hip):
+def test_hits_outside_the_scene_give_the_point_never_followed(tracers, dev):
     t, arrays = tracers("plain")
     pot_t, pot_arrays = tracers("teapot")
     W, H = 160, 144
@@ -273,13 +211,13 @@ def test_hits_outside_the_scene_give_the_point_never_followed(tracers, hip):
     bad["primId"] = [0, 0, 0, 0, prims[0], prims[1], 0xffffffff, 0x80000000]
     hits = np.concatenate([bad, hits])
     texels = np.concatenate([np.arange(8, dtype=U), texels])
-    want = check_points(t, hip, arrays, texels, hits, W, F(0.5), 4, "hits of another scene")
+    want = check_points(t, dev, arrays, texels, hits, W, F(0.5), 4, "hits of another scene")
     never = want["set"] == AR.NEVER
     assert never[:8].all() and never.sum() > len(hits) // 2 and (~never).sum() > 8
     assert not want[never]["P"].any() and not want[never]["N"].any() and not want[never]["bias"].any()
 
 
-def test_the_same_hits_follow_a_moved_mesh(hip):
+def test_the_same_hits_follow_a_moved_mesh(dev):
     prt_amd.build()
     scene = HS.scene("plain")[0]
     t = prt_amd.PathTracer(max_depth=DEPTH)
@@ -287,12 +225,12 @@ def test_the_same_hits_follow_a_moved_mesh(hip):
         t.upload_scene(scene)
         arrays = scene.arrays()["meshes"]
         _, texels, hits = scene_atlas(t, arrays, 45, 37)
-        first = check_points(t, hip, arrays, texels, hits, 45, F(0), 1, "before the move")
+        first = check_points(t, dev, arrays, texels, hits, 45, F(0), 1, "before the move")
         for m, shift in ((0, (0.4, 0.0, 0.3)), (1, (-0.1, 0.2, 0.0))):
             scene.update_positions(m, (arrays[m]["positions"] * F(1.25) + np.array(shift, F)).astype(F))
         t.update_meshes(scene, [0, 1])
         moved = scene.arrays()["meshes"]
-        second = check_points(t, hip, moved, texels, hits, 45, F(0), 1, "after update_meshes")
+        second = check_points(t, dev, moved, texels, hits, 45, F(0), 1, "after update_meshes")
         assert (second["P"] != first["P"]).any(axis=1).all()
     finally:
         t.close()
@@ -325,41 +263,37 @@ def resolve_values(n, stride, seed=6):
     return v
 
 
-def run_resolve(t, hip, texels, values, W, H, stride, gutter, device=False, with_mask=True, flags=HOST, n=None, image=None, mask=None):
+def run_resolve(t, dev, texels, values, W, H, stride, gutter, device=False, with_mask=True, flags=HOST, n=None, image=None, mask=None):
     n = len(texels) if n is None else n
     image = sentinel(W * H * stride + TAIL) if image is None else image
     mask = np.full(W * H + TAIL, 0xab, np.uint8) if mask is None else mask
     if not device:
         rc = t._L.prt_hip_atlas_resolve(t._ctx, W, H, n, ptr(texels), ptr(values), stride, gutter, ptr(image), ptr(mask) if with_mask else None, flags, None)
         return rc, image, mask
-    bufs = [Dev(hip, a) for a in (texels, values, image, mask)]
-    try:
-        rc = t._L.prt_hip_atlas_resolve(t._ctx, W, H, n, bufs[0].ptr, bufs[1].ptr, stride, gutter, bufs[2].ptr, bufs[3].ptr if with_mask else None, 0, None)
-        return rc, bufs[2].get(U), bufs[3].get(np.uint8)
-    finally:
-        for b in bufs:
-            b.free()
+    d_texels, d_values, d_image, d_mask = (dev.upload(a) for a in (texels, values, image, mask))
+    rc = t._L.prt_hip_atlas_resolve(t._ctx, W, H, n, d_texels, d_values, stride, gutter, d_image, d_mask if with_mask else None, 0, None)
+    return rc, fetch(dev, d_image, image.size), fetch(dev, d_mask, mask.size, np.uint8)
 
 
 @pytest.mark.parametrize("gutter", [0, 1, 3, 64])
 @pytest.mark.parametrize("stride", [1, 3, 48])
-def test_resolve_equals_the_restatement(tracers, hip, stride, gutter):
+def test_resolve_equals_the_restatement(tracers, dev, stride, gutter):
     t, _ = tracers("none")  # prt_hip_atlas_resolve needs no scene
     inside = islands()
     texels = np.concatenate([inside[:20], np.array([RW * RH, 0xffffffff], U), inside[20:]])  # two indices outside the image: ignored
     values = resolve_values(len(texels), stride)
     want_i, want_m = AR.resolve(texels, values, RW, RH, gutter)
-    rc, image, mask = run_resolve(t, hip, texels, values, RW, RH, stride, gutter)
+    rc, image, mask = run_resolve(t, dev, texels, values, RW, RH, stride, gutter)
     assert rc == 0, t._L.prt_hip_last_error()
     words = RW * RH * stride
     nans = BR.same_bytes(image[:words], want_i, f"stride={stride} gutter={gutter}")
     assert mask[:RW * RH].tobytes() == want_m.tobytes() and (image[words:] == SENTINEL).all() and (mask[RW * RH:] == 0xab).all()
     assert nans >= (1 if gutter == 0 else 3)
     assert want_m.all() if gutter == 64 else int(want_m.max()) == gutter + 1, "64 passes fill the image, fewer leave texels empty"
-    rc, dev_i, dev_m = run_resolve(t, hip, texels, values, RW, RH, stride, gutter, device=True)
+    rc, dev_i, dev_m = run_resolve(t, dev, texels, values, RW, RH, stride, gutter, device=True)
     assert rc == 0 and dev_i.tobytes() == image.tobytes() and dev_m.tobytes() == mask.tobytes(), "device and host pointers give different bytes"
     for device in (False, True):  # mask = NULL
-        rc, no_mask_i, untouched = run_resolve(t, hip, texels, values, RW, RH, stride, gutter, device=device, with_mask=False)
+        rc, no_mask_i, untouched = run_resolve(t, dev, texels, values, RW, RH, stride, gutter, device=device, with_mask=False)
         assert rc == 0 and no_mask_i.tobytes() == image.tobytes() and (untouched == 0xab).all()
 
 
@@ -397,7 +331,7 @@ def test_lightmap_equals_the_four_calls_and_the_restatement(tracers):
 
 
 # ----------------------------------------------------------------------------- 5. refusals
-def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
+def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, dev):
     t, arrays = tracers("plain")
     bare, _ = tracers("none")
     L = t._L
@@ -424,13 +358,13 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
     # points
     _, texels, hits = scene_atlas(t, arrays, 45, 37)
     pts_out = sentinel(len(hits) * 8)
-    rc, _ = run_points(bare, hip, texels, hits, 45, F(0), 1, out=pts_out)
+    rc, _ = run_points(bare, dev, texels, hits, 45, F(0), 1, out=pts_out)
     assert rc == -5 and b"upload a scene" in L.prt_hip_last_error()
     for kw in (dict(flags=HOST | 4), dict(flags=2), dict(n=0), dict(n=(1 << 26) + 1), dict(W=0), dict(W=8193), dict(tile=0), dict(tile=33),
                dict(reserved=(1, 0)), dict(reserved=(0, 1))):
         args = dict(W=45, bias=F(0), tile=1)
         args.update(kw)
-        rc, _ = run_points(t, hip, texels, hits, out=pts_out, **args)
+        rc, _ = run_points(t, dev, texels, hits, out=pts_out, **args)
         assert rc == -2 and L.prt_hip_last_error(), kw
     p = prt_amd.AtlasPointParams(bias=0.0, setTile=1)
     for args in ((None, ptr(hits), C.byref(p), ptr(pts_out)), (ptr(texels), None, C.byref(p), ptr(pts_out)), (ptr(texels), ptr(hits), None, ptr(pts_out)),
@@ -442,7 +376,7 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
     image_out, mask_out = sentinel(RW * RH * 3), np.full(RW * RH, 0xab, np.uint8)
 
     def resolve(W=RW, H=RH, stride=3, gutter=2, **kw):
-        return run_resolve(t, hip, inside, values, W, H, stride, gutter, image=image_out, mask=mask_out, **kw)[0]
+        return run_resolve(t, dev, inside, values, W, H, stride, gutter, image=image_out, mask=mask_out, **kw)[0]
     for kw in (dict(flags=HOST | 8), dict(flags=0x40000000), dict(W=0), dict(W=8193), dict(H=0), dict(H=8193), dict(n=0), dict(n=(1 << 26) + 1),
                dict(stride=0), dict(stride=49), dict(gutter=65)):
         assert resolve(**kw) == -2 and L.prt_hip_last_error(), kw
@@ -450,28 +384,24 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
                  (ptr(inside), ptr(values), 3, 2, None, ptr(mask_out))):
         assert L.prt_hip_atlas_resolve(t._ctx, RW, RH, len(inside), *args, HOST, None) == -2
     # device pointers that are not aligned
-    d = Dev(hip, np.zeros(1 << 16, np.uint8))
-    try:
-        base = d.ptr.value
-        one = (prt_amd.AtlasMesh * 1)(prt_amd.AtlasMesh(meshId=0, primCount=4, uv=base + 2))
-        assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096, base + 8192, C.byref(c), 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        one[0].uv = base
-        assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096 + 1, base + 8192, C.byref(c), 0, None) == -2
-        assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096, base + 8192 + 2, C.byref(c), 0, None) == -2
-        assert L.prt_hip_atlas_points(t._ctx, 16, 45, base, base + 4096, C.byref(p), base + 8192 + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_atlas_points(t._ctx, 16, 45, base + 2, base + 4096, C.byref(p), base + 8192, 0, None) == -2
-        assert L.prt_hip_atlas_points(t._ctx, 16, 45, base, base + 4096 + 1, C.byref(p), base + 8192, 0, None) == -2
-        assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base + 2, base + 4096, 3, 2, base + 8192, base + 16384, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base, base + 4096 + 1, 3, 2, base + 8192, base + 16384, 0, None) == -2
-        assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base, base + 4096, 3, 2, base + 8192 + 2, base + 16384, 0, None) == -2
-        assert not d.get(np.uint8).any(), "a refused call wrote device memory"
-    finally:
-        d.free()
+    base = dev.upload(np.zeros(1 << 16, np.uint8))
+    one = (prt_amd.AtlasMesh * 1)(prt_amd.AtlasMesh(meshId=0, primCount=4, uv=base + 2))
+    assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096, base + 8192, C.byref(c), 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
+    one[0].uv = base
+    assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096 + 1, base + 8192, C.byref(c), 0, None) == -2
+    assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, one, base + 4096, base + 8192 + 2, C.byref(c), 0, None) == -2
+    assert L.prt_hip_atlas_points(t._ctx, 16, 45, base, base + 4096, C.byref(p), base + 8192 + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_atlas_points(t._ctx, 16, 45, base + 2, base + 4096, C.byref(p), base + 8192, 0, None) == -2
+    assert L.prt_hip_atlas_points(t._ctx, 16, 45, base, base + 4096 + 1, C.byref(p), base + 8192, 0, None) == -2
+    assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base + 2, base + 4096, 3, 2, base + 8192, base + 16384, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base, base + 4096 + 1, 3, 2, base + 8192, base + 16384, 0, None) == -2
+    assert L.prt_hip_atlas_resolve(t._ctx, 8, 8, 16, base, base + 4096, 3, 2, base + 8192 + 2, base + 16384, 0, None) == -2
+    assert not fetch(dev, base, 1 << 16, np.uint8).any(), "a refused call wrote device memory"
     for name, o in (("texels", texels_out), ("hits", hits_out), ("points", pts_out), ("image", image_out)):
         assert (o == SENTINEL).all(), f"a refused call wrote its {name}"
     assert (mask_out == 0xab).all()
     # and the same arguments are accepted
     c = prt_amd.AtlasCounts()
     assert L.prt_hip_atlas_rasterize(t._ctx, W, H, 1, arr, ptr(texels_out), ptr(hits_out), C.byref(c), HOST, None) == 0 and c.n > 0
-    assert run_points(t, hip, texels, hits, 45, F(0), 1, out=pts_out)[0] == 0 and not (pts_out == SENTINEL).any()
+    assert run_points(t, dev, texels, hits, 45, F(0), 1, out=pts_out)[0] == 0 and not (pts_out == SENTINEL).any()
     assert resolve() == 0 and not (image_out == SENTINEL).any()

@@ -11,6 +11,8 @@ import prt_amd
 import prt_bake_ref as BR
 import prt_hostile_shade as HS
 import prt_probe_ref as PR
+from prt_gpukit import SCENES, SENTINEL, TAIL, fetch, ptr, sentinel, stage_tracers
+from prt_gpukit import dev  # noqa: F401  (fixture: device memory and streams for one test)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -19,70 +21,7 @@ DEPTH = 8
 N_POINTS = 37
 KS = (1, 63, 64, 65, 130)
 BLOCKS_PER_CU = 8       # PRT_BAKE_BLOCKS_PER_CU (prt_bake.hip): blocks of 256 lanes either kernel is launched with at the most
-SENTINEL = 0xffc0bad1   # a NaN no kernel here produces
-TAIL = 16               # sentinel words behind every output
-H2D, D2H = 1, 2
-
-
-def sky_stage():
-    s, cam = HS.scene("plain", light=None)
-    s.set_infinite_area_light(HS.sky())
-    return s, cam
-
-
-SCENES = {"plain": lambda: HS.scene("plain"), "sky": sky_stage, "box_rr": lambda: HS.scene("box_rr")}
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipFree.argtypes = [C.c_void_p]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    h.hipStreamDestroy.argtypes = [C.c_void_p]
-    return h
-
-
-class Dev:
-    """A numpy array's bytes in device memory (hipMalloc), 16-byte aligned."""
-
-    def __init__(self, hip, a):
-        self.hip, self.ptr, self.nbytes = hip, C.c_void_p(), a.nbytes
-        assert hip.hipMalloc(C.byref(self.ptr), max(a.nbytes, 64)) == 0 and self.ptr.value % 16 == 0
-        assert hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, H2D) == 0
-
-    def get(self, dtype):
-        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, D2H) == 0
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
-
-
-@pytest.fixture(scope="module")
-def tracers():
-    """Per stage a PathTracer with the scene uploaded and no camera; "none": a context without a scene."""
-    prt_amd.build()
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = prt_amd.PathTracer(max_depth=DEPTH)
-            if name != "none":
-                made[name].upload_scene(SCENES[name]()[0])
-        return made[name]
-    yield get
-    for t in made.values():
-        t.close()
-
-
-def sentinel(words):
-    return np.full(words, SENTINEL, dtype=U)
-
-
+tracers = stage_tracers(SCENES, max_depth=DEPTH)
 HOST = "the host array of the Sets"
 
 
@@ -94,10 +33,6 @@ def table(sets, dirs=HOST, weights=HOST, **fields):
     for k, v in fields.items():
         setattr(t, k, v)
     return t
-
-
-def ptr(a):
-    return a if a is None or isinstance(a, int) else a.ctypes.data
 
 
 # ----------------------------------------------------------------------------- the points
@@ -151,7 +86,7 @@ def make_sets(nSets, K, Cc, seed=2):
 
 
 # ----------------------------------------------------------------------------- 1. rays
-def run_rays(t, hip, pts, sets, device):
+def run_rays(t, dev, pts, sets, device):
     """prt_hip_bake_rays on host or device arrays: the n*K rays followed by the sentinel words."""
     n = len(pts)
     out = sentinel(n * sets.K * 8 + TAIL)
@@ -160,15 +95,11 @@ def run_rays(t, hip, pts, sets, device):
         rc = t._L.prt_hip_bake_rays(t._ctx, n, ptr(pts), C.byref(tb), ptr(out), prt_amd.QUERY_HOST, None)
         assert rc == 0, t._L.prt_hip_last_error()
         return out
-    bufs = [Dev(hip, a) for a in (pts, sets.dirs, out)]
-    try:
-        tb = table(sets, weights=None, dirs=bufs[1].ptr.value)
-        rc = t._L.prt_hip_bake_rays(t._ctx, n, bufs[0].ptr, C.byref(tb), bufs[2].ptr, 0, None)
-        assert rc == 0, t._L.prt_hip_last_error()
-        return bufs[2].get(U)  # (hipMemcpy on the null stream: behind the context's blocking stream)
-    finally:
-        for b in bufs:
-            b.free()
+    d_pts, d_dirs, d_out = (dev.upload(a) for a in (pts, sets.dirs, out))
+    tb = table(sets, weights=None, dirs=d_dirs)
+    rc = t._L.prt_hip_bake_rays(t._ctx, n, d_pts, C.byref(tb), d_out, 0, None)
+    assert rc == 0, t._L.prt_hip_last_error()
+    return fetch(dev, d_out, out.size)
 
 
 def check_rays(got, pts, sets, what):
@@ -185,19 +116,19 @@ def check_rays(got, pts, sets, what):
 
 @pytest.mark.parametrize("nSets", [1, 3])
 @pytest.mark.parametrize("K", KS)
-def test_rays_equal_the_restatement(tracers, hip, K, nSets):
+def test_rays_equal_the_restatement(tracers, dev, K, nSets):
     t = tracers("none")  # prt_hip_bake_rays needs no scene
     pts, sets = make_points(nSets, stage_origins), make_sets(nSets, K, 1)
-    host = run_rays(t, hip, pts, sets, device=False)
+    host = run_rays(t, dev, pts, sets, device=False)
     nans = check_rays(host, pts, sets, f"K={K} nSets={nSets}, host arrays")
     r = host[:N_POINTS * K * 8].view(BR.RAY_DTYPE).reshape(N_POINTS, K)
     assert not r["org"][[30, 33]].view(U).any() and not r["dir"][[30, 33]].view(U).any(), "a set outside the table was followed"
     assert np.isfinite(r["dir"][:17]).all() and nans > 0
-    dev = run_rays(t, hip, pts, sets, device=True)
-    assert dev.tobytes() == host.tobytes(), "device and host pointers give different bytes"
+    on_device = run_rays(t, dev, pts, sets, device=True)
+    assert on_device.tobytes() == host.tobytes(), "device and host pointers give different bytes"
 
 
-def test_rays_beyond_one_trip_of_the_grid_stride_loop(tracers, hip):
+def test_rays_beyond_one_trip_of_the_grid_stride_loop(tracers, dev):
     t = tracers("none")
     K, nSets = 65, 3
     one_trip = t.device_info()[1] * BLOCKS_PER_CU * 256
@@ -207,11 +138,12 @@ def test_rays_beyond_one_trip_of_the_grid_stride_loop(tracers, hip):
     pts = np.tile(base, n // N_POINTS + 1)[:n].copy()
     pts["P"][:, 0] += np.arange(n, dtype=F) * F(0.001)  # (no two points alike)
     sets = make_sets(nSets, K, 1)
-    got = run_rays(t, hip, pts, sets, device=False)
+    got = run_rays(t, dev, pts, sets, device=False)
     check_rays(got, pts, sets, f"{n} points x {K} directions")
 
 
 # ----------------------------------------------------------------------------- 2. reduce
+# (differs from test_gpu_lens.py's: a +1e38 / -1e38 pair that cancels in every point, NaN in point 5 only, no infinities)
 def synthetic_radiance(n, K, seed=3):
     """(n*K, 3): random values, -0.0, denormals, a +1e38 / -1e38 pair that cancels in every point (k = 0 and 1, where the weights are
     1), and NaN in rows of point 5 only."""
@@ -227,7 +159,7 @@ def synthetic_radiance(n, K, seed=3):
     return L.reshape(n * K, 3)
 
 
-def run_reduce(t, hip, pts, sets, L, device):
+def run_reduce(t, dev, pts, sets, L, device):
     n = len(pts)
     out = sentinel(n * sets.C * 3 + TAIL)
     if not device:
@@ -235,18 +167,14 @@ def run_reduce(t, hip, pts, sets, L, device):
         rc = t._L.prt_hip_bake_reduce(t._ctx, n, ptr(pts), C.byref(tb), ptr(L), ptr(out), prt_amd.QUERY_HOST, None)
         assert rc == 0, t._L.prt_hip_last_error()
         return out
-    bufs = [Dev(hip, a) for a in (pts, sets.weights, L, out)]
-    try:
-        tb = table(sets, dirs=None, weights=bufs[1].ptr.value)
-        rc = t._L.prt_hip_bake_reduce(t._ctx, n, bufs[0].ptr, C.byref(tb), bufs[2].ptr, bufs[3].ptr, 0, None)
-        assert rc == 0, t._L.prt_hip_last_error()
-        return bufs[3].get(U)
-    finally:
-        for b in bufs:
-            b.free()
+    d_pts, d_w, d_L, d_out = (dev.upload(a) for a in (pts, sets.weights, L, out))
+    tb = table(sets, dirs=None, weights=d_w)
+    rc = t._L.prt_hip_bake_reduce(t._ctx, n, d_pts, C.byref(tb), d_L, d_out, 0, None)
+    assert rc == 0, t._L.prt_hip_last_error()
+    return fetch(dev, d_out, out.size)
 
 
-def check_reduce(t, hip, K, Cc, nSets=3):
+def check_reduce(t, dev, K, Cc, nSets=3):
     pts, sets = make_points(nSets, stage_origins), make_sets(nSets, K, Cc)
     sets.weights[:, :2] = 1.0
     L = synthetic_radiance(N_POINTS, K)
@@ -254,30 +182,30 @@ def check_reduce(t, hip, K, Cc, nSets=3):
     words = want.size
     assert np.isnan(want[5]).all() and not np.isnan(np.delete(want, 5, axis=0)).any(), "the NaN stays in its point"
     assert want[[30, 33]].tobytes() == np.zeros((2, Cc, 3), F).tobytes()
-    host = run_reduce(t, hip, pts, sets, L, device=False)
+    host = run_reduce(t, dev, pts, sets, L, device=False)
     BR.same_bytes(host[:words], want, f"K={K} C={Cc}, host arrays")
     assert (host[words:] == SENTINEL).all(), "words behind out were written"
-    dev = run_reduce(t, hip, pts, sets, L, device=True)
-    assert dev.tobytes() == host.tobytes(), "device and host pointers give different bytes"
+    on_device = run_reduce(t, dev, pts, sets, L, device=True)
+    assert on_device.tobytes() == host.tobytes(), "device and host pointers give different bytes"
 
 
 @pytest.mark.parametrize("Cc", [1, 3, 9, 16])
 @pytest.mark.parametrize("K", KS)
-def test_reduce_equals_the_restatement(tracers, hip, K, Cc):
-    check_reduce(tracers("none"), hip, K, Cc)
+def test_reduce_equals_the_restatement(tracers, dev, K, Cc):
+    check_reduce(tracers("none"), dev, K, Cc)
 
 
-def test_reduce_of_the_largest_set(tracers, hip):
-    check_reduce(tracers("none"), hip, 4096, 3, nSets=2)
+def test_reduce_of_the_largest_set(tracers, dev):
+    check_reduce(tracers("none"), dev, 4096, 3, nSets=2)
 
 
-def test_a_nan_weight_stays_in_its_set(tracers, hip):
+def test_a_nan_weight_stays_in_its_set(tracers, dev):
     t = tracers("none")
     pts, sets = make_points(3, stage_origins), make_sets(3, 65, 3)
     sets.weights[1, 64, 2] = np.nan
     L = np.random.default_rng(4).gamma(1.0, 1.0, size=(N_POINTS * 65, 3)).astype(F)
     want = BR.reduce(pts, sets, L)
-    got = run_reduce(t, hip, pts, sets, L, device=False)
+    got = run_reduce(t, dev, pts, sets, L, device=False)
     BR.same_bytes(got[:want.size], want, "a NaN weight")
     hit = np.isnan(want).any(axis=(1, 2))
     assert (hit == (pts["set"] == 1)).all() and np.isnan(want[hit][:, 2]).all() and not np.isnan(want[hit][:, :2]).any()
@@ -368,7 +296,7 @@ def test_a_cosine_set_gives_the_irradiance_of_the_c10_recipe(tracers):
 
 
 # ----------------------------------------------------------------------------- 5. refusals and state
-def test_refusals_queue_nothing_and_leave_out_untouched(tracers, hip):
+def test_refusals_queue_nothing_and_leave_out_untouched(tracers, dev):
     t, bare = tracers("plain"), tracers("none")
     L = t._L
     pts, sets = make_points(3, stage_origins), make_sets(3, 8, 2)
@@ -408,18 +336,14 @@ def test_refusals_queue_nothing_and_leave_out_untouched(tracers, hip):
     assert L.prt_hip_bake(t._ctx, N_POINTS, ptr(pts), None, C.byref(p), ptr(outs["bake"]), prt_amd.QUERY_HOST, None) == -2
     assert L.prt_hip_bake(t._ctx, N_POINTS, ptr(pts), C.byref(tb), C.byref(p), None, prt_amd.QUERY_HOST, None) == -2
     # device pointers that are not aligned
-    d = Dev(hip, np.zeros(1 << 16, np.uint8))
-    try:
-        base = d.ptr.value
-        dt = table(sets, dirs=base, weights=base + 4096)
-        assert L.prt_hip_bake(t._ctx, N_POINTS, base + 8192 + 8, C.byref(dt), C.byref(p), base + 16384, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_bake(t._ctx, N_POINTS, base + 8192, C.byref(dt), C.byref(p), base + 16384 + 2, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_bake_rays(t._ctx, N_POINTS, base + 8192, C.byref(dt), base + 16384 + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
-        dt.weights = base + 4096 + 1
-        assert L.prt_hip_bake_reduce(t._ctx, N_POINTS, base + 8192, C.byref(dt), base + 16384, base + 32768, 0, None) == -2
-        assert not d.get(np.uint8).any(), "a refused call wrote device memory"
-    finally:
-        d.free()
+    base = dev.upload(np.zeros(1 << 16, np.uint8))
+    dt = table(sets, dirs=base, weights=base + 4096)
+    assert L.prt_hip_bake(t._ctx, N_POINTS, base + 8192 + 8, C.byref(dt), C.byref(p), base + 16384, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_bake(t._ctx, N_POINTS, base + 8192, C.byref(dt), C.byref(p), base + 16384 + 2, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_bake_rays(t._ctx, N_POINTS, base + 8192, C.byref(dt), base + 16384 + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
+    dt.weights = base + 4096 + 1
+    assert L.prt_hip_bake_reduce(t._ctx, N_POINTS, base + 8192, C.byref(dt), base + 16384, base + 32768, 0, None) == -2
+    assert not fetch(dev, base, 1 << 16, np.uint8).any(), "a refused call wrote device memory"
     assert t.stats()["kernelLaunches"] == 0
     for k, o in outs.items():
         assert (o == SENTINEL).all(), f"a refused {k} call wrote its output"
@@ -485,32 +409,25 @@ def test_a_bake_sees_the_moved_mesh():
         t.close()
 
 
-def test_device_arrays_on_a_callers_stream_with_a_copy_behind(tracers, hip):
+def test_device_arrays_on_a_callers_stream_with_a_copy_behind(tracers, dev):
     t = tracers("sky")
     pts, sets = make_points(3, stage_origins), make_sets(3, 130, 9)
     spp, seed = 8, 31
     rc, want = run_bake(t, pts, sets, spp, seed)
     assert rc == 0
     words = N_POINTS * 9 * 3
-    stream = C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    stream = dev.stream()
     zeros = np.zeros_like(pts)
-    bufs = [Dev(hip, a) for a in (zeros, sets.dirs, sets.weights, sentinel(words + TAIL), sentinel(words + TAIL))]
+    d_pts, d_dirs, d_w, d_out, d_copy = (dev.upload(a) for a in (zeros, sets.dirs, sets.weights, sentinel(words + TAIL), sentinel(words + TAIL)))
     got = np.zeros(words + TAIL, U)
-    try:
-        d_pts, d_dirs, d_w, d_out, d_copy = (b.ptr.value for b in bufs)
-        # the points arrive on the caller's stream, the bake is queued behind them and a device copy of the answer behind the bake
-        assert hip.hipMemcpyAsync(d_pts, pts.ctypes.data, pts.nbytes, H2D, stream) == 0
-        tb = prt_amd.BakeSets(K=sets.K, C=sets.C, nSets=sets.nSets, reserved=0, dirs=d_dirs, weights=d_w)
-        t.stats()
-        t.bake_async(N_POINTS, d_pts, tb, d_out, spp, seed=seed, stream=stream.value)
-        assert hip.hipMemcpyAsync(d_copy, d_out, (words + TAIL) * 4, 3, stream) == 0  # device to device
-        assert hip.hipMemcpyAsync(got.ctypes.data, d_copy, (words + TAIL) * 4, D2H, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        for b in bufs:
-            b.free()
-        hip.hipStreamDestroy(stream)
+    # the points arrive on the caller's stream, the bake is queued behind them and a device copy of the answer behind the bake
+    dev.upload_async(pts, stream, d_pts)
+    tb = prt_amd.BakeSets(K=sets.K, C=sets.C, nSets=sets.nSets, reserved=0, dirs=d_dirs, weights=d_w)
+    t.stats()
+    t.bake_async(N_POINTS, d_pts, tb, d_out, spp, seed=seed, stream=stream)
+    dev.copy_async(d_copy, d_out, (words + TAIL) * 4, stream)
+    dev.download_async(got, d_copy, stream)
+    dev.synchronize(stream)
     assert got.tobytes() == want.tobytes()
     st = t.stats()
     assert st["kernelLaunches"] == 1 and st["nPx"] == N_POINTS * 130

@@ -13,11 +13,12 @@ import pytest
 import prt_amd
 import prt_deform_ref as D
 import prt_testlib as T
-from prt_refit_ref import refit_nodes
-from test_gpu_denoise import DEFAULTS, assert_bits_equal
-from test_gpu_refit import CASES, arrays_equal, moved_normals, teapot_scene
-from test_gpu_temporal import TDEFAULTS, record_equal
-from test_refit_cpu import RIGID_MOVES, bend, no_negative_zero
+from prt_denoise_ref import DEFAULTS
+from prt_gpucases import CASES, arrays_equal, moved_normals, record_equal
+from prt_gpukit import assert_bits_equal
+from prt_gpukit import dev, rows, rows2  # noqa: F401  (fixtures)
+from prt_refit_ref import RIGID_MOVES, bend, no_negative_zero, refit_nodes, teapot_scene
+from prt_temporal_ref import TDEFAULTS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -25,45 +26,9 @@ KEEP, GIVEN, RECOMPUTE = 0, 1, 2
 EINVAL, ESTATE = -2, -5
 
 
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows2():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def hip():
-    return C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-
-
-class DeviceArray:
-    """A float32 array in device memory (hipMalloc); `fill` = False leaves it for a later asynchronous copy."""
-
-    def __init__(self, hip, a, fill=True):
-        self.hip, self.ptr = hip, C.c_void_p()
-        self.host = np.ascontiguousarray(a, dtype=F)
-        assert hip.hipMalloc(C.byref(self.ptr), C.c_size_t(max(self.host.nbytes, 64))) == 0
-        if fill:
-            assert hip.hipMemcpy(self.ptr, self.host.ctypes.data_as(C.c_void_p), C.c_size_t(self.host.nbytes), 1) == 0
-        else:
-            assert hip.hipMemset(self.ptr, 0xA5, C.c_size_t(self.host.nbytes)) == 0
-
-    @property
-    def value(self):
-        return self.ptr.value
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
+def on_device(dev, a):
+    """The device address of a float32 copy of `a`."""
+    return dev.upload(np.ascontiguousarray(a, dtype=F))
 
 
 def render_with_counts(t, samples=16):
@@ -76,7 +41,7 @@ STATE_CASES = {"teapot_bend": RECOMPUTE, "atrium_normals_kept": KEEP, "atrium_fa
 
 
 @pytest.mark.parametrize("case", list(STATE_CASES))
-def test_deform_from_device_memory_equals_a_fresh_upload(rows, rows2, hip, case):
+def test_deform_from_device_memory_equals_a_fresh_upload(rows, rows2, dev, case):
     make, m, deform, _, _ = CASES[case]
     mode = STATE_CASES[case]
     scene, camera, _ = make()
@@ -86,11 +51,7 @@ def test_deform_from_device_memory_equals_a_fresh_upload(rows, rows2, hip, case)
     old = rows.scene_arrays()
     P = deform(mesh["positions"])
     assert no_negative_zero(P)
-    dP = DeviceArray(hip, P)
-    try:
-        rows.deform_meshes([(m, dP.value, mode)])  # radius_auto
-    finally:
-        dP.free()
+    rows.deform_meshes([(m, on_device(dev, P), mode)])  # radius_auto
     scene.update_positions(m, P, moved_normals(mesh, P) if mode == RECOMPUTE else None)  # the host's way, with the oracle's normals
     rows2.upload_scene(scene)
     rows2.set_camera(camera)
@@ -131,17 +92,13 @@ ROW_MESHES = {
 
 
 @pytest.mark.parametrize("which", list(ROW_MESHES))
-def test_recomputed_normals_boxes_and_radius(rows, hip, which):
+def test_recomputed_normals_boxes_and_radius(rows, dev, which):
     idx, P = ROW_MESHES[which]()
     scene, desc = one_mesh_scene(idx, (F(2.0) * P).astype(F))  # uploaded at twice the size (exact), deformed to P
     rows.upload_scene(scene)
     with pytest.raises(prt_amd.PrtError, match=r"\(-5\).*no update yet"):
         rows.mesh_vertices(0)
-    dP = DeviceArray(hip, P)
-    try:
-        rows.deform_meshes([(0, dP.value, RECOMPUTE)])
-    finally:
-        dP.free()
+    rows.deform_meshes([(0, on_device(dev, P), RECOMPUTE)])
     gotP, gotN = rows.mesh_vertices(0)
     want = T.oracle_vertex_normals(desc).normals
     assert gotP.tobytes() == P.tobytes()
@@ -160,7 +117,7 @@ def test_recomputed_normals_boxes_and_radius(rows, hip, which):
 
 # ----------------------------------------------------------------------------- 3. GIVEN and HOST against prt_hip_update_meshes
 @pytest.mark.parametrize("flavour", ["device_given", "host_given", "host_recompute", "host_keep"])
-def test_flavours_equal_update_meshes_on_a_twin(rows, rows2, hip, flavour):
+def test_flavours_equal_update_meshes_on_a_twin(rows, rows2, dev, flavour):
     scene, camera, _ = teapot_scene()
     twin, _, _ = teapot_scene()
     tea = scene.arrays()["meshes"][1]
@@ -173,12 +130,7 @@ def test_flavours_equal_update_meshes_on_a_twin(rows, rows2, hip, flavour):
     rows2.update_meshes(twin, [1], keep_normals=keep)
     rows.upload_scene(scene)
     if flavour == "device_given":
-        dP, dN = DeviceArray(hip, P), DeviceArray(hip, N)
-        try:
-            rows.deform_meshes([(1, dP.value, dN.value)])
-        finally:
-            dP.free()
-            dN.free()
+        rows.deform_meshes([(1, on_device(dev, P), on_device(dev, N))])
     else:
         rows.deform_meshes([(1, P, {"host_given": N, "host_recompute": RECOMPUTE, "host_keep": KEEP}[flavour])], host=True)
     arrays_equal(rows.scene_arrays(), rows2.scene_arrays(), flavour)
@@ -190,7 +142,7 @@ def test_flavours_equal_update_meshes_on_a_twin(rows, rows2, hip, flavour):
     assert rows.scene_arrays()["radius"][0].tobytes() == before.tobytes()
 
 
-def test_auto_radius_sees_meshes_the_host_path_changed(rows, rows2, hip):
+def test_auto_radius_sees_meshes_the_host_path_changed(rows, rows2, dev):
     """Mesh 0 goes through prt_hip_update_meshes, mesh 1 through the device path: the radius is the host Scene's after both."""
     scene, camera, _ = teapot_scene()
     a = scene.arrays()
@@ -203,32 +155,23 @@ def test_auto_radius_sees_meshes_the_host_path_changed(rows, rows2, hip):
     rows.upload_scene(teapot_scene()[0])
     rows.update_meshes(scene, [0])
     P1 = RIGID_MOVES["shift0.25x"](tea["positions"])
-    dP = DeviceArray(hip, P1)
-    try:
-        rows.deform_meshes([(1, dP.value, RECOMPUTE)])
-    finally:
-        dP.free()
+    rows.deform_meshes([(1, on_device(dev, P1), RECOMPUTE)])
     scene.update_positions(1, P1, moved_normals(tea, P1))
     rows2.upload_scene(scene)
     arrays_equal(rows.scene_arrays(), rows2.scene_arrays(), "host path for mesh 0, device path for mesh 1")
 
 
 # ----------------------------------------------------------------------------- 4. a caller's stream
-def test_copy_and_deform_on_a_callers_stream(rows, rows2, hip):
+def test_copy_and_deform_on_a_callers_stream(rows, rows2, dev):
     scene, camera, _ = teapot_scene()
     tea = scene.arrays()["meshes"][1]
     P = bend(tea["positions"])
     rows.upload_scene(scene)
-    stream = C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    dP = DeviceArray(hip, P, fill=False)
-    try:
-        assert hip.hipMemcpyAsync(dP.ptr, P.ctypes.data_as(C.c_void_p), C.c_size_t(P.nbytes), 1, stream) == 0
-        rows.deform_meshes([(1, dP.value, RECOMPUTE)], stream=stream.value)  # no synchronisation in between
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        dP.free()
-        hip.hipStreamDestroy(stream)
+    stream, dP = dev.stream(), dev.alloc(P.nbytes)
+    dev.fill(dP, 0xA5, P.nbytes)
+    dev.upload_async(P, stream, dP)
+    rows.deform_meshes([(1, dP, RECOMPUTE)], stream=stream)  # no synchronisation in between
+    dev.synchronize(stream)
     scene.update_positions(1, P, moved_normals(tea, P))
     rows2.upload_scene(scene)
     arrays_equal(rows.scene_arrays(), rows2.scene_arrays(), "copy and deform on one stream")
@@ -243,7 +186,7 @@ def test_torch_tensor_on_torchs_stream():
 
 
 # ----------------------------------------------------------------------------- 5. what a deform invalidates
-def test_invalidation_is_update_meshes(hip):
+def test_invalidation_is_update_meshes(dev):
     prt_amd.build()
     out = []
     for device_path in (True, False):
@@ -260,11 +203,7 @@ def test_invalidation_is_update_meshes(hip):
                 t.adaptive_pass(8, 0.0, 8 * (k + 1), 8 * (k + 1), 0.01)
             t.denoise_temporal(exposure=exposure, **TDEFAULTS, **DEFAULTS)
             if device_path:
-                dP = DeviceArray(hip, P)
-                try:
-                    t.deform_meshes([(1, dP.value, RECOMPUTE)])
-                finally:
-                    dP.free()
+                t.deform_meshes([(1, on_device(dev, P), RECOMPUTE)])
             else:
                 scene.update_positions(1, P, N)
                 t.update_meshes(scene, [1])
@@ -279,7 +218,7 @@ def test_invalidation_is_update_meshes(hip):
 
 
 # ----------------------------------------------------------------------------- 6. refusals
-def test_refusals_change_nothing(rows, hip):
+def test_refusals_change_nothing(rows, dev):
     scene, camera, _ = teapot_scene()
     a = scene.arrays()
     box, tea = a["meshes"]
@@ -289,10 +228,10 @@ def test_refusals_change_nothing(rows, hip):
     before = rows.scene_arrays()
     L = rows._L
     P, PB = bend(tea["positions"]), np.ascontiguousarray(box["positions"])
-    dP, dB = DeviceArray(hip, P), DeviceArray(hip, PB)
+    dP, dB = on_device(dev, P), on_device(dev, PB)
     AUTO, HOST = prt_amd.MeshDeform.RADIUS_AUTO, prt_amd.MeshDeform.HOST
 
-    def de(mesh=1, count=len(P), pos=dP.value, normals=None, mode=KEEP, radius=0.0):
+    def de(mesh=1, count=len(P), pos=dP, normals=None, mode=KEEP, radius=0.0):
         d = prt_amd.MeshDeform()
         d.mesh, d.vertexCount, d.positions, d.normals, d.normalsMode, d.radius = mesh, count, pos, normals, mode, radius
         return d
@@ -301,40 +240,36 @@ def test_refusals_change_nothing(rows, hip):
            ([de(), de()], AUTO, "twice"), ([de(radius=-1.0)], 0, "radius"), ([de(radius=float("inf"))], 0, "radius"),
            ([de(radius=float("nan"))], 0, "radius"), ([], AUTO, "no mesh"),
            ([de(mode=3)], AUTO, "normalsMode"), ([de()], 4, "flag"), ([de()], AUTO | HOST | 8, "flag"),
-           ([de(mode=GIVEN)], AUTO, "NULL normals"), ([de(mode=KEEP, normals=dP.value)], AUTO, "normals must be NULL"),
-           ([de(mode=RECOMPUTE, normals=dP.value)], AUTO, "normals must be NULL"),
-           ([de(mesh=0, count=len(PB), pos=dB.value, normals=dB.value, mode=GIVEN)], AUTO, "without vertex normals"),
-           ([de(mesh=0, count=len(PB), pos=dB.value, mode=RECOMPUTE)], AUTO, "without vertex normals"),
+           ([de(mode=GIVEN)], AUTO, "NULL normals"), ([de(mode=KEEP, normals=dP)], AUTO, "normals must be NULL"),
+           ([de(mode=RECOMPUTE, normals=dP)], AUTO, "normals must be NULL"),
+           ([de(mesh=0, count=len(PB), pos=dB, normals=dB, mode=GIVEN)], AUTO, "without vertex normals"),
+           ([de(mesh=0, count=len(PB), pos=dB, mode=RECOMPUTE)], AUTO, "without vertex normals"),
            ([de(radius=1.0)], AUTO, "RADIUS_AUTO")]
+    for ds, flags, word in bad:
+        arr = (prt_amd.MeshDeform * max(len(ds), 1))(*ds)
+        assert L.prt_hip_deform_meshes(rows._ctx, len(ds), arr, flags, None) == EINVAL, word
+        assert word in L.prt_hip_last_error().decode(), (word, L.prt_hip_last_error().decode())
+    assert L.prt_hip_deform_meshes(rows._ctx, 1, None, AUTO, None) == EINVAL
+    assert (rows.accum_counts() == 8).all()  # a refused call does not even empty the accumulator
+    arrays_equal(rows.scene_arrays(), before, "after the refused calls")
+    with pytest.raises(prt_amd.PrtError, match=r"\(-5\)"):
+        rows.mesh_vertices(1)  # and no refused call counted as an update
+    with pytest.raises(prt_amd.PrtError, match=r"\(-2\)"):
+        rows.mesh_info(2)
+    fresh = prt_amd.PathTracer()
     try:
-        for ds, flags, word in bad:
-            arr = (prt_amd.MeshDeform * max(len(ds), 1))(*ds)
-            assert L.prt_hip_deform_meshes(rows._ctx, len(ds), arr, flags, None) == EINVAL, word
-            assert word in L.prt_hip_last_error().decode(), (word, L.prt_hip_last_error().decode())
-        assert L.prt_hip_deform_meshes(rows._ctx, 1, None, AUTO, None) == EINVAL
-        assert (rows.accum_counts() == 8).all()  # a refused call does not even empty the accumulator
-        arrays_equal(rows.scene_arrays(), before, "after the refused calls")
-        with pytest.raises(prt_amd.PrtError, match=r"\(-5\)"):
-            rows.mesh_vertices(1)  # and no refused call counted as an update
-        with pytest.raises(prt_amd.PrtError, match=r"\(-2\)"):
-            rows.mesh_info(2)
-        fresh = prt_amd.PathTracer()
-        try:
-            arr = (prt_amd.MeshDeform * 1)(de())
-            assert L.prt_hip_deform_meshes(fresh._ctx, 1, arr, AUTO, None) == ESTATE
-            assert L.prt_hip_get_mesh_vertices(fresh._ctx, 0, None, None, 0, None) == ESTATE
-            assert L.prt_hip_mesh_info(fresh._ctx, 0, C.byref(prt_amd.MeshInfo())) == ESTATE
-        finally:
-            fresh.close()
-        rows.deform_meshes([(1, dP.value, RECOMPUTE)])  # and the accepted call still works
-        assert rows.mesh_vertices(1)[0].tobytes() == P.tobytes()
+        arr = (prt_amd.MeshDeform * 1)(de())
+        assert L.prt_hip_deform_meshes(fresh._ctx, 1, arr, AUTO, None) == ESTATE
+        assert L.prt_hip_get_mesh_vertices(fresh._ctx, 0, None, None, 0, None) == ESTATE
+        assert L.prt_hip_mesh_info(fresh._ctx, 0, C.byref(prt_amd.MeshInfo())) == ESTATE
     finally:
-        dP.free()
-        dB.free()
+        fresh.close()
+    rows.deform_meshes([(1, dP, RECOMPUTE)])  # and the accepted call still works
+    assert rows.mesh_vertices(1)[0].tobytes() == P.tobytes()
 
 
 # ----------------------------------------------------------------------------- 7. the tree readout
-def test_mesh_info(rows, rows2, hip):
+def test_mesh_info(rows, rows2, dev):
     scene, camera, _ = teapot_scene()
     a = scene.arrays()
     tea = a["meshes"][1]
@@ -359,19 +294,15 @@ def test_mesh_info(rows, rows2, hip):
         assert all(np.asarray(first[k]).tobytes() == np.asarray(again[k]).tobytes() for k in first), "two calls return identical bits"
     at_upload = rows.mesh_info(1)["sahCost"]
     P = bend(tea["positions"])
-    dP, dBack = DeviceArray(hip, P), DeviceArray(hip, tea["positions"])
-    try:
-        rows.deform_meshes([(1, dP.value, RECOMPUTE)])
-        bent = rows.mesh_info(1)
-        check(bent, refit_nodes(tea["nodes"], tea["remap"], tea["indices"], P), "after the bend")
-        assert bent["sahCostAtUpload"] == at_upload and bent["sahCost"] > at_upload
-        assert rows.mesh_info(0)["sahCost"] == rows.mesh_info(0)["sahCostAtUpload"]  # the box did not move
-        rows.deform_meshes([(1, dBack.value, RECOMPUTE)])
-        back = rows.mesh_info(1)
-        assert back["sahCost"] == back["sahCostAtUpload"] == at_upload
-    finally:
-        dP.free()
-        dBack.free()
+    dP, dBack = on_device(dev, P), on_device(dev, tea["positions"])
+    rows.deform_meshes([(1, dP, RECOMPUTE)])
+    bent = rows.mesh_info(1)
+    check(bent, refit_nodes(tea["nodes"], tea["remap"], tea["indices"], P), "after the bend")
+    assert bent["sahCostAtUpload"] == at_upload and bent["sahCost"] > at_upload
+    assert rows.mesh_info(0)["sahCost"] == rows.mesh_info(0)["sahCostAtUpload"]  # the box did not move
+    rows.deform_meshes([(1, dBack, RECOMPUTE)])
+    back = rows.mesh_info(1)
+    assert back["sahCost"] == back["sahCostAtUpload"] == at_upload
     # a rigid move costs nothing: the refitted tree is the rebuilt one (tests/test_refit_cpu.py)
     name = "scale2"
     Pm = RIGID_MOVES[name](tea["positions"])

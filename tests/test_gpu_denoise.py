@@ -10,74 +10,11 @@ import pytest
 import prt_amd
 import prt_denoise_ref as R
 import prt_testlib as T
+from prt_denoise_ref import DEFAULTS
+from prt_gpukit import assert_bits_equal, bits, camera_of, synthetic_state
+from prt_gpukit import box_scene, dev, tracer  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-DEFAULTS = dict(iterations=5, normal_power_log2=5, sigma_luminance=4.0, sigma_albedo=0.1, demodulate=True)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_bits_equal(a, b, what=""):
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.nonzero(a != b)
-    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def box_scene():
-    return prt_amd.setup_cornell_box(64, 64)[0]
-
-
-def camera_of(width, height):
-    return prt_amd.setup_cornell_box(width, height)[1]
-
-
-def synthetic_state(width, height, seed):
-    """Random accumulator, moments and guides with every special case of the header in them: count 0, m < 2, miss normals, zero
-    variance, albedo 0, radiance from 1e-6 to 1e3 (HDR emitters next to dark walls)."""
-    rng = np.random.default_rng(seed)
-    shape = (height, width)
-    count = (rng.integers(1, 9, shape) * 8).astype(np.uint32)
-    count[rng.random(shape) < 0.15] = 0
-    count[0, 0] = 8  # (an import whose counts are all 0 leaves the accumulator empty, which is a refusal)
-    mean = (rng.random(shape + (3,)) * 10.0 ** rng.uniform(-6, 3, shape + (1,))).astype(np.float32)
-    total = (mean * count[..., None].astype(np.float32)).astype(np.float32)
-    m = np.minimum(rng.integers(0, 9, shape), count >> 3).astype(np.uint32)  # a share with m = 0 or 1: variance unknown
-    mom = np.zeros(shape + (4,), np.float32)
-    lum = R.lum(mean)
-    mom[..., 0] = lum
-    mom[..., 1] = (lum * lum * rng.random(shape) * 4.0).astype(np.float32)
-    mom[..., 1][rng.random(shape) < 0.1] = 0.0  # zero variance
-    mom[..., 2] = m.view(np.float32)
-    albedo = rng.random(shape + (3,)).astype(np.float32)
-    albedo[rng.random(shape) < 0.1] = 0.0
-    # guides that make regions, so that the weights are not all ~0: a few albedos and normals, blockwise, plus jitter
-    by, bx = np.meshgrid(np.arange(height) // 7, np.arange(width) // 5, indexing="ij")
-    palette = rng.random((8, 3)).astype(np.float32)
-    region = (by * 3 + bx) % 8
-    albedo = np.where(rng.random(shape)[..., None] < 0.7, palette[region] + rng.normal(0, 0.01, shape + (3,)).astype(np.float32), albedo)
-    albedo = np.abs(albedo).astype(np.float32)
-    albedo[rng.random(shape) < 0.05] = 0.0
-    n = rng.normal(size=(8, 3))
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    nn = n[(by + bx) % 8] + rng.normal(0, 0.05, shape + (3,))
-    nn *= rng.uniform(0.3, 1.0, shape + (1,)) / np.linalg.norm(nn, axis=-1, keepdims=True)  # averaged guide normals are short, never long
-    normal = (0.5 * nn + 0.5).astype(np.float32)
-    normal[rng.random(shape) < 0.1] = 0.0  # misses
-    state = dict(width=width, height=height, seed=12345, max_depth=14, rr_depth=4, rng=rng.integers(0, 2 ** 32, shape, dtype=np.uint32),
-                 sum=total, count=count)
-    return state, mom, albedo, normal
 
 
 def load_synthetic(t, scene, width, height, seed):
@@ -142,6 +79,7 @@ def rendered(t, scene, camera, adaptive, spp=64, step=16, **kw):
     return t.accum_export(), t.accum_export_moments()
 
 
+# (differs from prt_gpukit.c1_scene: 256 x 256)
 @pytest.fixture(scope="module")
 def c1_scene():
     return prt_amd.setup_cornell_box(256, 256, teapot_mesh=T.teapot_product_mesh())
@@ -258,26 +196,20 @@ def test_guides_go_stale(tracer, c1_scene):
     assert first[0].shape == (256, 256, 3)
 
 
-def test_explicit_target_on_a_callers_stream(tracer, box_scene):
+def test_explicit_target_on_a_callers_stream(tracer, box_scene, dev):
     s = load_synthetic(tracer, box_scene, 97, 61, seed=3)
     want, _ = R.denoise(s[0]["sum"], s[0]["count"], s[1], s[2], s[3], **DEFAULTS)
     tracer.accum_resolve(1.0)
     fb_before = np.zeros((61, 97, 3), np.float32)
     tracer._download(fb_before, 0, 0, 96, 60)
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
     nbytes = 61 * 97 * 3 * 4
-    stream, target = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
-    try:
-        assert hip.hipMemsetAsync(target, 0xff, C.c_size_t(nbytes), stream) == 0
-        tracer.denoise_async(d_rgb=target.value, stream=stream.value, **DEFAULTS)
-        got = np.zeros((61, 97, 3), np.float32)
-        # queued on the caller's stream only: the result must be there when that stream gets to the copy
-        assert hip.hipMemcpyAsync(got.ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        hip.hipFree(target)
-        hip.hipStreamDestroy(stream)
+    stream, target = dev.stream(), dev.alloc(nbytes)
+    dev.fill_async(target, 0xff, nbytes, stream)
+    tracer.denoise_async(d_rgb=target, stream=stream, **DEFAULTS)
+    got = np.zeros((61, 97, 3), np.float32)
+    # queued on the caller's stream only: the result must be there when that stream gets to the copy
+    dev.download_async(got, target, stream)
+    dev.synchronize(stream)
     assert_bits_equal(got, want, "caller's buffer")
     fb_after = np.zeros((61, 97, 3), np.float32)
     tracer._download(fb_after, 0, 0, 96, 60)

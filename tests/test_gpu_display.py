@@ -9,23 +9,13 @@ import pytest
 
 import prt_amd
 import prt_display_ref as R
-from test_display_cpu import BAD_FIELDS, assert_state_equal, frame
+from prt_display_ref import BAD_FIELDS, assert_state_equal, frame
+from prt_gpukit import camera_of, fetch
+from prt_gpukit import dev, tracer  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 P = prt_amd.DisplayParams.make
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-def camera_of(width, height):
-    return prt_amd.setup_cornell_box(width, height)[1]
 
 
 def ppm_block(tmp_path, img, tonemap):
@@ -56,63 +46,40 @@ def test_hostile_image_in_every_combination(tracer, tmp_path):
     assert np.array_equal(got, prt_amd.display_host(img, p)[0][1:36, 2:60])
 
 
-class DeviceBuffer:
-    def __init__(self, nbytes):
-        self.hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-        self.ptr, self.nbytes = C.c_void_p(), nbytes
-        assert self.hip.hipMalloc(C.byref(self.ptr), C.c_size_t(nbytes)) == 0
-
-    def fill(self, byte):
-        assert self.hip.hipMemset(self.ptr, byte, C.c_size_t(self.nbytes)) == 0
-
-    def read(self, shape, dtype=np.uint8):
-        out = np.zeros(shape, dtype)
-        assert out.nbytes == self.nbytes and self.hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), self.ptr, C.c_size_t(self.nbytes), 2) == 0
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
-
-
 @pytest.mark.parametrize("fmt", [0, 1, 2])
-def test_rectangles_into_a_callers_buffer(tracer, fmt):
+def test_rectangles_into_a_callers_buffer(tracer, dev, fmt):
     """Rectangles (3,5)-(57,30), a 1 x 1 and the full image into a caller's d_out prefilled with 0xA5: the bytes outside the rectangle
     stay, and the meter covers the rectangle only."""
     img = R.hostile_image()
     tracer.set_camera(camera_of(61, 37))
     tracer.upload_image(img)
     p = P(tonemap=1, transfer=1, format=fmt, meter=True, gain=1.25, adapt_rate=1.0)
-    buf = DeviceBuffer(61 * 37 * p.bpp)
-    try:
-        for rect in ((3, 5, 57, 30), (17, 9, 17, 9), (0, 0, 60, 36)):
-            buf.fill(0xA5)
-            tracer.display_reset()
-            tracer.display_async(p, *rect, d_out=buf.ptr.value)
-            st = tracer.display_state()
-            got = buf.read((37, 61, p.bpp))
-            want, ws = prt_amd.display_host(img, p, x0=rect[0], y0=rect[1], x1=rect[2], y1=rect[3], out=np.full((37, 61, p.bpp), 0xA5, np.uint8))
-            assert np.array_equal(got, want), (rect, int((got != want).sum()))
-            assert_state_equal(st, ws.as_dict(), str(rect))
-            assert st["metered"] + st["ignored"] == (rect[2] - rect[0] + 1) * (rect[3] - rect[1] + 1)
-            outside = np.ones((37, 61), bool)
-            outside[rect[1]:rect[3] + 1, rect[0]:rect[2] + 1] = False
-            assert (got[outside] == 0xA5).all()
-        # a d_out that is only 4-byte (RGB8: 1-byte) aligned: the scalar path alone, same bytes
-        shifted = DeviceBuffer(61 * 37 * p.bpp + 4)
-        try:
-            q = P(tonemap=0, transfer=0, format=fmt, gain=1.0)
-            tracer.display_async(q, d_out=shifted.ptr.value + (1 if fmt == 0 else 4))
-            tracer.display_state()  # synchronises
-            raw = shifted.read((61 * 37 * p.bpp + 4,))
-            off = 1 if fmt == 0 else 4
-            assert np.array_equal(raw[off:off + 61 * 37 * p.bpp].reshape(37, 61, p.bpp), prt_amd.display_host(img, q)[0])
-        finally:
-            shifted.free()
-    finally:
-        buf.free()
+    nbytes = 61 * 37 * p.bpp
+    buf = dev.alloc(nbytes)
+    for rect in ((3, 5, 57, 30), (17, 9, 17, 9), (0, 0, 60, 36)):
+        dev.fill(buf, 0xA5, nbytes)
+        tracer.display_reset()
+        tracer.display_async(p, *rect, d_out=buf)
+        st = tracer.display_state()
+        got = fetch(dev, buf, nbytes, np.uint8).reshape(37, 61, p.bpp)
+        want, ws = prt_amd.display_host(img, p, x0=rect[0], y0=rect[1], x1=rect[2], y1=rect[3], out=np.full((37, 61, p.bpp), 0xA5, np.uint8))
+        assert np.array_equal(got, want), (rect, int((got != want).sum()))
+        assert_state_equal(st, ws.as_dict(), str(rect))
+        assert st["metered"] + st["ignored"] == (rect[2] - rect[0] + 1) * (rect[3] - rect[1] + 1)
+        outside = np.ones((37, 61), bool)
+        outside[rect[1]:rect[3] + 1, rect[0]:rect[2] + 1] = False
+        assert (got[outside] == 0xA5).all()
+    # a d_out that is only 4-byte (RGB8: 1-byte) aligned: the scalar path alone, same bytes
+    shifted = dev.alloc(nbytes + 4)
+    q = P(tonemap=0, transfer=0, format=fmt, gain=1.0)
+    tracer.display_async(q, d_out=shifted + (1 if fmt == 0 else 4))
+    tracer.display_state()  # synchronises
+    raw = fetch(dev, shifted, nbytes + 4, np.uint8)
+    off = 1 if fmt == 0 else 4
+    assert np.array_equal(raw[off:off + 61 * 37 * p.bpp].reshape(37, 61, p.bpp), prt_amd.display_host(img, q)[0])
 
 
-def test_callers_image_and_stream_behind_a_queued_render(tracer, tmp_path):
+def test_callers_image_and_stream_behind_a_queued_render(tracer, dev, tmp_path):
     """A render into the caller's image on the caller's stream, then the display of that image on the same stream, then the copy: all
     three queued before anything is waited for."""
     scene, camera, exposure = prt_amd.setup_cornell_box(48, 40)
@@ -121,22 +88,15 @@ def test_callers_image_and_stream_behind_a_queued_render(tracer, tmp_path):
     want_rgb = tracer.render(8, exposure=exposure)
     p = P(tonemap=1, transfer=0, format=0, gain=1.0)
     fb_display_before = tracer.display(p)
-    hip = C.CDLL("libamdhip64.so")
-    stream = C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    rgb, out = DeviceBuffer(48 * 40 * 12), DeviceBuffer(48 * 40 * 3)
-    try:
-        assert hip.hipMemsetAsync(rgb.ptr, 0, C.c_size_t(rgb.nbytes), stream) == 0
-        assert hip.hipMemsetAsync(out.ptr, 0xA5, C.c_size_t(out.nbytes), stream) == 0
-        tracer.render_async(0, 0, 47, 39, 8, d_rgb=rgb.ptr.value, stream=stream.value, exposure=exposure)
-        tracer.display_async(p, d_rgb=rgb.ptr.value, d_out=out.ptr.value, stream=stream.value)
-        got = np.zeros((40, 48, 3), np.uint8)
-        assert hip.hipMemcpyAsync(got.ctypes.data_as(C.c_void_p), out.ptr, C.c_size_t(out.nbytes), 2, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        rgb.free()
-        out.free()
-        hip.hipStreamDestroy(stream)
+    stream = dev.stream()
+    rgb, out = dev.alloc(48 * 40 * 12), dev.alloc(48 * 40 * 3)
+    dev.fill_async(rgb, 0, 48 * 40 * 12, stream)
+    dev.fill_async(out, 0xA5, 48 * 40 * 3, stream)
+    tracer.render_async(0, 0, 47, 39, 8, d_rgb=rgb, stream=stream, exposure=exposure)
+    tracer.display_async(p, d_rgb=rgb, d_out=out, stream=stream)
+    got = np.zeros((40, 48, 3), np.uint8)
+    dev.download_async(got, out, stream)
+    dev.synchronize(stream)
     tracer.stats()
     assert np.array_equal(got, ppm_block(tmp_path, want_rgb, True))
     assert np.array_equal(got, fb_display_before)  # (the framebuffer held the same render)

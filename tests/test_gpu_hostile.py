@@ -11,7 +11,9 @@ import pytest
 import prt_amd
 import prt_hostile as H
 import prt_testlib as T
-from test_gpu_parity import _assert_same_tree, _host_bvh, assert_bits_equal
+from prt_gpucases import _assert_same_tree, _host_bvh
+from prt_gpukit import assert_bits_equal
+from prt_gpukit import gpu_event_accounting, rows, rows2  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -22,34 +24,11 @@ LIGHT = {"grid": (0.0, 1.0, 0.0), "twins": (0.0, 1.0, 0.0), "flat": (0.0, 0.0, 1
 CASES = [(name, seed) for name in H.SCENES for seed in H.SEEDS]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def gpu_event_accounting():
-    """As in test_gpu_parity.py: the oracle counts an occlusion query's events along the GPU's near-first visit."""
-    T.oracle().orc_set_anyhit_accounting(1)
-    yield
-    T.oracle().orc_set_anyhit_accounting(0)
-
-
+# (differs from prt_gpukit.tracer: max_depth=8)
 @pytest.fixture(scope="module")
 def tracer():
     prt_amd.build()
     t = prt_amd.PathTracer(max_depth=8)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows2():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
     yield t
     t.close()
 

@@ -16,8 +16,10 @@ import pytest
 
 import prt_hostile_shade as S
 import prt_testlib as T
-from test_gpu_shadow_skip import assert_same_image, check_scene, upload
-from test_gpu_shadow_skip import gpu_event_accounting, tracer  # noqa: F401  (fixtures: the oracle's any-hit accounting, a test-build context)
+from prt_gpucases import check_scene
+from prt_gpukit import assert_same_image, upload
+from prt_gpukit import gpu_event_accounting  # noqa: F401  (fixture: the oracle's any-hit accounting)
+from prt_gpukit import rows as tracer  # noqa: F401  (fixture: this module's tracer is a context of the test build)
 
 pytestmark = pytest.mark.gpu
 DEPTH = 14  # the reference's literal

@@ -26,8 +26,10 @@ import prt_display_ref as D
 import prt_hostile_shade as S
 import prt_hostile_state as HS
 import prt_temporal_ref as TR
-from test_display_cpu import assert_state_equal
-from test_gpu_temporal import PARAMETER_SETS
+from prt_display_ref import assert_state_equal
+from prt_gpukit import camera_of
+from prt_gpukit import box_scene  # noqa: F401  (fixtures)
+from prt_temporal_ref import PARAMETER_SETS
 
 pytestmark = pytest.mark.gpu
 F, U32 = np.float32, np.uint32
@@ -36,21 +38,13 @@ POWERS = (0, 5, 7)
 SEED = 1
 
 
+# (differs from prt_gpukit.tracer: every test runs on the product build and on the test build)
 @pytest.fixture(scope="module", params=["product", "test"])
 def tracer(request):
     prt_amd.build()
     t = prt_amd.PathTracer(test_entry_points=request.param == "test")
     yield t
     t.close()
-
-
-@pytest.fixture(scope="module")
-def box_scene():
-    return prt_amd.setup_cornell_box(64, 64)[0]
-
-
-def camera_of(width, height):
-    return prt_amd.setup_cornell_box(width, height)[1]
 
 
 def state_args(s):

@@ -9,7 +9,7 @@ import pytest
 import prt_amd
 import prt_hostile_taps as H
 import prt_testlib as T
-from test_gpu_parity import assert_bits_equal
+from prt_gpukit import assert_bits_equal, snapped_scene
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -17,6 +17,7 @@ TAP_WORDS = slice(0, 9)      # sample3, sample1, alpha single, alpha packet, sam
 SURFACE_WORDS = slice(0, 19)  # normal, uv, material, duv01, duv02, dp01, dp02, sampleBump's normal
 
 
+# (differs from prt_gpukit.rows: the golden scene is uploaded, and the fixture is (context, golden arrays))
 @pytest.fixture(scope="module")
 def rows():
     prt_amd.build()
@@ -79,28 +80,6 @@ def test_entries_refuse_what_would_read_outside_the_scene(rows):
     for rec in ([4, 0, 0, 0, 0], [1, 20, 0, 0, 0]):
         with pytest.raises(prt_amd.PrtError):
             t.test_surface(np.array([rec], dtype=np.uint32))
-
-
-def snapped_scene(z, width=64, height=48):
-    """Two quads seen head-on from (0, 0, 3): an alpha-masked one (the 16 x 16 block map, texcoords on texel edges from -1 to 2: three
-    wraps) in z = 0 and a bump-mapped, textured one (the 3 x 5 maps, texcoords on texel edges) in z = -1 that catches its shadow."""
-    tex = H.golden_maps(z)
-    names = [n for n, _ in tex]
-    a, g, c = names.index("b4_16x16"), names.index("g1_3x5"), names.index("n4_3x5")
-    mats = np.array([T.make_material(diffuse=(0.9, 0.8, 0.7), alpha_test=1, diffuse_map=a),
-                     T.make_material(diffuse=(1.0, 1.0, 1.0), diffuse_map=c, bump_map=g)], dtype=T.MATERIAL_DTYPE)
-
-    def quad(half, zpos, t0, t1):
-        pos = np.array([[-half, -half, zpos], [half, -half, zpos], [half, half, zpos], [-half, half, zpos]], dtype=F)
-        tc = np.array([[t0, t0], [t1, t0], [t1, t1], [t0, t1]], dtype=F)
-        return pos, tc
-    p0, t0 = quad(1.0, 0.0, -1.0, 2.0)
-    p1, t1 = quad(2.5, -1.0, -2.0 / 3.0, 5.0 / 3.0)
-    pos, tc = np.concatenate([p0, p1]), np.concatenate([t0, t1])
-    idx = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7]], dtype=np.uint32)
-    mesh = T.MeshDesc(idx, pos, np.array([0, 0, 1, 1], dtype=np.uint32), mats, texcoords=tc)
-    return T.SceneDesc([mesh], cam_pos=(0.0, 0.0, 3.0), cam_dir=(0.0, 0.0, -1.0), width=width, height=height,
-                       light=((0.0, 0.0, 1.0), (3.0, 3.0, 2.5)), textures=[t for _, t in tex])
 
 
 @pytest.mark.parametrize("count_traffic", [False, True], ids=["timed", "counting"])

@@ -13,20 +13,13 @@ import pytest
 import prt_amd
 import prt_hostile as H
 import prt_testlib as T
+from prt_gpukit import rows  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 MODES = ((0, "single"), (1, "packet"), (2, "occluded_single"), (3, "occluded_packet"))
 FAR = 1e5
 PITCH = 4.0  # distance of the meshes' columns along x
-
-
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
 
 
 def stack(m, k, rng):
@@ -170,7 +163,7 @@ def test_alpha_tested_leaf(rows, tmp_path):
     test_gpu_parity.py::test_alpha_cell_classes_at_the_threshold_bytes) beside a plain leaf of 3: candidates of the alpha leaf are
     accepted or rejected by the pair's lane before the owners read the ballot, so a ray passes through the holes of the nearer
     triangles and stops at the first opaque texel."""
-    from test_host_cpu import _png
+    from prt_images import _png
     rng = np.random.default_rng(7300)
     td = str(tmp_path)
     vals = np.array([0, 126, 127, 128, 255], dtype=np.uint8)

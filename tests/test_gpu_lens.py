@@ -13,6 +13,8 @@ import prt_bake_ref as BR
 import prt_hostile_shade as HS
 import prt_lens_ref as LR
 import prt_probe_ref as PR
+from prt_gpukit import SCENES, SENTINEL, TAIL, fetch, ptr, sentinel, stage_tracers
+from prt_gpukit import dev  # noqa: F401  (fixture: device memory and streams for one test)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -22,73 +24,8 @@ SPP = 8
 W, H = 13, 7            # 91 pixels: no multiple of 64, so the last wave of either kernel is partial
 BANDS = ((0, 7), (2, 5), (6, 7))
 BLOCKS_PER_CU = 8       # PRT_LENS_BLOCKS_PER_CU (prt_lens.hip): blocks of 256 lanes either kernel is launched with at the most
-SENTINEL = 0xffc0bad1   # a NaN no kernel here produces
-TAIL = 16               # sentinel words behind every output
-H2D, D2H = 1, 2
 HOST = prt_amd.QUERY_HOST
-
-
-def sky_stage():
-    s, cam = HS.scene("plain", light=None)
-    s.set_infinite_area_light(HS.sky())
-    return s, cam
-
-
-SCENES = {"plain": lambda: HS.scene("plain"), "sky": sky_stage, "box_rr": lambda: HS.scene("box_rr")}
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipFree.argtypes = [C.c_void_p]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    h.hipStreamDestroy.argtypes = [C.c_void_p]
-    return h
-
-
-class Dev:
-    """A numpy array's bytes in device memory (hipMalloc), 16-byte aligned."""
-
-    def __init__(self, hip, a):
-        self.hip, self.ptr, self.nbytes = hip, C.c_void_p(), a.nbytes
-        assert hip.hipMalloc(C.byref(self.ptr), max(a.nbytes, 64)) == 0 and self.ptr.value % 16 == 0
-        assert hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, H2D) == 0
-
-    def get(self, dtype):
-        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, D2H) == 0
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
-
-
-@pytest.fixture(scope="module")
-def tracers():
-    """Per stage a PathTracer with the scene uploaded and no camera; "none": a context without a scene."""
-    prt_amd.build()
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = prt_amd.PathTracer(max_depth=DEPTH)
-            if name != "none":
-                made[name].upload_scene(SCENES[name]()[0])
-        return made[name]
-    yield get
-    for t in made.values():
-        t.close()
-
-
-def sentinel(words):
-    return np.full(words, SENTINEL, dtype=U)
-
-
-def ptr(a):
-    return a if a is None or isinstance(a, int) else a.ctypes.data
+tracers = stage_tracers(SCENES, max_depth=DEPTH)
 
 
 def make_lens(kind, K=3, box=False, **kw):
@@ -108,20 +45,17 @@ def make_lens(kind, K=3, box=False, **kw):
 
 
 # ----------------------------------------------------------------------------- 1. rays
-def run_rays(t, hip, lens, y0, y1, device):
+def run_rays(t, dev, lens, y0, y1, device):
     """prt_hip_lens_rays on host or device arrays: the rays of the band followed by the sentinel words."""
     out = sentinel((y1 - y0) * lens.width * lens.K * 8 + TAIL)
     if not device:
         rc = t._L.prt_hip_lens_rays(t._ctx, C.byref(lens), y0, y1, ptr(out), HOST, None)
         assert rc == 0, t._L.prt_hip_last_error()
         return out
-    buf = Dev(hip, out)
-    try:
-        rc = t._L.prt_hip_lens_rays(t._ctx, C.byref(lens), y0, y1, buf.ptr, 0, None)
-        assert rc == 0, t._L.prt_hip_last_error()
-        return buf.get(U)  # (hipMemcpy on the null stream: behind the context's blocking stream)
-    finally:
-        buf.free()
+    d_out = dev.upload(out)
+    rc = t._L.prt_hip_lens_rays(t._ctx, C.byref(lens), y0, y1, d_out, 0, None)
+    assert rc == 0, t._L.prt_hip_last_error()
+    return fetch(dev, d_out, out.size)
 
 
 def check_rays(got, lens, y0, y1, what):
@@ -134,17 +68,17 @@ def check_rays(got, lens, y0, y1, what):
 
 @pytest.mark.parametrize("K", [1, 3, 64])
 @pytest.mark.parametrize("kind", ["pinhole", "thin", "ortho", "equirect", "fisheye"])
-def test_rays_equal_the_restatement(tracers, hip, kind, K):
+def test_rays_equal_the_restatement(tracers, dev, kind, K):
     t = tracers("none")  # prt_hip_lens_rays needs no scene
     for p in (0, 5):
         for flags in (0, LR.CENTRE):
             lens = make_lens(kind, K, pass_=p, flags=flags)
             for y0, y1 in BANDS:
                 what = f"{kind} K={K} pass={p} flags={flags} rows [{y0}, {y1})"
-                host = run_rays(t, hip, lens, y0, y1, device=False)
+                host = run_rays(t, dev, lens, y0, y1, device=False)
                 assert check_rays(host, lens, y0, y1, what + ", host arrays") == 0
-                dev = run_rays(t, hip, lens, y0, y1, device=True)
-                assert dev.tobytes() == host.tobytes(), what + ": device and host pointers give different bytes"
+                on_device = run_rays(t, dev, lens, y0, y1, device=True)
+                assert on_device.tobytes() == host.tobytes(), what + ": device and host pointers give different bytes"
 
 
 def hostile_lenses():
@@ -166,29 +100,30 @@ def hostile_lenses():
     return out
 
 
-def test_hostile_records_give_what_the_arithmetic_gives(tracers, hip):
+def test_hostile_records_give_what_the_arithmetic_gives(tracers, dev):
     t = tracers("none")
     nans = 0
     for what, lens in hostile_lenses():
-        got = run_rays(t, hip, lens, 0, H, device=False)
+        got = run_rays(t, dev, lens, 0, H, device=False)
         n = check_rays(got, lens, 0, H, what)
         print(f"{what}: {n} NaN words")
         nans += n
     assert nans > 0
 
 
-def test_rays_beyond_one_trip_of_the_grid_stride_loop(tracers, hip):
+def test_rays_beyond_one_trip_of_the_grid_stride_loop(tracers, dev):
     """256 x 256 with K = 9: 589 824 rays, more than the 8 blocks of 256 lanes per CU cover in one trip.  Rays only: nothing is traced.
     (A jittered pinhole: the restatement's sinf and cosf go through ctypes one value at a time.)"""
     t = tracers("none")
     lens = prt_amd.lens_pinhole((0.1, 1.2, 3.0), (0.0, 0.4, 0.0), (0.0, 1.0, 0.0), 0.9, 256, 256, K=9, jitter_seed=3, pass_=2)
     one_trip = t.device_info()[1] * BLOCKS_PER_CU * 256
     assert 256 * 256 * 9 > one_trip + 256
-    got = run_rays(t, hip, lens, 0, 256, device=True)
+    got = run_rays(t, dev, lens, 0, 256, device=True)
     check_rays(got, lens, 0, 256, "256 x 256 x 9")
 
 
 # ----------------------------------------------------------------------------- 2. accumulate
+# (differs from test_gpu_bake.py's: +-0, infinities of both signs and a sum that depends on its order, each in a pixel of its own)
 def synthetic_radiance(n, K, seed=3):
     """(n*K, 3): ordinary values, +-0, infinities of both signs, NaN and 1e-45, each in pixels of its own; one pixel whose sum depends on
     its order."""
@@ -206,25 +141,21 @@ def synthetic_radiance(n, K, seed=3):
     return L.reshape(n * K, 3)
 
 
-def run_accumulate(t, hip, lens, y0, y1, L, prior, device):
+def run_accumulate(t, dev, lens, y0, y1, L, prior, device):
     """prt_hip_lens_accumulate over `prior` (the whole image), followed by sentinel words."""
     img = np.concatenate([prior.view(U).reshape(-1), sentinel(TAIL)])
     if not device:
         rc = t._L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), y0, y1, ptr(L), ptr(img), HOST, None)
         assert rc == 0, t._L.prt_hip_last_error()
         return img
-    bufs = [Dev(hip, L), Dev(hip, img)]
-    try:
-        rc = t._L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), y0, y1, bufs[0].ptr, bufs[1].ptr, 0, None)
-        assert rc == 0, t._L.prt_hip_last_error()
-        return bufs[1].get(U)
-    finally:
-        for b in bufs:
-            b.free()
+    d_L, d_img = dev.upload(L), dev.upload(img)
+    rc = t._L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), y0, y1, d_L, d_img, 0, None)
+    assert rc == 0, t._L.prt_hip_last_error()
+    return fetch(dev, d_img, img.size)
 
 
 @pytest.mark.parametrize("K", [1, 3, 64])
-def test_accumulate_equals_the_restatement(tracers, hip, K):
+def test_accumulate_equals_the_restatement(tracers, dev, K):
     t = tracers("none")
     prior = np.random.default_rng(8).normal(size=(H, W, 3)).astype(F)
     prior[2, 4] = (np.inf, -0.0, np.nan)
@@ -238,14 +169,14 @@ def test_accumulate_equals_the_restatement(tracers, hip, K):
             assert np.isnan(want[y0, 5, 1]) and want[y0, 6, 0] == np.inf and (K == 1 or np.isnan(want[y0, 7, 0]))
             if not flags:
                 assert want[y0, 3].tobytes() == np.zeros(3, F).tobytes(), "S starts at +0"
-            host = run_accumulate(t, hip, lens, y0, y1, L, prior, device=False)
+            host = run_accumulate(t, dev, lens, y0, y1, L, prior, device=False)
             words = H * W * 3
             BR.same_bytes(host[:words], want, what + ", host arrays")
             assert (host[words:] == SENTINEL).all(), "words behind the image were written"
             rows = host[:words].reshape(H, W * 3)
             assert rows[:y0].tobytes() == prior[:y0].tobytes() and rows[y1:].tobytes() == prior[y1:].tobytes(), "rows outside the band"
-            dev = run_accumulate(t, hip, lens, y0, y1, L, prior, device=True)
-            assert dev.tobytes() == host.tobytes(), what + ": device and host pointers give different bytes"
+            on_device = run_accumulate(t, dev, lens, y0, y1, L, prior, device=True)
+            assert on_device.tobytes() == host.tobytes(), what + ": device and host pointers give different bytes"
     # the Python wrapper is the same call
     lens = make_lens("pinhole", K, flags=LR.ACCUMULATE)
     L = synthetic_radiance(3 * W, K)
@@ -356,7 +287,7 @@ def test_a_lens_render_leaves_the_context_alone():
 
 
 # ----------------------------------------------------------------------------- 5. refusals and state
-def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
+def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, dev):
     t, bare = tracers("plain"), tracers("none")
     L = t._L
     lens = make_lens("pinhole", 3)
@@ -365,7 +296,7 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
     # without a scene: the render is refused, the two halves work
     rc, out = run_render(bare, lens, 1)
     assert rc == -5 and b"upload a scene" in bare._L.prt_hip_last_error() and (out == SENTINEL).all()
-    check_rays(run_rays(bare, hip, lens, 0, H, device=False), lens, 0, H, "without a scene")
+    check_rays(run_rays(bare, dev, lens, 0, H, device=False), lens, 0, H, "without a scene")
     img = bare.lens_accumulate(lens, rad + F(1))
     assert (img == 3).all()
     # the record and the flags: all three calls
@@ -398,17 +329,13 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
     for kw in (dict(use_lens=False), dict(use_params=False), dict(use_image=False)):
         assert run_render(t, lens, 1, image=outs["render"], **kw)[0] == -2, kw
     # device pointers that are not aligned
-    d = Dev(hip, np.zeros(1 << 16, np.uint8))
-    try:
-        base = d.ptr.value
-        p = t.params(SPP, max_depth=DEPTH)
-        assert L.prt_hip_lens_rays(t._ctx, C.byref(lens), 0, H, base + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), 0, H, base + 2, base + 32768, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        assert L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), 0, H, base, base + 32768 + 1, 0, None) == -2
-        assert L.prt_hip_lens_render(t._ctx, C.byref(lens), C.byref(p), base + 2, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        assert not d.get(np.uint8).any(), "a refused call wrote device memory"
-    finally:
-        d.free()
+    base = dev.upload(np.zeros(1 << 16, np.uint8))
+    p = t.params(SPP, max_depth=DEPTH)
+    assert L.prt_hip_lens_rays(t._ctx, C.byref(lens), 0, H, base + 8, 0, None) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), 0, H, base + 2, base + 32768, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
+    assert L.prt_hip_lens_accumulate(t._ctx, C.byref(lens), 0, H, base, base + 32768 + 1, 0, None) == -2
+    assert L.prt_hip_lens_render(t._ctx, C.byref(lens), C.byref(p), base + 2, 0, None) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
+    assert not fetch(dev, base, 1 << 16, np.uint8).any(), "a refused call wrote device memory"
     assert t.stats()["kernelLaunches"] == 0
     for k, o in outs.items():
         assert (o == SENTINEL).all(), f"a refused {k} call wrote its output"
@@ -417,7 +344,7 @@ def test_refusals_queue_nothing_and_leave_the_outputs_untouched(tracers, hip):
 
 
 # ----------------------------------------------------------------------------- 6. a caller's stream
-def test_device_memory_on_a_callers_stream_with_copies_around(tracers, hip):
+def test_device_memory_on_a_callers_stream_with_copies_around(tracers, dev):
     """The prior image arrives on the caller's stream, the accumulating render is queued behind it and a device copy of the answer
     behind the render: the answer must hold prior + render, so the call waited for the first copy and the second waited for it."""
     t = tracers("sky")
@@ -426,22 +353,15 @@ def test_device_memory_on_a_callers_stream_with_copies_around(tracers, hip):
     prior = np.concatenate([np.random.default_rng(9).normal(size=words).astype(F).view(U), sentinel(TAIL)])
     rc, want = run_render(t, lens, seed, image=prior.copy())
     assert rc == 0
-    stream = C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    bufs = [Dev(hip, np.zeros_like(prior)), Dev(hip, sentinel(words + TAIL))]
+    stream = dev.stream()
+    d_image, d_copy = dev.upload(np.zeros_like(prior)), dev.upload(sentinel(words + TAIL))
     got = np.zeros(words + TAIL, U)
-    try:
-        d_image, d_copy = (b.ptr.value for b in bufs)
-        assert hip.hipMemcpyAsync(d_image, prior.ctypes.data, prior.nbytes, H2D, stream) == 0
-        t.stats()
-        t.render_lens_async(lens, d_image, SPP, seed=seed, stream=stream.value)
-        assert hip.hipMemcpyAsync(d_copy, d_image, (words + TAIL) * 4, 3, stream) == 0  # device to device
-        assert hip.hipMemcpyAsync(got.ctypes.data, d_copy, (words + TAIL) * 4, D2H, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        for b in bufs:
-            b.free()
-        hip.hipStreamDestroy(stream)
+    dev.upload_async(prior, stream, d_image)
+    t.stats()
+    t.render_lens_async(lens, d_image, SPP, seed=seed, stream=stream)
+    dev.copy_async(d_copy, d_image, (words + TAIL) * 4, stream)
+    dev.download_async(got, d_copy, stream)
+    dev.synchronize(stream)
     assert got.tobytes() == want.tobytes()
     st = t.stats()
     assert st["kernelLaunches"] == 3 and st["nPx"] == 1 * W * 3

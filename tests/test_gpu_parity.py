@@ -11,47 +11,12 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_gpucases import _assert_same_tree, _host_bvh
+from prt_gpukit import assert_bits_equal, bits, upload
+from prt_gpukit import gpu_event_accounting, rows, tracer  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 G = T.GOLDEN
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_bits_equal(a, b, what=""):
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.nonzero(a != b)
-    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def gpu_event_accounting():
-    """The oracle's nBox/nTri/nTap for occlusion queries follow the GPU's near-first visit in this module (the images
-    and ray counts are the reference traversal's either way; the oracle aborts if the two visits ever disagree)."""
-    T.oracle().orc_set_anyhit_accounting(1)
-    yield
-    T.oracle().orc_set_anyhit_accounting(0)
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows():
-    """A context of the TEST build of the library (libprt_hip_test.so: the product's sources + the row-level entry points
-    of include/prt_hip_test.h).  Whole-image tests run on `tracer`, the product library."""
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
 
 
 @pytest.fixture(scope="module")
@@ -60,11 +25,6 @@ def c1(tracer):
     scene, camera, exposure = prt_amd.setup_cornell_box(512, 512, teapot_mesh=T.teapot_product_mesh())
     desc = T.scene_desc_from_product(scene, camera, exposure)
     return scene, camera, desc
-
-
-def upload(tracer, scene, camera):
-    tracer.upload_scene(scene)
-    tracer.set_camera(camera)
 
 
 # ----------------------------------------------------------------------------- leaf rows (a3, a4, a10, box tests)
@@ -623,29 +583,6 @@ def test_single_process_gather_of_several_contexts(tracer, c1):
             t.close()
 
 
-def _host_bvh(idx, pos):
-    import ctypes as C
-    L = prt_amd.lib()
-    n = len(idx)
-    nodes_p, cnt, remap_p = C.POINTER(prt_amd.BvhNode)(), C.c_uint32(), C.POINTER(C.c_uint32)()
-    assert L.prt_host_bvh_build(n, idx.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p), 0, C.byref(nodes_p), C.byref(cnt),
-                                C.byref(remap_p)) == 0
-    nodes = np.frombuffer(C.string_at(nodes_p, cnt.value * C.sizeof(prt_amd.BvhNode)), dtype=T.NODE_DTYPE).copy()
-    remap = np.ctypeslib.as_array(remap_p, shape=(n,)).copy()
-    L.prt_host_free(nodes_p)
-    L.prt_host_free(remap_p)
-    return nodes, remap
-
-
-def _assert_same_tree(nodes, remap, ref_nodes, ref_remap, what):
-    assert len(nodes) == len(ref_nodes), (what, len(nodes), len(ref_nodes))
-    for f in ("primOrSecondNodeIndex", "triVectorIndex", "primCount", "splitAxis"):
-        assert (nodes[f] == ref_nodes[f]).all(), (what, f, int(np.argmax(nodes[f] != ref_nodes[f])))
-    # bounds: equal as floats (the min / max of the same vertices; only the sign of a zero bound can depend on the merge order)
-    assert np.array_equal(nodes["lower"], ref_nodes["lower"]) and np.array_equal(nodes["upper"], ref_nodes["upper"]), what
-    assert (remap == ref_remap).all(), what
-
-
 @pytest.mark.parametrize("n,seed", [(1, 0), (8, 1), (9, 2), (300, 3), (5000, 4), (70000, 5)])
 def test_gpu_bvh_build_matches_host_builder_on_soups(tracer, n, seed):
     """prt_hip_build_bvh (level-parallel binned SAH on the device) produces the node array, leaf order and
@@ -731,7 +668,7 @@ def test_alpha_cell_classes_at_the_threshold_bytes(tracer, tmp_path, seed):
     or straddle 126 / 128, are hit by thousands of candidates; uv inside and far outside [0, 1]; scatter, packet-occlusion and
     single-occlusion rays (directional light).  Image and ray counts equal the oracle's bit for bit, in the timed build (the cell
     classes) and in the counting build (the serial leaf form: the blend every time)."""
-    from test_host_cpu import _png
+    from prt_images import _png
     rng = np.random.default_rng(9100 + seed)
     td = str(tmp_path)
     bw, bh = int(rng.integers(5, 9)), int(rng.integers(4, 8))
@@ -790,7 +727,7 @@ def test_textured_obj_scenes_through_the_asset_loaders(tracer, tmp_path, seed):
     scene: images, ray counts and every event counter (texture taps included) in the counting build, the timed build's image,
     and the three G-buffer kinds.  (The decoders themselves are pinned by the CPU suite; what this adds is that loader output --
     texel layout, alpha flags, per-triangle materials, bump records -- is what the device scene expects.)"""
-    from test_host_cpu import _png, _tga
+    from prt_images import _png, _tga
     rng = np.random.default_rng(70000 + seed)
     td = str(tmp_path)
 

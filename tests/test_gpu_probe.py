@@ -13,6 +13,7 @@ import prt_amd
 import prt_hostile_shade as HS
 import prt_probe_ref as PR
 import prt_testlib as T
+from prt_gpukit import SCENES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -20,16 +21,6 @@ DEPTH = 8
 POOL_GROUPS = 16 * 64   # PRT_POOL_CHUNKS rows of PRT_CHUNK pixel groups per workgroup (prt_frame.h)
 BLOCKS_PER_CU = 2       # a workgroup of the frame kernel holds 78 576 B of the CU's 160 KB of LDS
 UNWRITTEN = 0xffc0bad1  # a NaN no probe produces: the scenes here hold no NaN, and arithmetic gives the default NaN
-
-
-def sky_stage():
-    """The plain stage lit by prt_hostile_shade.sky() instead of its sun: the ENV instantiation."""
-    s, cam = HS.scene("plain", light=None)
-    s.set_infinite_area_light(HS.sky())
-    return s, cam
-
-
-SCENES = {"plain": lambda: HS.scene("plain"), "sky": sky_stage, "box_rr": lambda: HS.scene("box_rr")}
 
 
 class Case:
@@ -286,16 +277,10 @@ def test_refusals_launch_nothing_and_a_camera_is_not_needed():
             kw = dict(kw)
             rc = raw_query(t, rays, out, kw.pop("spp", 8), 1, n=kw.pop("n", None), flags=kw.pop("flags", prt_amd.QUERY_HOST), **kw)
             assert rc == -2 and L.prt_hip_last_error(), (kw, rc, L.prt_hip_last_error())
-        hip = C.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        hip.hipFree.argtypes = [C.c_void_p]
-        dptr = C.c_void_p()
-        assert hip.hipMalloc(C.byref(dptr), 4096) == 0
-        try:
-            assert raw_query(t, dptr.value + 8, dptr.value + 2048, 8, 1, flags=0, n=16) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
-            assert raw_query(t, dptr.value, dptr.value + 2050, 8, 1, flags=0, n=16) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
-        finally:
-            hip.hipFree(dptr)
+        with prt_amd.DeviceArrays() as dev:
+            dptr = dev.alloc(4096)
+            assert raw_query(t, dptr + 8, dptr + 2048, 8, 1, flags=0, n=16) == -2 and b"16-byte aligned" in L.prt_hip_last_error()
+            assert raw_query(t, dptr, dptr + 2050, 8, 1, flags=0, n=16) == -2 and b"4-byte aligned" in L.prt_hip_last_error()
         assert t.stats()["kernelLaunches"] == 0
         assert (out.view(np.uint32) == UNWRITTEN).all(), "a refused call wrote radiance"
         assert raw_query(t, rays, out, 8, 1) == 0, L.prt_hip_last_error()  # success without a camera

@@ -10,7 +10,8 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
-from test_refit_cpu import bend
+from prt_gpukit import upload
+from prt_refit_ref import bend, teapot_scene
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -35,15 +36,6 @@ def B():
     t = prt_amd.PathTracer(test_entry_points=True)
     yield t
     t.close()
-
-
-def teapot_scene(size=64):
-    return prt_amd.setup_cornell_box(size, size, teapot_mesh=T.teapot_product_mesh())
-
-
-def upload(t, scene, camera):
-    t.upload_scene(scene)
-    t.set_camera(camera)
 
 
 def same(got, want, keys, what):

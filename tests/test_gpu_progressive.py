@@ -1,7 +1,6 @@
 """Progressive rendering on the MI355X (include/prt_hip.h "progressive rendering"): after accumulate passes of s1, ..., sk samples
 the image is, bit for bit, the one-shot render of s1 + ... + sk samples -- so every check below compares bit patterns (tolerance
 0) with a one-shot render, the oracle, or the oracle's whole-frame digests."""
-import ctypes as C
 import hashlib
 import os
 
@@ -10,20 +9,11 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_gpukit import assert_bits_equal, bits, upload
+from prt_gpukit import c1_scene, dev, tracer  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 G = T.GOLDEN
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def assert_bits_equal(a, b, what=""):
-    a, b = bits(a), bits(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    bad = np.nonzero(a != b)
-    assert len(bad[0]) == 0, f"{what}: {len(bad[0])} of {a.size} differ, first at {tuple(int(x[0]) for x in bad)}"
 
 
 def assert_frame_equals_digests(img, rays, occluded, name, spp, depth, exposure):
@@ -38,24 +28,6 @@ def assert_frame_equals_digests(img, rays, occluded, name, spp, depth, exposure)
                  != z["sha"][r, c].tobytes()]
     assert not differing, f"{len(differing)} of {ty * tx} tiles differ from the oracle's frame ({name}), first {differing[:4]}"
     assert (rays, occluded) == (int(z["rays"]), int(z["occluded"]))
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-def upload(tracer, scene, camera):
-    tracer.upload_scene(scene)
-    tracer.set_camera(camera)
-
-
-@pytest.fixture(scope="module")
-def c1_scene():
-    return prt_amd.setup_cornell_box(512, 512, teapot_mesh=T.teapot_product_mesh())
 
 
 def test_c1_passes_equal_one_shot_renders_of_the_running_total(tracer, c1_scene):
@@ -209,7 +181,7 @@ def test_rules(tracer, c1_scene):
     assert reached == 8  # a pass always runs; the budget is checked after it
 
 
-def test_passes_on_a_callers_stream(tracer):
+def test_passes_on_a_callers_stream(tracer, dev):
     """Accumulate, adaptive, resolve and G-buffer into an explicit target on a caller's stream: each result is there when that
     stream gets to its copy, bit for bit the one of the same step on the context's own stream and framebuffer."""
     W = H = 64
@@ -217,29 +189,23 @@ def test_passes_on_a_callers_stream(tracer):
     upload(tracer, scene, camera)
     tracer.seed = 12345
     L, ctx = prt_amd.lib(), tracer._ctx
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
     nbytes = H * W * 3 * 4
-    stream, target = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
+    stream, target = dev.stream(), dev.alloc(nbytes)
     got = [np.zeros((H, W, 3), np.float32) for _ in range(4)]
 
     def copy_out(k):  # queued on the caller's stream only
-        assert hip.hipMemcpyAsync(got[k].ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
+        dev.download_async(got[k], target, stream)
 
-    try:
-        assert hip.hipMemsetAsync(target, 0xff, C.c_size_t(nbytes), stream) == 0
-        tracer.accumulate_async(16, d_rgb=target.value, stream=stream.value, tile=16)
-        copy_out(0)
-        active = tracer.adaptive_pass_async(16, 0.0, 16, 64, d_rgb=target.value, stream=stream.value, tile=16)
-        copy_out(1)
-        assert L.prt_hip_accum_resolve(ctx, 0, 0, W - 1, H - 1, 1.0, target, stream) == 0, L.prt_hip_last_error()
-        copy_out(2)
-        assert L.prt_hip_render_gbuffer(ctx, 0, 0, W - 1, H - 1, 0, tracer.seed, 1.0, target, stream) == 0, L.prt_hip_last_error()
-        copy_out(3)
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        hip.hipFree(target)
-        hip.hipStreamDestroy(stream)
+    dev.fill_async(target, 0xff, nbytes, stream)
+    tracer.accumulate_async(16, d_rgb=target, stream=stream, tile=16)
+    copy_out(0)
+    active = tracer.adaptive_pass_async(16, 0.0, 16, 64, d_rgb=target, stream=stream, tile=16)
+    copy_out(1)
+    assert L.prt_hip_accum_resolve(ctx, 0, 0, W - 1, H - 1, 1.0, target, stream) == 0, L.prt_hip_last_error()
+    copy_out(2)
+    assert L.prt_hip_render_gbuffer(ctx, 0, 0, W - 1, H - 1, 0, tracer.seed, 1.0, target, stream) == 0, L.prt_hip_last_error()
+    copy_out(3)
+    dev.synchronize(stream)
     assert active > 0  # the launch path of the adaptive pass, not the empty one
     tracer.accum_reset()
     want = [tracer.accumulate(16, tile=16)]

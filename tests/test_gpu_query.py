@@ -10,6 +10,8 @@ import prt_amd
 import prt_hostile as H
 import prt_hostile_taps as HT
 import prt_testlib as T
+from prt_gpukit import same_records, snapped_scene
+from prt_gpukit import dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -23,6 +25,7 @@ def miss_surface():
     return s[0]
 
 
+# (differs from prt_gpukit.tracer: max_depth=8)
 @pytest.fixture(scope="module")
 def tracer():
     prt_amd.build()
@@ -38,19 +41,12 @@ def upload_hostile(tracer, name, seed):
     return g, scene, camera, desc
 
 
-def same_bytes(got, want, what):
-    if got.tobytes() != want.tobytes():
-        a, b = got.view(np.uint8).reshape(len(got), -1), want.view(np.uint8).reshape(len(want), -1)
-        bad = np.unique(np.nonzero(a != b)[0])
-        raise AssertionError(f"{what}: {len(bad)} of {len(got)} records differ, first {bad[:4]}: {got[bad[0]]} != {want[bad[0]]}")
-
-
 # ----------------------------------------------------------------------------- 1. the goldens
 @pytest.mark.parametrize("name,seed", CASES)
 def test_nearest_and_any_equal_the_compiled_reference(tracer, name, seed):
     g, _, _, _ = upload_hostile(tracer, name, seed)
     hits = tracer.query_nearest(g["org"], g["dir"], g["max_t"])
-    same_bytes(hits, g["single"], f"{name}{seed} nearest")
+    same_records(hits, g["single"], f"{name}{seed} nearest")
     occ = tracer.query_any(g["org"], g["dir"], g["max_t"])
     assert occ.dtype == np.uint8 and (occ == g["occluded_single"]).all(), f"{name}{seed}: {int((occ != g['occluded_single']).sum())} flags differ"
     if name == "flat":
@@ -69,7 +65,7 @@ def test_every_ray_has_its_own_limit(tracer):
     o = T.OracleScene(desc)
     for first, limit in ((0, 4.0), (1, 1e5)):
         want, wocc = o.intersect_single(org[first::2], d[first::2], limit)
-        same_bytes(hits[first::2], want, f"rays {first}::2 with tMax {limit}")
+        same_records(hits[first::2], want, f"rays {first}::2 with tMax {limit}")
         assert (occ[first::2] == wocc).all()
     # and a limit that matters for every ray that hits: half of its own hit distance leaves nothing in reach, the float above it keeps the hit
     found = g["single"]["t"] != -1
@@ -80,7 +76,7 @@ def test_every_ray_has_its_own_limit(tracer):
     above = np.where(found, np.nextafter(g["single"]["t"], F(np.inf)), F(1e5)).astype(F)
     want = np.concatenate([o.intersect_single(org[r:r + 1], d[r:r + 1], float(above[r]))[0] for r in range(H.RAYS)])
     got = tracer.query_nearest(org, d, above)
-    same_bytes(got, want, "limits one float above the hit")
+    same_records(got, want, "limits one float above the hit")
     print("hits kept one float above the hit:", int((got["t"] != -1).sum()), "of", int(found.sum()))
     assert (got["t"] != -1).sum() > found.sum() // 2
 
@@ -89,7 +85,7 @@ def test_every_ray_has_its_own_limit(tracer):
 @pytest.mark.parametrize("n", [1, 7, 63, 65, 1000])
 def test_prefixes_give_the_prefix_of_the_full_answer(tracer, n):
     g, _, _, _ = upload_hostile(tracer, "grid", 0)
-    same_bytes(tracer.query_nearest(g["org"][:n], g["dir"][:n], g["max_t"]), g["single"][:n], f"the first {n} rays")
+    same_records(tracer.query_nearest(g["org"][:n], g["dir"][:n], g["max_t"]), g["single"][:n], f"the first {n} rays")
     assert (tracer.query_any(g["org"][:n], g["dir"][:n], g["max_t"]) == g["occluded_single"][:n]).all()
 
 
@@ -130,10 +126,10 @@ def test_nan_rays_are_misses_and_leave_their_neighbours_alone(tracer):
     occ = tracer.query_any(rays["org"], rays["dir"], rays["tMax"])
     rest = np.ones(H.RAYS, bool)
     rest[bad] = False
-    same_bytes(hits[bad], np.repeat(MISS_HIT, 32), "NaN rays")
-    same_bytes(surf[bad], np.repeat(miss_surface(), 32), "NaN rays' surfaces")
+    same_records(hits[bad], np.repeat(MISS_HIT, 32), "NaN rays")
+    same_records(surf[bad], np.repeat(miss_surface(), 32), "NaN rays' surfaces")
     assert not occ[bad].any()
-    same_bytes(hits[rest], g["single"][rest], "the other rays")
+    same_records(hits[rest], g["single"][rest], "the other rays")
     assert (occ[rest] == g["occluded_single"][rest]).all()
     assert not np.isnan(hits["t"]).any() and not np.isnan(surf["t"]).any()
 
@@ -189,7 +185,7 @@ def test_fused_surface_records_equal_the_row_level_entries(taps):
     mats = [c.desc.meshes[m].materials[c.desc.meshes[m].prim_material[p]] for m, p in zip(pinned["meshId"][hit], pinned["primId"][hit])]
     print("hits", int(hit.sum()), "on bump-mapped materials", sum(int(m["bumpMap"] >= 0) for m in mats))
     assert hit.sum() >= 256 and any(m["bumpMap"] >= 0 for m in mats)
-    same_bytes(c.hits, pinned, "query_nearest against the row-level trace")
+    same_records(c.hits, pinned, "query_nearest against the row-level trace")
     h, s, org, d = c.hits[hit], c.surf[hit], c.org[hit], c.dir[hit]
     assert s["t"].tobytes() == h["t"].tobytes() and (s["primId"] == h["primId"]).all() and (s["meshId"] == h["meshId"]).all() and not s["pad"].any()
     rec = np.column_stack([h["meshId"], h["primId"], h["i"].view(np.uint32), h["j"].view(np.uint32), h["k"].view(np.uint32)])
@@ -206,8 +202,8 @@ def test_fused_surface_records_equal_the_row_level_entries(taps):
     assert s["diffuse"][none].tobytes() == kd.tobytes()
     P = (org + (h["t"][:, None] * d).astype(F)).astype(F)
     assert s["P"].tobytes() == P.tobytes()
-    same_bytes(c.surf[~hit], np.repeat(miss_surface(), int((~hit).sum())), "misses")
-    same_bytes(c.hits[~hit], np.repeat(MISS_HIT, int((~hit).sum())), "missed hits")
+    same_records(c.surf[~hit], np.repeat(miss_surface(), int((~hit).sum())), "misses")
+    same_records(c.hits[~hit], np.repeat(MISS_HIT, int((~hit).sum())), "missed hits")
 
 
 # ----------------------------------------------------------------------------- 6. the stand-alone surface fetch
@@ -230,7 +226,7 @@ def test_surface_of_the_goldens_records_equals_the_compiled_reference(taps):
 
 def test_surface_of_the_products_own_hits_equals_the_fused_records(taps):
     c = taps
-    same_bytes(c.t.query_surface(c.org, c.dir, c.hits), c.surf, "query_surface(hits) against the fused records")
+    same_records(c.t.query_surface(c.org, c.dir, c.hits), c.surf, "query_surface(hits) against the fused records")
     assert c.t.query_get_counts() == 0
 
 
@@ -249,53 +245,40 @@ def test_indices_outside_the_scene_are_refused_on_the_device(taps):
     hits["primId"][30], hits["primId"][63] = 0xffffffff, 0x7fffffff
     got = c.t.query_surface(c.org[idx], c.dir[idx], hits)
     assert c.t.query_get_counts() == 8
-    same_bytes(got[bad], np.repeat(miss_surface(), 8), "the refused records")
+    same_records(got[bad], np.repeat(miss_surface(), 8), "the refused records")
     want[bad] = miss_surface()
-    same_bytes(got, want, "the 56 others")
+    same_records(got, want, "the 56 others")
     c.t.stats()  # no launch error
 
 
 # ----------------------------------------------------------------------------- 8. device pointers, a caller's stream
-class DeviceBuffer:
-    def __init__(self, hip, nbytes):
-        self.hip, self.ptr, self.nbytes = hip, C.c_void_p(), nbytes
-        assert hip.hipMalloc(C.byref(self.ptr), C.c_size_t(nbytes)) == 0
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
 
 
-def test_device_arrays_on_a_callers_stream(taps):
+def test_device_arrays_on_a_callers_stream(taps, dev):
     c = taps
     n = len(c.org)
     rays = prt_amd.make_rays(c.org, c.dir, 1e5)
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    stream = C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    d_rays, d_hits, d_surf = DeviceBuffer(hip, rays.nbytes + 16), DeviceBuffer(hip, n * 24), DeviceBuffer(hip, n * 80)
+    stream = dev.stream()
+    d_rays, d_hits, d_surf = dev.alloc(rays.nbytes + 16), dev.alloc(n * 24), dev.alloc(n * 80)
     got_h, got_s = np.zeros(n, prt_amd.HIT_DTYPE), np.zeros(n, prt_amd.SURFACE_DTYPE)
-    try:
-        assert d_rays.ptr.value % 16 == 0 and d_surf.ptr.value % 16 == 0
-        c.t.stats()
-        with pytest.raises(prt_amd.PrtError, match="16-byte aligned"):
-            c.t.query_nearest_async(n - 1, d_rays.ptr.value + 4, d_hits.ptr.value, None, stream.value)
-        with pytest.raises(prt_amd.PrtError, match="16-byte aligned"):
-            c.t.query_surface_async(n - 1, d_rays.ptr.value, d_hits.ptr.value, d_surf.ptr.value + 8, stream.value)
-        assert c.t.stats()["kernelLaunches"] == 0  # refused before anything was launched
-        assert hip.hipMemcpyAsync(d_rays.ptr, rays.ctypes.data_as(C.c_void_p), C.c_size_t(rays.nbytes), 1, stream) == 0
-        assert hip.hipMemsetAsync(d_hits.ptr, 0xA5, C.c_size_t(n * 24), stream) == 0
-        assert hip.hipMemsetAsync(d_surf.ptr, 0xA5, C.c_size_t(n * 80), stream) == 0
-        c.t.query_nearest_async(n, d_rays.ptr.value, d_hits.ptr.value, None, stream.value)
-        c.t.query_surface_async(n, d_rays.ptr.value, d_hits.ptr.value, d_surf.ptr.value, stream.value)
-        assert hip.hipStreamSynchronize(stream) == 0
-        assert hip.hipMemcpy(got_h.ctypes.data_as(C.c_void_p), d_hits.ptr, C.c_size_t(n * 24), 2) == 0
-        assert hip.hipMemcpy(got_s.ctypes.data_as(C.c_void_p), d_surf.ptr, C.c_size_t(n * 80), 2) == 0
-    finally:
-        for b in (d_rays, d_hits, d_surf):
-            b.free()
-        hip.hipStreamDestroy(stream)
-    same_bytes(got_h, c.hits, "hits through device pointers")
-    same_bytes(got_s, c.surf, "surfaces through device pointers")
+    assert d_rays % 16 == 0 and d_surf % 16 == 0
+    c.t.stats()
+    with pytest.raises(prt_amd.PrtError, match="16-byte aligned"):
+        c.t.query_nearest_async(n - 1, d_rays + 4, d_hits, None, stream)
+    with pytest.raises(prt_amd.PrtError, match="16-byte aligned"):
+        c.t.query_surface_async(n - 1, d_rays, d_hits, d_surf + 8, stream)
+    assert c.t.stats()["kernelLaunches"] == 0  # refused before anything was launched
+    dev.upload_async(rays, stream, d_rays)
+    dev.fill_async(d_hits, 0xA5, n * 24, stream)
+    dev.fill_async(d_surf, 0xA5, n * 80, stream)
+    c.t.query_nearest_async(n, d_rays, d_hits, None, stream)
+    c.t.query_surface_async(n, d_rays, d_hits, d_surf, stream)
+    dev.synchronize(stream)
+    assert got_h.nbytes == n * 24 and got_s.nbytes == n * 80
+    dev.download(got_h, d_hits)
+    dev.download(got_s, d_surf)
+    same_records(got_h, c.hits, "hits through device pointers")
+    same_records(got_s, c.surf, "surfaces through device pointers")
     st = c.t.stats()
     assert st["raysTraced"] == n and st["kernelLaunches"] == 1
 
@@ -305,7 +288,7 @@ def test_queries_follow_mesh_updates_and_new_uploads(tracer):
     g, scene, _, _ = upload_hostile(tracer, "grid", 0)
     org, d, max_t = g["org"], g["dir"], g["max_t"]
     hits0, surf0 = tracer.query_nearest(org, d, max_t, surface=True)
-    same_bytes(tracer.query_surface(org, d, hits0), surf0, "before the update")  # (builds the inverse table)
+    same_records(tracer.query_surface(org, d, hits0), surf0, "before the update")  # (builds the inverse table)
     moved = (g["meshes"][1] + np.array([0.25, 0.0, 0.0], F)).astype(F)
     scene.update_positions(1, moved)
     tracer.update_meshes(scene, [1])
@@ -316,39 +299,19 @@ def test_queries_follow_mesh_updates_and_new_uploads(tracer):
         want_h, want_s = other.query_nearest(org, d, max_t, surface=True)
     finally:
         other.close()
-    same_bytes(hits1, want_h, "after update_meshes")
-    same_bytes(surf1, want_s, "surfaces after update_meshes")
+    same_records(hits1, want_h, "after update_meshes")
+    same_records(surf1, want_s, "surfaces after update_meshes")
     assert hits1.tobytes() != hits0.tobytes()
-    same_bytes(tracer.query_surface(org, d, hits1), surf1, "query_surface after update_meshes")  # the table was kept: same primIds
+    same_records(tracer.query_surface(org, d, hits1), surf1, "query_surface after update_meshes")  # the table was kept: same primIds
     assert tracer.query_get_counts() == 0
     g2, _, _, _ = upload_hostile(tracer, "twins", 0)
     hits2, surf2 = tracer.query_nearest(g2["org"], g2["dir"], g2["max_t"], surface=True)
-    same_bytes(hits2, g2["single"], "twins0 after a new upload")
-    same_bytes(tracer.query_surface(g2["org"], g2["dir"], hits2), surf2, "query_surface after a new upload")  # the table was rebuilt
+    same_records(hits2, g2["single"], "twins0 after a new upload")
+    same_records(tracer.query_surface(g2["org"], g2["dir"], hits2), surf2, "query_surface after a new upload")  # the table was rebuilt
     assert tracer.query_get_counts() == 0
 
 
 # ----------------------------------------------------------------------------- 10. pick
-def snapped_scene(z, width=64, height=48):
-    """The two-quad scene of tests/test_gpu_hostile_taps.py: an alpha-masked quad (primitives 0, 1) in z = 0 and a bump-mapped, textured
-    one (primitives 2, 3) in z = -1, seen head-on from (0, 0, 3)."""
-    tex = HT.golden_maps(z)
-    names = [n for n, _ in tex]
-    a, g, c = names.index("b4_16x16"), names.index("g1_3x5"), names.index("n4_3x5")
-    mats = np.array([T.make_material(diffuse=(0.9, 0.8, 0.7), alpha_test=1, diffuse_map=a),
-                     T.make_material(diffuse=(1.0, 1.0, 1.0), diffuse_map=c, bump_map=g)], dtype=T.MATERIAL_DTYPE)
-
-    def quad(half, zpos, t0, t1):
-        pos = np.array([[-half, -half, zpos], [half, -half, zpos], [half, half, zpos], [-half, half, zpos]], dtype=F)
-        tc = np.array([[t0, t0], [t1, t0], [t1, t1], [t0, t1]], dtype=F)
-        return pos, tc
-    p0, t0 = quad(1.0, 0.0, -1.0, 2.0)
-    p1, t1 = quad(2.5, -1.0, -2.0 / 3.0, 5.0 / 3.0)
-    pos, tc = np.concatenate([p0, p1]), np.concatenate([t0, t1])
-    idx = np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7]], dtype=np.uint32)
-    mesh = T.MeshDesc(idx, pos, np.array([0, 0, 1, 1], dtype=np.uint32), mats, texcoords=tc)
-    return T.SceneDesc([mesh], cam_pos=(0.0, 0.0, 3.0), cam_dir=(0.0, 0.0, -1.0), width=width, height=height,
-                       light=((0.0, 0.0, 1.0), (3.0, 3.0, 2.5)), textures=[t for _, t in tex])
 
 
 def test_pick_agrees_with_the_position_guide():
@@ -401,7 +364,7 @@ def test_refusals_launch_nothing():
                 assert call(n, flags) == -2, (n, flags, L.prt_hip_last_error())
         assert t.stats()["kernelLaunches"] == 0 and t.query_get_counts() == 0
         g = H.golden("grid", 0)
-        same_bytes(t.query_nearest(g["org"][:8], g["dir"][:8], g["max_t"]), g["single"][:8], "a query without a camera")
+        same_records(t.query_nearest(g["org"][:8], g["dir"][:8], g["max_t"]), g["single"][:8], "a query without a camera")
     finally:
         t.close()
 

@@ -11,55 +11,16 @@ import pytest
 import prt_amd
 import prt_temporal_ref as TR
 import prt_testlib as T
-from prt_refit_ref import refit_nodes
-from test_gpu_denoise import DEFAULTS, assert_bits_equal
-from test_gpu_temporal import TDEFAULTS, camera_equal, check, exported, record_equal
-from test_refit_cpu import RIGID_MOVES, bend, no_negative_zero
+from prt_denoise_ref import DEFAULTS
+from prt_gpucases import CASES, arrays_equal, camera_equal, check, exported, moved_normals, record_equal
+from prt_gpukit import assert_bits_equal
+from prt_gpukit import dev, rows, rows2, tracer  # noqa: F401  (fixtures)
+from prt_refit_ref import RIGID_MOVES, bend, no_negative_zero, refit_nodes, teapot_scene
+from prt_temporal_ref import TDEFAULTS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-ARRAYS = ("wnodes", "hot", "tris", "shade", "bump", "root_boxes", "radius")
 EVENTS = ("raysTraced", "occludedTraced", "nBox", "nTri", "nTap", "modeBox", "modeTri", "modeTap")
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows2():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-def teapot_scene(size=64):
-    return prt_amd.setup_cornell_box(size, size, teapot_mesh=T.teapot_product_mesh())
-
-
-def moved_normals(mesh, P):
-    """calculateVertexNormals of the mesh at positions P, through the oracle."""
-    md = T.MeshDesc(mesh["indices"], P, mesh["prim_material"], mesh["materials"].view(T.MATERIAL_DTYPE), texcoords=mesh["texcoords"])
-    return T.oracle_vertex_normals(md).normals
-
-
-def arrays_equal(got, want, what):
-    for k in ARRAYS:
-        assert got[k].shape == want[k].shape, (what, k, got[k].shape, want[k].shape)
-        assert got[k].tobytes() == want[k].tobytes(), f"{what}: {k} differs in {(got[k].view(np.uint32) != want[k].view(np.uint32)).sum()} words"
 
 
 def record_boxes(nodes):
@@ -109,43 +70,6 @@ def test_rigid_moves_match_the_oracle(tracer):
 
 
 # ----------------------------------------------------------------------------- 2. general deformations against a fresh upload
-def soup_scene():
-    rng = np.random.default_rng(5)
-    n = 3000
-    centre = rng.uniform(-1.0, 1.0, (n, 1, 3))
-    P = (centre + rng.uniform(-0.08, 0.08, (n, 3, 3))).reshape(-1, 3).astype(F)
-    idx = np.arange(3 * n, dtype=np.uint32).reshape(-1, 3)
-    mats = np.array([T.make_material(diffuse=(0.7, 0.6, 0.5)), T.make_material(emissive=(6, 6, 5)),
-                     T.make_material(diffuse=(0.9, 0.9, 0.9), reflection=1)], dtype=T.MATERIAL_DTYPE)
-    scene = prt_amd.Scene()
-    scene.add(prt_amd.Mesh.from_arrays(idx, P, rng.integers(0, 3, n), mats.view(prt_amd.MATERIAL_DTYPE)))
-    scene.set_directional_light(prt_amd._normalize((0.2, 1.0, 0.3)), (8.0, 8.0, 7.0))
-    return scene, prt_amd.Camera().create((0.0, 0.2, 3.5), (0.0, 0.0, -1.0), 64, 48), 1.0
-
-
-def atrium_face_normals():
-    scene = prt_amd.Scene()
-    scene.add(prt_amd.Mesh.atrium(20000, 1, True, True, 0.05))  # no calculate_vertex_normals: the face-normal path
-    scene.set_directional_light(prt_amd._normalize((0.05, 1.0, 0.1)), (16.7, 15.6, 11.7))
-    return scene, prt_amd.Camera().create((-15.0, 4.0, 0.5), (1.0, 0.08, -0.05), 64, 36), 1.0
-
-
-def jitter(P):
-    return (P + np.random.default_rng(9).normal(0.0, 0.01, P.shape)).astype(F)
-
-
-def bent_normals(mesh, P):
-    n = mesh["normals"] + F(0.2) * np.sin(P, dtype=F)
-    return (n / np.linalg.norm(n, axis=1, keepdims=True)).astype(F)
-
-
-CASES = {
-    "teapot_bend": (teapot_scene, 1, bend, moved_normals, False),
-    "soup_jitter": (soup_scene, 0, jitter, None, False),
-    "atrium_normals_passed": (lambda: prt_amd.setup_atrium_standin(64, 36, tris=20000, emissive_fraction=0.05), 0, bend, bent_normals, False),
-    "atrium_normals_kept": (lambda: prt_amd.setup_atrium_standin(64, 36, tris=20000, emissive_fraction=0.05), 0, bend, None, True),
-    "atrium_face_normals": (atrium_face_normals, 0, bend, None, False),
-}
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -372,7 +296,7 @@ def test_refusals_change_nothing(tracer):
 
 
 # ----------------------------------------------------------------------------- 6. a caller's stream
-def test_update_render_download_on_a_callers_stream(tracer):
+def test_update_render_download_on_a_callers_stream(tracer, dev):
     scene, camera, _ = teapot_scene()
     tea = scene.arrays()["meshes"][1]
     tracer.upload_scene(scene)
@@ -386,19 +310,12 @@ def test_update_render_download_on_a_callers_stream(tracer):
         want = fresh.render(16)
     finally:
         fresh.close()
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    nbytes = 64 * 64 * 3 * 4
-    stream, target = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
-    try:
-        tracer.render_async(0, 0, 63, 63, 16, d_rgb=target.value, stream=stream.value)  # the old geometry, queued ahead
-        tracer.update_meshes(scene, [1], stream=stream.value)
-        tracer.render_async(0, 0, 63, 63, 16, d_rgb=target.value, stream=stream.value)
-        got = np.zeros((64, 64, 3), F)
-        assert hip.hipMemcpyAsync(got.ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        hip.hipFree(target)
-        hip.hipStreamDestroy(stream)
+    stream, target = dev.stream(), dev.alloc(64 * 64 * 3 * 4)
+    tracer.render_async(0, 0, 63, 63, 16, d_rgb=target, stream=stream)  # the old geometry, queued ahead
+    tracer.update_meshes(scene, [1], stream=stream)
+    tracer.render_async(0, 0, 63, 63, 16, d_rgb=target, stream=stream)
+    got = np.zeros((64, 64, 3), F)
+    dev.download_async(got, target, stream)
+    dev.synchronize(stream)
     tracer.stats()
     assert_bits_equal(got, want, "update, render and download on one stream")

@@ -11,8 +11,11 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
-from test_gpu_denoise import assert_bits_equal
-from test_scene_edit_cpu import ENV_SHAPES, env_of
+from prt_denoise_ref import DEFAULTS
+from prt_env_ref import ENV_SHAPES, env_of
+from prt_gpukit import assert_bits_equal, upload
+from prt_gpukit import dev, gpu_event_accounting, rows, rows2  # noqa: F401  (fixtures)
+from prt_temporal_ref import TDEFAULTS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -22,30 +25,7 @@ SHADING = ("mats", "alpha_class", "texels", "env_texels", "env_vertical", "env_h
 EVENTS = ("raysTraced", "occludedTraced", "nBox", "nTri", "nTap")
 
 
-@pytest.fixture(scope="module", autouse=True)
-def gpu_event_accounting():
-    """nBox / nTri of occlusion queries follow the GPU's near-first visit (as in test_gpu_parity.py)."""
-    T.oracle().orc_set_anyhit_accounting(1)
-    yield
-    T.oracle().orc_set_anyhit_accounting(0)
-
-
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows2():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
+# (differs from prt_refit_ref.teapot_scene: an environment map on request)
 def teapot_scene(size=64, env=None):
     scene, camera, exposure = prt_amd.setup_cornell_box(size, size, teapot_mesh=T.teapot_product_mesh())
     if env is not None:
@@ -55,11 +35,6 @@ def teapot_scene(size=64, env=None):
 
 def atrium_scene(size=64, bump=True):
     return prt_amd.setup_atrium_standin(size, size, tris=2000, bump=bump)
-
-
-def upload(t, scene, camera):
-    t.upload_scene(scene)
-    t.set_camera(camera)
 
 
 def shading_equal(got, want, what):
@@ -395,8 +370,6 @@ def test_texture_repaint_equals_a_fresh_upload(rows, rows2):
 
 # ----------------------------------------------------------------------------- 11. invalidation
 def test_what_the_edits_invalidate(rows, rows2):
-    from test_gpu_denoise import DEFAULTS
-    from test_gpu_temporal import TDEFAULTS
     scene, camera, exposure = atrium_scene()
     scene.set_infinite_area_light(T.sky_env(16, 8))
     upload(rows, scene, camera)
@@ -467,7 +440,7 @@ def test_what_the_edits_invalidate(rows, rows2):
 
 
 # ----------------------------------------------------------------------------- 12. a caller's stream
-def test_render_update_render_on_a_callers_stream(rows, rows2):
+def test_render_update_render_on_a_callers_stream(rows, rows2, dev):
     scene, camera, _ = teapot_scene(64, T.sky_env(64, 32))
     upload(rows, scene, camera)
     old = rows.render(8)
@@ -476,23 +449,15 @@ def test_render_update_render_on_a_callers_stream(rows, rows2):
     upload(rows2, scene_new, camera)
     new = rows2.render(8)
     assert old.tobytes() != new.tobytes()
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
     nbytes = 64 * 64 * 3 * 4
-    stream, first, second = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    assert hip.hipMalloc(C.byref(first), C.c_size_t(nbytes)) == 0 and hip.hipMalloc(C.byref(second), C.c_size_t(nbytes)) == 0
-    try:
-        rows.render_async(0, 0, 63, 63, 8, d_rgb=first.value, stream=stream.value)  # the old scene, queued ahead
-        rows.update_lights(scene_new, stream=stream.value)
-        rows.render_async(0, 0, 63, 63, 8, d_rgb=second.value, stream=stream.value)
-        got = [np.zeros((64, 64, 3), F), np.zeros((64, 64, 3), F)]
-        for dst, src in zip(got, (first, second)):
-            assert hip.hipMemcpyAsync(dst.ctypes.data_as(C.c_void_p), src, C.c_size_t(nbytes), 2, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        hip.hipFree(first)
-        hip.hipFree(second)
-        hip.hipStreamDestroy(stream)
+    stream, first, second = dev.stream(), dev.alloc(nbytes), dev.alloc(nbytes)
+    rows.render_async(0, 0, 63, 63, 8, d_rgb=first, stream=stream)  # the old scene, queued ahead
+    rows.update_lights(scene_new, stream=stream)
+    rows.render_async(0, 0, 63, 63, 8, d_rgb=second, stream=stream)
+    got = [np.zeros((64, 64, 3), F), np.zeros((64, 64, 3), F)]
+    for dst, src in zip(got, (first, second)):
+        dev.download_async(dst, src, stream)
+    dev.synchronize(stream)
     rows.stats()
     assert_bits_equal(got[0], old, "the render queued before the edit")
     assert_bits_equal(got[1], new, "the render queued after the edit")

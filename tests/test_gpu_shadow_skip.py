@@ -9,63 +9,12 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_gpucases import check_scene
+from prt_gpukit import assert_same_image, upload
+from prt_gpukit import gpu_event_accounting  # noqa: F401  (fixture)
+from prt_gpukit import rows as tracer  # noqa: F401  (fixture: this module's tracer is a context of the test build, for the tally's entry point)
 
 pytestmark = pytest.mark.gpu
-
-COUNTS = ("raysTraced", "occludedTraced", "nBox", "nTri", "nHit", "nTap", "nPx")
-
-
-def assert_same_image(img, ref, what):
-    """Bit patterns equal; where the oracle has a NaN the GPU must have one too (sign and payload of a NaN differ between SSE and the GPU)."""
-    nan = np.isnan(ref)
-    assert np.array_equal(np.isnan(img), nan), f"{what}: NaN pixels differ"
-    a = np.ascontiguousarray(img, dtype=np.float32).view(np.uint32)[~nan]
-    b = np.ascontiguousarray(ref, dtype=np.float32).view(np.uint32)[~nan]
-    bad = np.nonzero(a != b)[0]
-    assert len(bad) == 0, f"{what}: {len(bad)} of {a.size} values differ, first at {int(bad[0])}"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def gpu_event_accounting():
-    """nBox / nTri of occlusion queries follow the GPU's near-first visit (as in test_gpu_parity.py)."""
-    T.oracle().orc_set_anyhit_accounting(1)
-    yield
-    T.oracle().orc_set_anyhit_accounting(0)
-
-
-@pytest.fixture(scope="module")
-def tracer():
-    """A context of the test build: the product's kernels plus the tally's entry point."""
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-def upload(tracer, scene, camera):
-    tracer.upload_scene(scene)
-    tracer.set_camera(camera)
-
-
-def check_scene(tracer, scene, camera, spp, depth, what, exposure=1.0):
-    """Timed render: image, raysTraced, occludedTraced = the oracle's; counting render: image and all event counts = the oracle's, and
-    no ray skipped.  Returns (oracle stats, rays skipped by the timed render, the oracle's image)."""
-    upload(tracer, scene, camera)
-    desc = T.scene_desc_from_product(scene, camera, exposure)
-    ref, ost = T.OracleScene(desc).render(spp, max_depth=depth)
-    img = tracer.render(spp, max_depth=depth, exposure=exposure)
-    st = tracer.last_stats
-    skipped = tracer.occlusion_skipped()
-    print(f"{what}: occlusion rays {ost['occludedTraced']} of {ost['raysTraced']} rays, answered without a walk {skipped}")
-    assert_same_image(img, ref, what + ", timed build")
-    assert st["raysTraced"] == ost["raysTraced"] and st["occludedTraced"] == ost["occludedTraced"], (what, st, ost)
-    img = tracer.render(spp, max_depth=depth, exposure=exposure, count_traffic=True)
-    st = tracer.last_stats
-    assert tracer.occlusion_skipped() == 0, what
-    assert_same_image(img, ref, what + ", counting build")
-    for k in COUNTS:
-        assert st[k] == ost[k], (what, k, st[k], ost[k])
-    return ost, skipped, ref
 
 
 def quad_mesh(kd=(0.7, 0.6, 0.5), half=1.5, normals=None):

@@ -9,12 +9,12 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_gpukit import SENTINEL
+from prt_gpukit import dev  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 U = np.uint32
-SENTINEL = 0xffc0bad1
-H2D, D2H = 1, 2
 CAM_W, CAM_H = 64, 48
 AW = AH = 4  # the atlas
 
@@ -132,39 +132,24 @@ def test_a_rasterise_that_owns_no_texel_leaves_the_arrays_alone(fresh):
     assert (texels == SENTINEL).all() and (hits == SENTINEL).all(), "n = 0, and an entry of the caller's arrays was written"
 
 
-def test_device_array_calls_leave_the_arena_alone(fresh):
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    held = []
-
-    def dev(a):
-        p = C.c_void_p()
-        assert hip.hipMalloc(C.byref(p), max(a.nbytes, 64)) == 0 and hip.hipMemcpy(p, a.ctypes.data, a.nbytes, H2D) == 0
-        held.append(p)
-        return p.value
-
+def test_device_array_calls_leave_the_arena_alone(fresh, dev):
     t = fresh()
     want = step_nearest1(fresh(), fresh, {})
     assert step_nearest1(t, fresh, {}) == want  # the arena holds one ray's worth
-    try:
-        points, normals, dirs, weights = bake_inputs()
-        pts = prt_amd.make_bake_points(points, normals)
-        d, w, table = prt_amd.make_bake_sets(dirs, weights)
-        table.dirs, table.weights = dev(d), dev(w)
-        out = np.zeros((5, 2, 3), F)
-        d_out = dev(out)
-        t.bake_async(5, dev(pts), table, d_out, 8, seed=9)
-        texels = np.array([0, 5, 10, 15], U)
-        image = np.zeros((AH, AW, 3), F)
-        d_image = dev(image)
-        t.atlas_resolve_async(AW, AH, 4, dev(texels), dev(values_for(4)), 3, 2, d_image, None)  # mask = NULL: the context's scratch mask
-        t.stats()  # synchronises the context's stream
-        assert hip.hipMemcpy(out.ctypes.data, d_out, out.nbytes, D2H) == 0 and hip.hipMemcpy(image.ctypes.data, d_image, image.nbytes, D2H) == 0
-        assert out.tobytes() == step_bake(fresh(), fresh, {}), "device and host arrays give different sums"
-        assert image.tobytes() == fresh().atlas_resolve(texels, values_for(4), AW, AH, gutter=2)[0].tobytes()
-        assert step_nearest1(t, fresh, {}) == want, "a host-array query after device-array calls differs from a fresh context's"
-    finally:
-        for p in held:
-            hip.hipFree(p)
+    points, normals, dirs, weights = bake_inputs()
+    pts = prt_amd.make_bake_points(points, normals)
+    d, w, table = prt_amd.make_bake_sets(dirs, weights)
+    table.dirs, table.weights = dev.upload(d), dev.upload(w)
+    out = np.zeros((5, 2, 3), F)
+    d_out = dev.upload(out)
+    t.bake_async(5, dev.upload(pts), table, d_out, 8, seed=9)
+    texels = np.array([0, 5, 10, 15], U)
+    image = np.zeros((AH, AW, 3), F)
+    d_image = dev.upload(image)
+    t.atlas_resolve_async(AW, AH, 4, dev.upload(texels), dev.upload(values_for(4)), 3, 2, d_image, None)  # mask = NULL: the context's scratch mask
+    t.stats()  # synchronises the context's stream
+    dev.download(out, d_out)
+    dev.download(image, d_image)
+    assert out.tobytes() == step_bake(fresh(), fresh, {}), "device and host arrays give different sums"
+    assert image.tobytes() == fresh().atlas_resolve(texels, values_for(4), AW, AH, gutter=2)[0].tobytes()
+    assert step_nearest1(t, fresh, {}) == want, "a host-array query after device-array calls differs from a fresh context's"

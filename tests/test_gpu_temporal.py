@@ -11,48 +11,21 @@ import pytest
 import prt_amd
 import prt_temporal_ref as TR
 import prt_testlib as T
-from test_gpu_denoise import DEFAULTS, assert_bits_equal, bits, synthetic_state
+from prt_denoise_ref import DEFAULTS
+from prt_gpucases import camera_equal, check, exported, record_equal
+from prt_gpukit import assert_bits_equal, bits, synthetic_state
+from prt_gpukit import box_scene, dev, rows, tracer  # noqa: F401  (fixtures)
+from prt_temporal_ref import PARAMETER_SETS, TDEFAULTS
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-TDEFAULTS = dict(position_tolerance=0.01, normal_cos=0.9, max_history=256.0)
 VIEW_A = ((0.0, 0.965, 2.6), (0.0, 0.0, -1.0))
 VIEW_B = ((0.15, 0.965, 2.5), (-0.05, 0.0, -1.0))
 VIEW_C = ((0.4, 1.1, 2.3), (-0.15, -0.05, -1.0))
 
 
-@pytest.fixture(scope="module")
-def tracer():
-    prt_amd.build()
-    t = prt_amd.PathTracer()
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def rows():
-    prt_amd.build()
-    t = prt_amd.PathTracer(test_entry_points=True)
-    yield t
-    t.close()
-
-
-@pytest.fixture(scope="module")
-def box_scene():
-    return prt_amd.setup_cornell_box(64, 64)[0]
-
-
 def view(v, width, height):
     return prt_amd.Camera().create(v[0], v[1], width, height)
-
-
-def record_equal(got, want, what):
-    for k in ("color_var", "pos_len", "normal"):
-        assert_bits_equal(got[k], want[k], f"{what}: {k}")
-
-
-def camera_equal(a, b):
-    return bytes(a) == bytes(b)
 
 
 # ----------------------------------------------------------------------------- 4. the position guide
@@ -197,24 +170,6 @@ def load_synthetic(t, scene, width, height, seed, pixels=1.5):
     return dict(total=state["sum"], count=state["count"], mom=mom, albedo=albedo, normal=normal, position=position, history=hist)
 
 
-def check(t, s, exposure=1.0, what="", temporal=None, **kw):
-    p = dict(DEFAULTS, **kw)
-    tp = dict(TDEFAULTS, **(temporal or {}))
-    img = t.denoise_temporal(exposure=exposure, **tp, **p)
-    var = t.denoise_variance()
-    pend = t.history_export(1)
-    want, want_var, want_pend = TR.denoise_temporal(exposure=exposure, **s, **tp, **p)
-    assert_bits_equal(img, want, f"{what} {tp} {kw}: image")
-    assert_bits_equal(var, want_var, f"{what} {tp} {kw}: variance")
-    record_equal(pend, want_pend, f"{what} {tp} {kw}: pending")
-    assert camera_equal(pend["camera"], t._camera.desc)
-    return img, want_pend
-
-
-PARAMETER_SETS = (TDEFAULTS, dict(position_tolerance=0.05, normal_cos=0.5, max_history=32.0),
-                  dict(position_tolerance=0.02, normal_cos=-1.0, max_history=1e6))
-
-
 @pytest.mark.parametrize("size", [(97, 61), (33, 200), (1, 1), (5, 3)])
 def test_synthetic_state_matches_the_restatement(tracer, box_scene, size):
     w, h = size
@@ -295,10 +250,6 @@ def test_without_history_it_is_the_plain_denoiser(tracer, box_scene):
 
 
 # ----------------------------------------------------------------------------- 7. / 8. rendered chains and the life cycle
-def exported(t, guide_samples=8):
-    state, mom = t.accum_export(), t.accum_export_moments()
-    albedo, normal = t.denoise_guides(guide_samples)
-    return dict(total=state["sum"], count=state["count"], mom=mom, albedo=albedo, normal=normal, position=t.denoise_position())
 
 
 def history_or_none(t):
@@ -425,25 +376,19 @@ def test_temporal_denoise_is_a_pure_read(tracer):
     assert_bits_equal(img, tracer.accumulate(8), "continued accumulation")
 
 
-def test_explicit_target_on_a_callers_stream(tracer, box_scene):
+def test_explicit_target_on_a_callers_stream(tracer, box_scene, dev):
     s = load_synthetic(tracer, box_scene, 97, 61, seed=3)
     want, _, _ = TR.denoise_temporal(**s, **TDEFAULTS, **DEFAULTS)
     tracer.accum_resolve(1.0)
     fb_before = np.zeros((61, 97, 3), F)
     tracer._download(fb_before, 0, 0, 96, 60)
-    hip = C.CDLL("libamdhip64.so")  # the runtime the library itself is linked to
     nbytes = 61 * 97 * 3 * 4
-    stream, target = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0 and hip.hipMalloc(C.byref(target), C.c_size_t(nbytes)) == 0
-    try:
-        assert hip.hipMemsetAsync(target, 0xff, C.c_size_t(nbytes), stream) == 0
-        tracer.denoise_temporal_async(d_rgb=target.value, stream=stream.value, **TDEFAULTS, **DEFAULTS)
-        got = np.zeros((61, 97, 3), F)
-        assert hip.hipMemcpyAsync(got.ctypes.data_as(C.c_void_p), target, C.c_size_t(nbytes), 2, stream) == 0
-        assert hip.hipStreamSynchronize(stream) == 0
-    finally:
-        hip.hipFree(target)
-        hip.hipStreamDestroy(stream)
+    stream, target = dev.stream(), dev.alloc(nbytes)
+    dev.fill_async(target, 0xff, nbytes, stream)
+    tracer.denoise_temporal_async(d_rgb=target, stream=stream, **TDEFAULTS, **DEFAULTS)
+    got = np.zeros((61, 97, 3), F)
+    dev.download_async(got, target, stream)
+    dev.synchronize(stream)
     assert_bits_equal(got, want, "caller's buffer")
     fb_after = np.zeros((61, 97, 3), F)
     tracer._download(fb_after, 0, 0, 96, 60)

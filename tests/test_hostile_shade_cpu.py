@@ -19,7 +19,7 @@ import pytest
 import prt_amd
 import prt_hostile_shade as S
 import prt_testlib as T
-from test_gpu_shadow_skip import assert_same_image
+from prt_gpukit import assert_same_image
 
 need_ref = pytest.mark.skipif(T.ref_binary("ref_path_stats") is None, reason="oracle/_ref/ref_path_stats is not built (no reference sources here)")
 

@@ -18,7 +18,7 @@ import prt_adaptive_ref as AR
 import prt_denoise_ref as R
 import prt_hostile_state as HS
 import prt_temporal_ref as TR
-from test_gpu_temporal import PARAMETER_SETS
+from prt_temporal_ref import PARAMETER_SETS
 
 F = np.float32
 NAN, INF = float("nan"), float("inf")

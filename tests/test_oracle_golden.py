@@ -8,14 +8,12 @@ import numpy as np
 import pytest
 
 import prt_testlib as T
+from prt_testlib import bits
 
 G = T.GOLDEN
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
+# (differs from prt_testlib.assert_bits_equal: the shapes may differ as long as they broadcast)
 def assert_bits_equal(a, b, what=""):
     a, b = bits(a), bits(b)
     bad = np.nonzero(a != b)

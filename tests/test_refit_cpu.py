@@ -11,24 +11,8 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
-from prt_refit_ref import refit_nodes
+from prt_refit_ref import RIGID_MOVES, atrium_scene, bend, no_negative_zero, refit_nodes, teapot_scene
 
-# the rigid moves of the teapot for which a REBUILD gives the refit's tree (checked below; the GPU suite relies on it)
-RIGID_MOVES = {
-    "scale2": lambda P: (np.float32(2.0) * P).astype(np.float32),
-    "scale0.5": lambda P: (np.float32(0.5) * P).astype(np.float32),
-    "shift0.25x": lambda P: (P + np.array([0.25, 0.0, 0.0], dtype=np.float32)).astype(np.float32),
-}
-
-
-def bend(P):
-    P = np.ascontiguousarray(P, dtype=np.float32)
-    return (P + np.float32(0.05) * np.sin(np.float32(6.0) * P[:, [1, 2, 0]], dtype=np.float32)).astype(np.float32)
-
-
-def no_negative_zero(a):
-    a = np.asarray(a, dtype=np.float32)
-    return not np.signbit(a[a == 0]).any()
 
 
 @pytest.fixture(scope="module")
@@ -68,14 +52,6 @@ def test_rigid_moves_rebuild_to_the_refitted_tree():
         rnodes, rremap, _ = single_mesh_oracle(moved)
         assert (rremap == remap).all(), name
         assert rnodes.tobytes() == refit_nodes(nodes, remap, tea.indices, P).tobytes(), name
-
-
-def teapot_scene():
-    return prt_amd.setup_cornell_box(64, 64, teapot_mesh=T.teapot_product_mesh())
-
-
-def atrium_scene():
-    return prt_amd.setup_atrium_standin(64, 64, tris=4000, emissive_fraction=0.05)
 
 
 @pytest.mark.parametrize("which", ["teapot", "atrium"])

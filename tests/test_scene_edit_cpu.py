@@ -11,21 +11,10 @@ import pytest
 
 import prt_amd
 import prt_testlib as T
+from prt_env_ref import ENV_SHAPES, env_of
 
 F = np.float32
-# width x height of the maps the GPU suite builds on the device as well (tests/test_gpu_scene_edit.py): one texel, one column, one row,
-# more rows than a wavefront has lanes with a width that is no multiple of 64, more than two chunks per row
-ENV_SHAPES = [(1, 1), (1, 7), (67, 1), (67, 70), (130, 3)]
 BAD_VERTICAL, PARTLY_NAN, BAD_ROW = 1, 2, 4
-
-
-def env_of(name):
-    if name == "black_row":
-        e = T.sky_env(64, 32)
-        e[5, :, :3] = 0.0
-        return e
-    w, h = name
-    return T.sky_env(w, h, seed=w + 100 * h)
 
 
 def first_step(cdf):

@@ -14,6 +14,7 @@ import prt_denoise_ref as R
 import prt_temporal_ref as TR
 import prt_testlib as T
 from prt_amd import _build as B
+from prt_testlib import bits
 
 F = np.float32
 ENTRY_POINTS = ("prt_hip_denoise_get_position", "prt_hip_denoise_set_position", "prt_hip_accum_denoise_temporal", "prt_hip_history_reset",
@@ -206,10 +207,6 @@ def loop_merge(total, count, mom, albedo, normal, position, history, tol, ncos, 
                 out["cm"][y, x], out["vm"][y, x], out["len"][y, x], out["have"][y, x] = cm, vm, ln, have
                 out["plen"][y, x] = ln if (valid and t >= 0) else F(0)
     return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
 
 
 def camera(pos, direction=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), right=(1.0, 0.0, 0.0), width=12, height=8):

@@ -6,7 +6,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 import numpy as np
 import prt_amd
-import test_gpu_parity as G
+import prt_gpucases as G
 tr = prt_amd.PathTracer(device=0)
 bad = 0
 for seed in range(int(sys.argv[1]), int(sys.argv[2]) + 1):

@@ -123,27 +123,11 @@ def radiance(args):
     emit(out, args.out)
 
 
-class DeviceArray:
-    """A numpy array's bytes in device memory (hipMalloc through the runtime the library is linked to)."""
-    hip = None
-
-    def __init__(self, a):
-        if DeviceArray.hip is None:
-            h = DeviceArray.hip = C.CDLL("libamdhip64.so")
-            h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-            h.hipFree.argtypes = [C.c_void_p]
-            h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.ptr, self.nbytes = C.c_void_p(), a.nbytes
-        assert self.hip.hipMalloc(C.byref(self.ptr), max(a.nbytes, 64)) == 0, "hipMalloc"
-        assert self.hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, 1) == 0
-
-    def get(self, dtype):
-        out = np.zeros(self.nbytes // np.dtype(dtype).itemsize, dtype=dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
+def fetch(dev, p, count, dtype):
+    """`count` elements of `dtype` from device address p (the null stream: behind the context's blocking stream)."""
+    out = np.zeros(count, dtype=dtype)
+    dev.download(out, p)
+    return out
 
 
 def bake(args):
@@ -173,48 +157,46 @@ def bake(args):
         pts = prt_amd.make_bake_points(surf["P"], surf["shadingNormal"], 1e-4)
         for K in (64, 256):
             d, w = prt_amd.bake_cosine_set(K, np.random.default_rng(K))
-            bufs = [DeviceArray(a) for a in (pts, d, w, np.zeros(n * 3, np.float32), np.zeros(n * K, prt_amd.RAY_DTYPE),
-                                             np.zeros((n * K, 3), np.float32))]
-            d_pts, d_dirs, d_w, d_out, d_rays, d_rad = (b.ptr.value for b in bufs)
-            table = prt_amd.BakeSets(K=K, C=1, nSets=1, reserved=0, dirs=d_dirs, weights=d_w)
-            p = t._probe_params(spp, None, None, None)
-            times = {k: [] for k in ("a_bake_wall", "c_frame_kernel", "rays_kernel_wall", "reduce_kernel_wall", "b_host_route_wall",
-                                     "b_numpy_rays", "b_query_radiance", "b_numpy_reduce")}
-            host = None
-            for rep in range(2 + args.reps):
-                keep = rep >= 2
-                sync()
-                t0 = time.perf_counter()
+            with prt_amd.DeviceArrays() as dev:
+                d_pts, d_dirs, d_w, d_out, d_rays, d_rad = (dev.upload(a) for a in (pts, d, w, np.zeros(n * 3, np.float32), np.zeros(n * K, prt_amd.RAY_DTYPE),
+                                                                                       np.zeros((n * K, 3), np.float32)))
+                table = prt_amd.BakeSets(K=K, C=1, nSets=1, reserved=0, dirs=d_dirs, weights=d_w)
+                p = t._probe_params(spp, None, None, None)
+                times = {k: [] for k in ("a_bake_wall", "c_frame_kernel", "rays_kernel_wall", "reduce_kernel_wall", "b_host_route_wall",
+                                         "b_numpy_rays", "b_query_radiance", "b_numpy_reduce")}
+                host = None
+                for rep in range(2 + args.reps):
+                    keep = rep >= 2
+                    sync()
+                    t0 = time.perf_counter()
+                    t.bake_async(n, d_pts, table, d_out, spp)
+                    st = t.stats()
+                    dt = (time.perf_counter() - t0) * 1e3
+                    if keep:
+                        times["a_bake_wall"].append(dt)
+                        times["c_frame_kernel"].append(st["kernelMs"])
+                    for name, call in (("rays_kernel_wall", lambda: t._L.prt_hip_bake_rays(t._ctx, n, d_pts, C.byref(table), d_rays, 0, None)),
+                                       ("reduce_kernel_wall", lambda: t._L.prt_hip_bake_reduce(t._ctx, n, d_pts, C.byref(table), d_rad, d_out, 0, None))):
+                        sync()
+                        t0 = time.perf_counter()
+                        assert call() == 0
+                        sync()
+                        if keep:
+                            times[name].append((time.perf_counter() - t0) * 1e3)
+                    if rep in (0, 2 + args.reps - 1) or (keep and n * K <= 1 << 20):  # (the host route at 16.8 M rays: once warm, once timed)
+                        t0 = time.perf_counter()
+                        rays = host_rays(pts, d)
+                        t1 = time.perf_counter()
+                        L = t.query_radiance(rays["org"], rays["dir"], spp)
+                        t2 = time.perf_counter()
+                        host = (np.pi * L.reshape(n, K, 3).mean(axis=1, dtype=np.float64)).astype(np.float32)
+                        t3 = time.perf_counter()
+                        if keep:
+                            for k, v in (("b_host_route_wall", t3 - t0), ("b_numpy_rays", t1 - t0), ("b_query_radiance", t2 - t1), ("b_numpy_reduce", t3 - t2)):
+                                times[k].append(v * 1e3)
                 t.bake_async(n, d_pts, table, d_out, spp)
-                st = t.stats()
-                dt = (time.perf_counter() - t0) * 1e3
-                if keep:
-                    times["a_bake_wall"].append(dt)
-                    times["c_frame_kernel"].append(st["kernelMs"])
-                for name, call in (("rays_kernel_wall", lambda: t._L.prt_hip_bake_rays(t._ctx, n, d_pts, C.byref(table), d_rays, 0, None)),
-                                   ("reduce_kernel_wall", lambda: t._L.prt_hip_bake_reduce(t._ctx, n, d_pts, C.byref(table), d_rad, d_out, 0, None))):
-                    sync()
-                    t0 = time.perf_counter()
-                    assert call() == 0
-                    sync()
-                    if keep:
-                        times[name].append((time.perf_counter() - t0) * 1e3)
-                if rep in (0, 2 + args.reps - 1) or (keep and n * K <= 1 << 20):  # (the host route at 16.8 M rays: once warm, once timed)
-                    t0 = time.perf_counter()
-                    rays = host_rays(pts, d)
-                    t1 = time.perf_counter()
-                    L = t.query_radiance(rays["org"], rays["dir"], spp)
-                    t2 = time.perf_counter()
-                    host = (np.pi * L.reshape(n, K, 3).mean(axis=1, dtype=np.float64)).astype(np.float32)
-                    t3 = time.perf_counter()
-                    if keep:
-                        for k, v in (("b_host_route_wall", t3 - t0), ("b_numpy_rays", t1 - t0), ("b_query_radiance", t2 - t1), ("b_numpy_reduce", t3 - t2)):
-                            times[k].append(v * 1e3)
-            t.bake_async(n, d_pts, table, d_out, spp)
-            rays_traced = t.stats()["raysTraced"]
-            got = bufs[3].get(np.float32).reshape(n, 3)
-            for b in bufs:
-                b.free()
+                rays_traced = t.stats()["raysTraced"]
+                got = fetch(dev, d_out, n * 3, np.float32).reshape(n, 3)
             a, c = float(np.median(times["a_bake_wall"])), float(np.median(times["c_frame_kernel"]))
             out["bake"][f"{n}x{K}"] = {
                 "ms": {k: spread(v) for k, v in times.items()}, "rays_traced": rays_traced,
@@ -251,37 +233,34 @@ def atlas(args):
     sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
     for W in (1024, 4096):
         H = W
-        d_uv = {m: DeviceArray(uv) for m, uv in uvs.items()}
-        bufs = [DeviceArray(np.zeros(W * H, np.uint32)), DeviceArray(np.zeros(W * H, prt_amd.HIT_DTYPE))]
-        d_texels, d_hits = (b.ptr.value for b in bufs)
-        rasterize = lambda: t.atlas_rasterize_device(W, H, {m: b.ptr.value for m, b in d_uv.items()}, dict(enumerate(prims)), d_texels, d_hits)  # noqa: E731
-        counts = rasterize()
-        n = counts["n"]
-        bufs += [DeviceArray(np.zeros(n, prt_amd.BAKE_POINT_DTYPE)), DeviceArray(np.zeros((n, 3), np.float32)),
-                 DeviceArray(np.zeros((W * H, 3), np.float32)), DeviceArray(np.zeros(W * H, np.uint8))]
-        d_points, d_values, d_image, d_mask = (b.ptr.value for b in bufs[2:])
-        times = {k: [] for k in ("rasterize_wall", "points_wall", "resolve_wall", "lightmap_wall", "bake_kernels")}
-        image = mask = None
-        for rep in range(2 + args.reps):
-            keep = rep >= 2
-            for name, call in (("rasterize_wall", rasterize), ("points_wall", lambda: t.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias)),
-                               ("resolve_wall", lambda: t.atlas_resolve_async(W, H, n, d_texels, d_values, 3, gutter, d_image, d_mask))):
+        with prt_amd.DeviceArrays() as dev:
+            d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
+            d_texels, d_hits = dev.upload(np.zeros(W * H, np.uint32)), dev.upload(np.zeros(W * H, prt_amd.HIT_DTYPE))
+            rasterize = lambda: t.atlas_rasterize_device(W, H, d_uv, dict(enumerate(prims)), d_texels, d_hits)  # noqa: E731
+            counts = rasterize()
+            n = counts["n"]
+            d_points, d_values, d_image, d_mask = (dev.upload(a) for a in (np.zeros(n, prt_amd.BAKE_POINT_DTYPE), np.zeros((n, 3), np.float32),
+                                                                           np.zeros((W * H, 3), np.float32), np.zeros(W * H, np.uint8)))
+            times = {k: [] for k in ("rasterize_wall", "points_wall", "resolve_wall", "lightmap_wall", "bake_kernels")}
+            image = mask = None
+            for rep in range(2 + args.reps):
+                keep = rep >= 2
+                for name, call in (("rasterize_wall", rasterize), ("points_wall", lambda: t.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias)),
+                                   ("resolve_wall", lambda: t.atlas_resolve_async(W, H, n, d_texels, d_values, 3, gutter, d_image, d_mask))):
+                    sync()
+                    t0 = time.perf_counter()
+                    call()
+                    sync()
+                    if keep:
+                        times[name].append((time.perf_counter() - t0) * 1e3)
                 sync()
                 t0 = time.perf_counter()
-                call()
-                sync()
+                image, mask = t.lightmap(uvs, W, H, d, w, spp, bias=bias, gutter=gutter)
+                dt = (time.perf_counter() - t0) * 1e3
                 if keep:
-                    times[name].append((time.perf_counter() - t0) * 1e3)
-            sync()
-            t0 = time.perf_counter()
-            image, mask = t.lightmap(uvs, W, H, d, w, spp, bias=bias, gutter=gutter)
-            dt = (time.perf_counter() - t0) * 1e3
-            if keep:
-                times["lightmap_wall"].append(dt)
-                times["bake_kernels"].append(t.last_stats["kernelMsSum"])  # (a bake of more than 2^24 rays is several launches)
-        launches, rays_last = t.last_stats["kernelLaunches"], t.last_stats["raysTraced"]
-        for b in bufs + list(d_uv.values()):
-            b.free()
+                    times["lightmap_wall"].append(dt)
+                    times["bake_kernels"].append(t.last_stats["kernelMsSum"])  # (a bake of more than 2^24 rays is several launches)
+            launches, rays_last = t.last_stats["kernelLaunches"], t.last_stats["raysTraced"]
         # the route it replaces, once
         host = {}
         t0 = time.perf_counter()
@@ -353,82 +332,80 @@ def lens(args):
     pos = np.array(list(c.pos), np.float64)
     at, up = pos + np.array(list(c.dir), np.float64), (0.0, 1.0, 0.0)
     sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
-    scratch = [DeviceArray(np.zeros(1 << 24, prt_amd.RAY_DTYPE)), DeviceArray(np.zeros((1 << 24, 3), np.float32))]
-    d_rays, d_rad = (b.ptr.value for b in scratch)
-    workloads = {"equirect_2048x1024_K1": prt_amd.lens_equirect(pos, 2048, 1024, K=1, fwd=list(c.dir), jitter_seed=1),
-                 "thin_lens_1920x1080_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 1920, 1080, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1),
-                 "thin_lens_3840x2160_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 3840, 2160, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1)}
-    for name, d in workloads.items():
-        W, H, K = d.width, d.height, d.K
-        rows = min(H, (1 << 24) // (W * K))
-        image = DeviceArray(np.zeros(W * H * 3, np.float32))
-        times = {k: [] for k in ("a_lens_render_wall", "c_frame_kernels", "rays_kernel_wall", "accumulate_kernel_wall")}
-        launches = 0
-        for rep in range(1 + args.reps):  # one warm-up round
-            sync()
+    with prt_amd.DeviceArrays() as scratch:
+        d_rays, d_rad = scratch.upload(np.zeros(1 << 24, prt_amd.RAY_DTYPE)), scratch.upload(np.zeros((1 << 24, 3), np.float32))
+        workloads = {"equirect_2048x1024_K1": prt_amd.lens_equirect(pos, 2048, 1024, K=1, fwd=list(c.dir), jitter_seed=1),
+                     "thin_lens_1920x1080_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 1920, 1080, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1),
+                     "thin_lens_3840x2160_K8": prt_amd.lens_pinhole(pos, at, up, 0.9, 3840, 2160, K=8, lens_radius=0.05, focus=6.0, jitter_seed=1)}
+        for name, d in workloads.items():
+            W, H, K = d.width, d.height, d.K
+            rows = min(H, (1 << 24) // (W * K))
+            with prt_amd.DeviceArrays() as dev:
+                image = dev.upload(np.zeros(W * H * 3, np.float32))
+                times = {k: [] for k in ("a_lens_render_wall", "c_frame_kernels", "rays_kernel_wall", "accumulate_kernel_wall")}
+                launches = 0
+                for rep in range(1 + args.reps):  # one warm-up round
+                    sync()
+                    t0 = time.perf_counter()
+                    t.render_lens_async(d, image, spp)
+                    st = t.stats()
+                    dt = (time.perf_counter() - t0) * 1e3
+                    launches = st["kernelLaunches"]
+                    if rep:
+                        times["a_lens_render_wall"].append(dt)
+                        times["c_frame_kernels"].append(st["kernelMsSum"])
+                    for key, call in (("rays_kernel_wall", lambda: t._L.prt_hip_lens_rays(t._ctx, C.byref(d), 0, rows, d_rays, 0, None)),
+                                      ("accumulate_kernel_wall", lambda: t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, rows, d_rad, image, 0, None))):
+                        sync()
+                        t0 = time.perf_counter()
+                        assert call() == 0
+                        sync()
+                        if rep:
+                            times[key].append((time.perf_counter() - t0) * 1e3)
+                t.render_lens_async(d, image, spp)
+                rays_traced_last_band = t.stats()["raysTraced"]
+                got = fetch(dev, image, W * H * 3, np.float32).reshape(H, W, 3) / np.float32(K)
+            # (b), once: the chunks are the caller's to cut
+            rng = np.random.default_rng(7)
+            host = np.zeros((H, W, 3), np.float32)
+            tb = {"numpy_rays": 0.0, "query_radiance": 0.0, "numpy_sum": 0.0}
             t0 = time.perf_counter()
-            t.render_lens_async(d, image.ptr.value, spp)
-            st = t.stats()
-            dt = (time.perf_counter() - t0) * 1e3
-            launches = st["kernelLaunches"]
-            if rep:
-                times["a_lens_render_wall"].append(dt)
-                times["c_frame_kernels"].append(st["kernelMsSum"])
-            for key, call in (("rays_kernel_wall", lambda: t._L.prt_hip_lens_rays(t._ctx, C.byref(d), 0, rows, d_rays, 0, None)),
-                              ("accumulate_kernel_wall", lambda: t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, rows, d_rad, image.ptr.value, 0, None))):
-                sync()
-                t0 = time.perf_counter()
-                assert call() == 0
-                sync()
-                if rep:
-                    times[key].append((time.perf_counter() - t0) * 1e3)
-        t.render_lens_async(d, image.ptr.value, spp)
-        rays_traced_last_band = t.stats()["raysTraced"]
-        got = image.get(np.float32).reshape(H, W, 3) / np.float32(K)
-        image.free()
-        # (b), once: the chunks are the caller's to cut
-        rng = np.random.default_rng(7)
-        host = np.zeros((H, W, 3), np.float32)
-        tb = {"numpy_rays": 0.0, "query_radiance": 0.0, "numpy_sum": 0.0}
-        t0 = time.perf_counter()
-        for y0 in range(0, H, rows):
-            y1 = min(H, y0 + rows)
-            t1 = time.perf_counter()
-            org, dr = lens_host_band(d, y0, y1, rng)
-            t2 = time.perf_counter()
-            L = t.query_radiance(org, dr, spp, seed=seed + y0 * W * K)
-            t3 = time.perf_counter()
-            host[y0:y1] = L.reshape(y1 - y0, W, K, 3).sum(axis=2) / np.float32(K)
-            t4 = time.perf_counter()
-            tb["numpy_rays"] += (t2 - t1) * 1e3
-            tb["query_radiance"] += (t3 - t2) * 1e3
-            tb["numpy_sum"] += (t4 - t3) * 1e3
-            del org, dr, L
-        b_ms = (time.perf_counter() - t0) * 1e3
-        a, cc = float(np.median(times["a_lens_render_wall"])), float(np.median(times["c_frame_kernels"]))
-        out["lens"][name] = {
-            "rays": W * H * K, "bands": launches, "rows_per_band": rows, "ms": {k: spread(v) for k, v in times.items()},
-            "a_over_c": a / cc, "b_host_route_wall_ms": b_ms, "b_parts_ms": tb, "b_over_a": b_ms / a,
-            "new_kernels_ms_per_call": (float(np.median(times["rays_kernel_wall"])) + float(np.median(times["accumulate_kernel_wall"]))) * launches,
-            "rays_traced_last_band": rays_traced_last_band, "image_mean": float(got.mean(dtype=np.float64)),
-            "host_route_image_mean": float(host.mean(dtype=np.float64))}
-    # the accumulate kernel alone: 2^24 radiances (201 MB read) into 2^24 / K pixels
-    for K, (W, H) in ((1, (4096, 4096)), (8, (2048, 1024)), (64, (512, 512))):
-        d = prt_amd.lens_pinhole(pos, at, up, 0.9, W, H, K=K)
-        image = DeviceArray(np.zeros(W * H * 3, np.float32))
-        ms = []
-        for rep in range(2 + args.reps):
-            sync()
-            t0 = time.perf_counter()
-            assert t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, H, d_rad, image.ptr.value, 0, None) == 0
-            sync()
-            if rep >= 2:
-                ms.append((time.perf_counter() - t0) * 1e3)
-        image.free()
-        nbytes = 12 * (1 << 24) + 12 * W * H
-        out["accumulate_alone"][f"K{K}"] = {"pixels": W * H, "wall_ms": spread(ms), "GB_per_s": nbytes / float(np.median(ms)) / 1e6}
-    for b in scratch:
-        b.free()
+            for y0 in range(0, H, rows):
+                y1 = min(H, y0 + rows)
+                t1 = time.perf_counter()
+                org, dr = lens_host_band(d, y0, y1, rng)
+                t2 = time.perf_counter()
+                L = t.query_radiance(org, dr, spp, seed=seed + y0 * W * K)
+                t3 = time.perf_counter()
+                host[y0:y1] = L.reshape(y1 - y0, W, K, 3).sum(axis=2) / np.float32(K)
+                t4 = time.perf_counter()
+                tb["numpy_rays"] += (t2 - t1) * 1e3
+                tb["query_radiance"] += (t3 - t2) * 1e3
+                tb["numpy_sum"] += (t4 - t3) * 1e3
+                del org, dr, L
+            b_ms = (time.perf_counter() - t0) * 1e3
+            a, cc = float(np.median(times["a_lens_render_wall"])), float(np.median(times["c_frame_kernels"]))
+            out["lens"][name] = {
+                "rays": W * H * K, "bands": launches, "rows_per_band": rows, "ms": {k: spread(v) for k, v in times.items()},
+                "a_over_c": a / cc, "b_host_route_wall_ms": b_ms, "b_parts_ms": tb, "b_over_a": b_ms / a,
+                "new_kernels_ms_per_call": (float(np.median(times["rays_kernel_wall"])) + float(np.median(times["accumulate_kernel_wall"]))) * launches,
+                "rays_traced_last_band": rays_traced_last_band, "image_mean": float(got.mean(dtype=np.float64)),
+                "host_route_image_mean": float(host.mean(dtype=np.float64))}
+        # the accumulate kernel alone: 2^24 radiances (201 MB read) into 2^24 / K pixels
+        for K, (W, H) in ((1, (4096, 4096)), (8, (2048, 1024)), (64, (512, 512))):
+            d = prt_amd.lens_pinhole(pos, at, up, 0.9, W, H, K=K)
+            with prt_amd.DeviceArrays() as dev:
+                image = dev.upload(np.zeros(W * H * 3, np.float32))
+                ms = []
+                for rep in range(2 + args.reps):
+                    sync()
+                    t0 = time.perf_counter()
+                    assert t._L.prt_hip_lens_accumulate(t._ctx, C.byref(d), 0, H, d_rad, image, 0, None) == 0
+                    sync()
+                    if rep >= 2:
+                        ms.append((time.perf_counter() - t0) * 1e3)
+            nbytes = 12 * (1 << 24) + 12 * W * H
+            out["accumulate_alone"][f"K{K}"] = {"pixels": W * H, "wall_ms": spread(ms), "GB_per_s": nbytes / float(np.median(ms)) / 1e6}
     t.close()
     emit(out, args.out)
 

@@ -60,24 +60,6 @@ def bend_by(P, amplitude):
     return np.ascontiguousarray(P + np.float32(amplitude) * np.sin(np.float32(6.0) * P[:, [1, 2, 0]], dtype=np.float32), dtype=np.float32)
 
 
-class DeviceArray:
-    def __init__(self, hip, a):
-        self.hip, self.ptr, self.nbytes = hip, C.c_void_p(), a.nbytes
-        assert hip.hipMalloc(C.byref(self.ptr), C.c_size_t(a.nbytes)) == 0
-        self.set(a)
-
-    def set(self, a):
-        a = np.ascontiguousarray(a, dtype=np.float32)  # (a sum with a fancy-indexed operand may come out column-major)
-        assert a.nbytes == self.nbytes
-        assert self.hip.hipMemcpy(self.ptr, a.ctypes.data_as(C.c_void_p), C.c_size_t(a.nbytes), 1) == 0
-
-    def to_host(self, out):
-        assert self.hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), self.ptr, C.c_size_t(out.nbytes), 2) == 0
-
-    def free(self):
-        self.hip.hipFree(self.ptr)
-
-
 def fmt(v):
     s = spread(v)
     return f"{s['median']:.3f} ({s['min']:.3f}-{s['max']:.3f})"
@@ -106,7 +88,6 @@ def upload_rebuilt(t, scene, nodes, remap, P, N, radius):
 
 def device_mode(args):
     RECOMPUTE = prt_amd.MeshDeform.NORMALS_RECOMPUTE
-    hip = C.CDLL("libamdhip64.so")
     lines = []
 
     def say(text=""):
@@ -130,63 +111,63 @@ def device_mode(args):
         t.upload_scene(scene)
         t.set_camera(camera)
         P = np.ascontiguousarray(bend(P0))
-        dP = DeviceArray(hip, P)
-        t0 = time.perf_counter()
-        t.deform_meshes([(0, dP.ptr.value, RECOMPUTE)])
-        first = (time.perf_counter() - t0) * 1e3
-        deform = wall_ms(lambda: t.deform_meshes([(0, dP.ptr.value, RECOMPUTE)]), args.reps, 2)
-        ups, _ = t._deforms([(0, dP.ptr.value, RECOMPUTE)], False)
-        ms = (C.c_float * 5)()
-        t._chk(t._L.prt_hip_test_deform_profile(t._ctx, 1, ups, prt_amd.MeshDeform.RADIUS_AUTO, args.reps, ms), "prt_hip_test_deform_profile")
-        say(f"(a) prt_hip_deform_meshes, device pointers, RECOMPUTE + RADIUS_AUTO: {fmt(deform)} ms; first call (builds the incidence list) {first:.1f} ms")
-        say(f"    kernels: keep + box {ms[0]:.4f}  face normals {ms[1]:.4f}  vertex normals {ms[2]:.4f}  gather {ms[3]:.4f}  levels + finish {ms[4]:.4f}  "
-            f"sum {sum(ms):.4f} ms")
-        gotP, gotN = t.mesh_vertices(0)
-        # (b) the round trip through the host
-        back = np.zeros_like(P)
-        d2h = wall_ms(lambda: dP.to_host(back), args.reps, 1)
-        one = np.zeros((), dtype=prt_amd.MATERIAL_DTYPE)
-        normals = []
-        for _ in range(max(3, args.reps // 2)):
-            pm = prt_amd.Mesh.from_arrays(idx, back, np.zeros(len(idx), np.uint32), one.reshape(1))
+        with prt_amd.DeviceArrays() as dev:
+            dP = dev.upload(P)
             t0 = time.perf_counter()
-            pm.calculate_vertex_normals()
-            normals.append((time.perf_counter() - t0) * 1e3)
-            del pm
-        host_update = wall_ms(lambda: scene.update_positions(0, back, gotN), max(3, args.reps // 2), 1)
-        update = wall_ms(lambda: t.update_meshes(scene), args.reps, 2)
-        total = sum(float(np.median(v)) for v in (d2h, normals, host_update, update))
-        say(f"(b) the host round trip it replaces: device->host copy {fmt(d2h)} + calculate_vertex_normals {fmt(normals)} + "
-            f"Scene.update_positions {fmt(host_update)} + prt_hip_update_meshes (positions and normals) {fmt(update)} = {total:.3f} ms")
-        say(f"    (b) / (a) = {total / float(np.median(deform)):.1f}")
-        a = scene.arrays()
-        same = t.mesh_vertices(0)
-        say(f"    state check: positions held by the library equal the caller's {same[0].tobytes() == P.tobytes()}; radius {t.mesh_info(0)['radius']!r}, "
-            f"host Scene's {a['radius']!r}")
-        if key == "c3":
-            say()
-            say(f"-- bend amplitudes on {key}: P + A sin(6 P.yzx); frame = 960x540, {args.spp} spp, kernel ms median (min-max) of {args.reps}; "
-                "rebuild = prt_hip_build_bvh + prt_hip_upload_scene of the same positions and normals")
-            say("   A      sahCost/sahCostAtUpload   refit frame ms            rebuild sahCost ratio   rebuild frame ms          refit / rebuild")
-            t.upload_scene(scene_fresh(kw))
-            t.set_camera(camera)
-            t2 = prt_amd.PathTracer(test_entry_points=True)
-            for A in args.amplitudes:
-                PA = bend_by(P0, A)
-                dP.set(PA)
-                t.deform_meshes([(0, dP.ptr.value, RECOMPUTE)])
-                info = t.mesh_info(0)
-                refit = frame_ms(t, args.reps, args.spp)
-                _, NA = t.mesh_vertices(0)
-                nodes, remap, _ = t2.build_bvh(idx, PA)
-                upload_rebuilt(t2, scene, nodes, remap, PA, NA, float(info["radius"]))
-                t2.set_camera(camera)
-                info2 = t2.mesh_info(0)
-                rebuilt = frame_ms(t2, args.reps, args.spp)
-                say(f"   {A:<6g} {info['sahCost'] / info['sahCostAtUpload']:<25.4f} {fmt(refit):<25} {info2['sahCost'] / info['sahCostAtUpload']:<23.4f} "
-                    f"{fmt(rebuilt):<25} {np.median(refit) / np.median(rebuilt):.3f}")
-            t2.close()
-        dP.free()
+            t.deform_meshes([(0, dP, RECOMPUTE)])
+            first = (time.perf_counter() - t0) * 1e3
+            deform = wall_ms(lambda: t.deform_meshes([(0, dP, RECOMPUTE)]), args.reps, 2)
+            ups, _ = t._deforms([(0, dP, RECOMPUTE)], False)
+            ms = (C.c_float * 5)()
+            t._chk(t._L.prt_hip_test_deform_profile(t._ctx, 1, ups, prt_amd.MeshDeform.RADIUS_AUTO, args.reps, ms), "prt_hip_test_deform_profile")
+            say(f"(a) prt_hip_deform_meshes, device pointers, RECOMPUTE + RADIUS_AUTO: {fmt(deform)} ms; first call (builds the incidence list) {first:.1f} ms")
+            say(f"    kernels: keep + box {ms[0]:.4f}  face normals {ms[1]:.4f}  vertex normals {ms[2]:.4f}  gather {ms[3]:.4f}  levels + finish {ms[4]:.4f}  "
+                f"sum {sum(ms):.4f} ms")
+            gotP, gotN = t.mesh_vertices(0)
+            # (b) the round trip through the host
+            back = np.zeros_like(P)
+            d2h = wall_ms(lambda: dev.download(back, dP), args.reps, 1)
+            one = np.zeros((), dtype=prt_amd.MATERIAL_DTYPE)
+            normals = []
+            for _ in range(max(3, args.reps // 2)):
+                pm = prt_amd.Mesh.from_arrays(idx, back, np.zeros(len(idx), np.uint32), one.reshape(1))
+                t0 = time.perf_counter()
+                pm.calculate_vertex_normals()
+                normals.append((time.perf_counter() - t0) * 1e3)
+                del pm
+            host_update = wall_ms(lambda: scene.update_positions(0, back, gotN), max(3, args.reps // 2), 1)
+            update = wall_ms(lambda: t.update_meshes(scene), args.reps, 2)
+            total = sum(float(np.median(v)) for v in (d2h, normals, host_update, update))
+            say(f"(b) the host round trip it replaces: device->host copy {fmt(d2h)} + calculate_vertex_normals {fmt(normals)} + "
+                f"Scene.update_positions {fmt(host_update)} + prt_hip_update_meshes (positions and normals) {fmt(update)} = {total:.3f} ms")
+            say(f"    (b) / (a) = {total / float(np.median(deform)):.1f}")
+            a = scene.arrays()
+            same = t.mesh_vertices(0)
+            say(f"    state check: positions held by the library equal the caller's {same[0].tobytes() == P.tobytes()}; radius {t.mesh_info(0)['radius']!r}, "
+                f"host Scene's {a['radius']!r}")
+            if key == "c3":
+                say()
+                say(f"-- bend amplitudes on {key}: P + A sin(6 P.yzx); frame = 960x540, {args.spp} spp, kernel ms median (min-max) of {args.reps}; "
+                    "rebuild = prt_hip_build_bvh + prt_hip_upload_scene of the same positions and normals")
+                say("   A      sahCost/sahCostAtUpload   refit frame ms            rebuild sahCost ratio   rebuild frame ms          refit / rebuild")
+                t.upload_scene(scene_fresh(kw))
+                t.set_camera(camera)
+                t2 = prt_amd.PathTracer(test_entry_points=True)
+                for A in args.amplitudes:
+                    PA = bend_by(P0, A)
+                    dev.upload(PA, dP)  # (bend_by returns a C-contiguous float32 array of P's size)
+                    t.deform_meshes([(0, dP, RECOMPUTE)])
+                    info = t.mesh_info(0)
+                    refit = frame_ms(t, args.reps, args.spp)
+                    _, NA = t.mesh_vertices(0)
+                    nodes, remap, _ = t2.build_bvh(idx, PA)
+                    upload_rebuilt(t2, scene, nodes, remap, PA, NA, float(info["radius"]))
+                    t2.set_camera(camera)
+                    info2 = t2.mesh_info(0)
+                    rebuilt = frame_ms(t2, args.reps, args.spp)
+                    say(f"   {A:<6g} {info['sahCost'] / info['sahCostAtUpload']:<25.4f} {fmt(refit):<25} {info2['sahCost'] / info['sahCostAtUpload']:<23.4f} "
+                        f"{fmt(rebuilt):<25} {np.median(refit) / np.median(rebuilt):.3f}")
+                t2.close()
         t.close()
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -45,7 +45,7 @@ def main():
           f"environment map {a.env[0]} x {a.env[1]}; alpha-tested texture {alpha}: {arr['textures'][alpha].shape}; library {prt_amd.test_lib().prt_hip_source_sha16().decode()}")
 
     def drain():
-        C.CDLL("libamdhip64.so").hipDeviceSynchronize()
+        prt_amd.hip_runtime().hipDeviceSynchronize()
 
     def env_edit(k):
         scene.set_infinite_area_light(envs[k % 2])  # (the host mirror builds its tables here; the edit does not send them)
