@@ -267,7 +267,7 @@ void InfiniteAreaLight::release()
 // tinyexr is absent here, so the format is read directly: single-part scan-line files with NO, RLE, ZIPS or ZIP compression
 // and UINT / HALF / FLOAT channels sampled 1:1.  Channels R, G, B (and A) by name; a file with one channel is grey, a missing A
 // is 1, as LoadEXR fills them.  PIZ / PXR24 / B44 / DWA, tiles, deep and multi-part files are refused with a message.
-bool inflateZlibBytes(const std::vector<uint8_t>& in, std::vector<uint8_t>& out); // prt_models.cpp (the PNG reader's inflate)
+bool inflateZlibBytes(const std::vector<uint8_t>& in, std::vector<uint8_t>& out, size_t limit); // prt_models.cpp (the PNG reader's inflate: stops at `limit` bytes)
 
 static float halfToFloat(uint16_t h)
 {
@@ -360,10 +360,14 @@ static bool loadExrRgba(const std::vector<uint8_t>& file, int& width, int& heigh
         else if (n == "A") target[c] = 3;
     }
     const bool grey = channels.size() == 1 && target[0] < 0;
-    rgba.assign((size_t)w * h * 4, 0.0f);
-    for (size_t i = 3; i < rgba.size(); i += 4) rgba[i] = 1.0f;
     const uint32_t linesPerBlock = compression == 3 ? 16u : 1u, blocks = ((uint32_t)h + linesPerBlock - 1) / linesPerBlock;
     if (!need((size_t)blocks * 8)) { err = "truncated offset table"; return false; }
+    // The data window against the bytes that can fill it, before the texels are allocated: stored lines are in the file byte for
+    // byte, an RLE pair of bytes yields at most 128, and deflate expands by at most 1032 : 1.
+    const uint64_t mostPerByte = compression == 0 ? 1 : compression == 1 ? 64 : 1032;
+    if ((uint64_t)lineBytes * (uint64_t)h > (uint64_t)(file.size() - pos) * mostPerByte) { err = "data window larger than the file can fill"; return false; }
+    rgba.assign((size_t)w * h * 4, 0.0f);
+    for (size_t i = 3; i < rgba.size(); i += 4) rgba[i] = 1.0f;
     const size_t table = pos;
     std::vector<uint8_t> packed, raw, tmp;
     for (uint32_t b = 0; b < blocks; b++) {
@@ -394,10 +398,11 @@ static bool loadExrRgba(const std::vector<uint8_t>& file, int& width, int& heigh
                         if (i >= size) { err = "bad RLE block"; return false; }
                         tmp.insert(tmp.end(), (size_t)n + 1, data[i++]);
                     }
+                    if (tmp.size() > expect) break; // told apart below
                 }
             } else {
                 packed.assign(data, data + size);
-                if (!inflateZlibBytes(packed, tmp)) { err = "bad ZIP block"; return false; }
+                if (!inflateZlibBytes(packed, tmp, expect + 1)) { err = "bad ZIP block"; return false; } // (+ 1: a block that unpacks to more is told apart below)
             }
             if (tmp.size() != expect) { err = "block does not unpack to its size"; return false; }
             for (size_t k = 1; k < tmp.size(); k++) tmp[k] = (uint8_t)(tmp[k - 1] + tmp[k] - 128); // predictor
@@ -471,6 +476,17 @@ void InfiniteAreaLight::create(const char* path)
         return;
     }
     fgetc(f); // the single whitespace after the header
+    {   // the header's size against the bytes that follow it, before anything is allocated
+        const long at = ftell(f);
+        fseek(f, 0, SEEK_END);
+        const long end = ftell(f);
+        fseek(f, at, SEEK_SET);
+        if (at < 0 || end < at || (uint64_t)w * (uint64_t)h * 12 > (uint64_t)(end - at)) {
+            logPrintf(LogLevel::kError, "'%s' is truncated\n", path);
+            fclose(f);
+            return;
+        }
+    }
     std::vector<float> rgb((size_t)w * h * 3);
     size_t got = fread(rgb.data(), sizeof(float), rgb.size(), f);
     fclose(f);

@@ -2,6 +2,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <exception>
+
 #include "../../../include/prt_host.h"
 #include "prt.h"
 
@@ -40,14 +42,17 @@ prt_host_mesh* prt_host_mesh_cornell(int box)
 
 prt_host_mesh* prt_host_mesh_load_obj(const char* path, const prt_material* mat)
 {
-    auto* m = new prt_host_mesh;
-    if (mat) m->mesh.loadObj(path, toMaterial(*mat));
-    else m->mesh.loadObj(path);
-    if (m->mesh.getPrimCount() == 0) {
-        delete m;
+    // The readers take files from a user's disk.  No exception may pass through extern "C" (the caller may be C, or ctypes): a
+    // file that makes a reader run out of memory, or throw anything else, is a file that did not load.
+    try {
+        std::unique_ptr<prt_host_mesh> m(new prt_host_mesh);
+        if (mat) m->mesh.loadObj(path, toMaterial(*mat));
+        else m->mesh.loadObj(path);
+        if (m->mesh.getPrimCount() == 0) return nullptr;
+        return m.release();
+    } catch (const std::exception&) { // std::bad_alloc included
         return nullptr;
     }
-    return m;
 }
 
 prt_host_mesh* prt_host_mesh_from_arrays(uint32_t primCount, uint32_t vertexCount, uint32_t materialCount, const uint32_t* indices,
@@ -129,7 +134,11 @@ void prt_host_scene_set_env_light(prt_host_scene* s, int32_t width, int32_t heig
 
 int prt_host_scene_load_env_light(prt_host_scene* s, const char* path)
 {
-    s->scene.setInfiniteAreaLight(path);
+    try {
+        s->scene.setInfiniteAreaLight(path);
+    } catch (const std::exception&) { // as in prt_host_mesh_load_obj
+        return -1;
+    }
     return s->scene.isLightAvailable(LightType::kInfiniteArea) ? 0 : -1;
 }
 

@@ -78,7 +78,7 @@ bool parseObj(const char* path, ObjData& o)
     std::map<std::string, int32_t> matIndex;
     int32_t curMat = -1;
     std::string line;
-    struct Corner { int32_t v, t; };
+    struct Corner { long v, t; }; // as parsed: an index is range-checked before it is narrowed to the table's 32 bits
     std::vector<Corner> corners;
     while (std::getline(f, line)) {
         const char* s = line.c_str();
@@ -103,22 +103,26 @@ bool parseObj(const char* path, ObjData& o)
                 long t = 0;
                 bool hasT = false;
                 p = e;
+                // (strtol skips white space: an index that is left out, as in "1//" or "1/", must not take the next corner's number)
+                auto number = [](const char* q) { return (*q >= '0' && *q <= '9') || *q == '-' || *q == '+'; };
                 if (*p == '/') {
                     p++;
-                    if (*p != '/') {
+                    if (number(p)) {
                         t = strtol(p, &e, 10);
                         hasT = e != p;
                         p = e;
                     }
                     if (*p == '/') {
                         p++;
-                        (void)strtol(p, &e, 10);
-                        p = e;
+                        if (number(p)) {
+                            (void)strtol(p, &e, 10);
+                            p = e;
+                        }
                     }
                 }
                 Corner c;
-                c.v = (int32_t)(v > 0 ? v - 1 : (long)o.positions.size() + v);
-                c.t = hasT ? (int32_t)(t > 0 ? t - 1 : (long)vt.size() + t) : -1;
+                c.v = v > 0 ? v - 1 : (long)o.positions.size() + v;
+                c.t = hasT ? (t > 0 ? t - 1 : (long)vt.size() + t) : -1;
                 corners.push_back(c);
             }
             // fan triangulation 0-(k)-(k+1)
@@ -153,6 +157,17 @@ bool parseObj(const char* path, ObjData& o)
     return true;
 }
 
+// Bytes between the read position and the end of the file: what a header may claim is held against this BEFORE anything is allocated,
+// so that the memory a reader takes is bounded by the size of the file it was given, not by the numbers in it.
+static size_t bytesLeft(FILE* f)
+{
+    const long at = ftell(f);
+    if (at < 0 || fseek(f, 0, SEEK_END) != 0) return 0;
+    const long end = ftell(f);
+    if (fseek(f, at, SEEK_SET) != 0 || end < at) return 0;
+    return (size_t)(end - at);
+}
+
 // Decoders of the two 8-bit image families this build reads without stb: rows top to bottom, `depth` interleaved components.
 // Binary PPM (P6), PGM (P5) and PAM (P7) ...
 static bool decodePnm(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>& raw)
@@ -179,6 +194,7 @@ static bool decodePnm(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>&
     }
     fgetc(f);
     if (w <= 0 || h <= 0 || w > 65535 || h > 65535 || maxv != 255 || depth < 1 || depth > 4) return false;
+    if ((size_t)w * h * depth > bytesLeft(f)) return false;
     raw.resize((size_t)w * h * depth);
     return fread(raw.data(), 1, raw.size(), f) == raw.size();
 }
@@ -197,7 +213,9 @@ static bool decodeTga(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>&
     if (!((grey && bpp == 8) || (!grey && (bpp == 24 || bpp == 32)))) return false;
     depth = bpp / 8;
     if (fseek(f, idLength, SEEK_CUR) != 0) return false;
-    const size_t n = (size_t)w * h;
+    const size_t n = (size_t)w * h, left = bytesLeft(f);
+    // raw: every pixel is in the file; run-length encoded: a packet of 1 + depth bytes yields at most 128 pixels
+    if (rle ? n > left / (1 + (size_t)depth) * 128 : n * depth > left) return false;
     std::vector<uint8_t> px(n * depth);
     if (!rle) {
         if (fread(px.data(), 1, px.size(), f) != px.size()) return false;
@@ -287,9 +305,12 @@ struct Huffman {
         return -1;
     }
 };
-bool inflateZlib(const std::vector<uint8_t>& in, std::vector<uint8_t>& out)
+// `limit`: the inflate stops (and succeeds) once `out` holds that many bytes -- the caller knows how many it can use, and a
+// stream that inflates to more must not be able to take memory without bound.
+bool inflateZlib(const std::vector<uint8_t>& in, std::vector<uint8_t>& out, size_t limit)
 {
     if (in.size() < 6) return false;
+    if (out.size() >= limit) return true;
     BitReader br{in.data() + 2, in.size() - 2}; // skip the zlib header (CMF, FLG); the Adler-32 trailer is not checked
     static const uint16_t lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
     static const uint8_t lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
@@ -304,8 +325,10 @@ bool inflateZlib(const std::vector<uint8_t>& in, std::vector<uint8_t>& out)
             size_t len = br.p[br.pos] | (br.p[br.pos + 1] << 8);
             br.pos += 4;
             if (br.pos + len > br.n) return false;
+            len = std::min(len, limit - out.size());
             out.insert(out.end(), br.p + br.pos, br.p + br.pos + len);
             br.pos += len;
+            if (out.size() >= limit) return true;
         } else if (type == 1 || type == 2) {
             Huffman lit, dist;
             uint8_t lens[320];
@@ -340,8 +363,10 @@ bool inflateZlib(const std::vector<uint8_t>& in, std::vector<uint8_t>& out)
             for (;;) {
                 int sym = lit.decode(br);
                 if (sym < 0 || br.fail) return false;
-                if (sym < 256) out.push_back((uint8_t)sym);
-                else if (sym == 256) break;
+                if (sym < 256) {
+                    out.push_back((uint8_t)sym);
+                    if (out.size() >= limit) return true;
+                } else if (sym == 256) break;
                 else {
                     sym -= 257;
                     if (sym >= 29) return false;
@@ -350,7 +375,10 @@ bool inflateZlib(const std::vector<uint8_t>& in, std::vector<uint8_t>& out)
                     if (ds < 0 || ds >= 30) return false;
                     size_t d = dbase[ds] + (size_t)br.bits(dext[ds]);
                     if (d > out.size()) return false;
-                    for (int k = 0; k < len; k++) out.push_back(out[out.size() - d]);
+                    for (int k = 0; k < len; k++) {
+                        out.push_back(out[out.size() - d]);
+                        if (out.size() >= limit) return true;
+                    }
                 }
             }
         } else {
@@ -399,12 +427,22 @@ static bool decodePng(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>&
                          (colorType == 3 && (bits == 1 || bits == 2 || bits == 4 || bits == 8)) ||
                          ((colorType == 2 || colorType == 4 || colorType == 6) && (bits == 8 || bits == 16));
     if (!okDepth) return false;
+    static const int x0s[8] = {0, 0, 4, 0, 2, 0, 1, 0}, y0s[8] = {0, 0, 0, 4, 0, 2, 0, 1}, dxs[8] = {1, 8, 8, 4, 4, 2, 2, 1}, dys[8] = {1, 8, 8, 8, 4, 4, 2, 2};
+    // What the IDAT stream has to inflate to: a filter byte and a row of samples for every row of every pass.  Deflate expands by
+    // at most 1032 : 1 (a 258-byte match per 2 bits), so a header that asks for more than the IDAT bytes can hold is refused here,
+    // before anything is inflated or allocated; the inflate stops at that size (what follows is ignored, as libpng ignores it),
+    // and a stream that falls short is refused.  Only then are the samples allocated.
+    uint64_t expected = 0;
+    for (int pass = interlace ? 1 : 0; pass <= (interlace ? 7 : 0); pass++) {
+        const int pw = (w - x0s[pass] + dxs[pass] - 1) / dxs[pass], ph = (h - y0s[pass] + dys[pass] - 1) / dys[pass];
+        if (pw > 0 && ph > 0) expected += (1 + ((uint64_t)pw * channels * bits + 7) / 8) * (uint64_t)ph;
+    }
+    if (expected > (uint64_t)idat.size() * 1032) return false;
     std::vector<uint8_t> data;
-    if (!inflateZlib(idat, data)) return false;
+    if (!inflateZlib(idat, data, (size_t)expected) || data.size() < expected) return false;
     // samples of the whole image, 16 bits each (as stored: not yet scaled)
     std::vector<uint16_t> img((size_t)w * h * channels);
     const size_t bpp = std::max<size_t>(1, (size_t)channels * bits / 8); // the filters' "corresponding byte" distance
-    static const int x0s[8] = {0, 0, 4, 0, 2, 0, 1, 0}, y0s[8] = {0, 0, 0, 4, 0, 2, 0, 1}, dxs[8] = {1, 8, 8, 4, 4, 2, 2, 1}, dys[8] = {1, 8, 8, 8, 4, 4, 2, 2};
     size_t at = 0;
     std::vector<uint8_t> prev, cur;
     for (int pass = interlace ? 1 : 0; pass <= (interlace ? 7 : 0); pass++) {
@@ -598,18 +636,22 @@ const uint8_t kJpegZigzag[64 + 15] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32
                                       6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31,
                                       39, 46, 53, 60, 61, 54, 47, 55, 62, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
 inline uint8_t jclamp(int x) { return (unsigned)x > 255u ? (x < 0 ? 0 : 255) : (uint8_t)x; }
-#define J_F2F(x) ((int)(((x) * 4096 + 0.5)))
-#define J_FSH(x) ((x) * 4096)
+// The sums and products of the IDCT run in uint32_t: the same bits as stb_image's `int` arithmetic wherever that is defined (every
+// conforming file), and defined -- wrapping -- where coefficients a hostile file dequantises to would overflow an int.  J_S
+// reinterprets a result as signed for the arithmetic shifts.
+#define J_F2F(x) ((uint32_t)(int)(((x) * 4096 + 0.5)))
+#define J_FSH(x) ((x) * 4096u)
+#define J_S(x) ((int32_t)(x))
 #define J_IDCT_1D(s0, s1, s2, s3, s4, s5, s6, s7)                                               \
-    int t0, t1, t2, t3, p1, p2, p3, p4, p5, x0, x1, x2, x3;                                     \
-    p2 = s2; p3 = s6;                                                                           \
+    uint32_t t0, t1, t2, t3, p1, p2, p3, p4, p5, x0, x1, x2, x3;                                \
+    p2 = (uint32_t)(s2); p3 = (uint32_t)(s6);                                                   \
     p1 = (p2 + p3) * J_F2F(0.5411961f);                                                         \
     t2 = p1 + p3 * J_F2F(-1.847759065f);                                                        \
     t3 = p1 + p2 * J_F2F(0.765366865f);                                                         \
-    p2 = s0; p3 = s4;                                                                           \
+    p2 = (uint32_t)(s0); p3 = (uint32_t)(s4);                                                   \
     t0 = J_FSH(p2 + p3); t1 = J_FSH(p2 - p3);                                                   \
     x0 = t0 + t3; x3 = t0 - t3; x1 = t1 + t2; x2 = t1 - t2;                                     \
-    t0 = s7; t1 = s5; t2 = s3; t3 = s1;                                                         \
+    t0 = (uint32_t)(s7); t1 = (uint32_t)(s5); t2 = (uint32_t)(s3); t3 = (uint32_t)(s1);         \
     p3 = t0 + t2; p4 = t1 + t3; p1 = t0 + t3; p2 = t1 + t2;                                     \
     p5 = (p3 + p4) * J_F2F(1.175875602f);                                                       \
     t0 = t0 * J_F2F(0.298631336f); t1 = t1 * J_F2F(2.053119869f);                               \
@@ -628,10 +670,10 @@ void jpegIdct(uint8_t* out, int stride, const short* data)
         } else {
             J_IDCT_1D(d[0], d[8], d[16], d[24], d[32], d[40], d[48], d[56])
             x0 += 512; x1 += 512; x2 += 512; x3 += 512;
-            v[0] = (x0 + t3) >> 10; v[56] = (x0 - t3) >> 10;
-            v[8] = (x1 + t2) >> 10; v[48] = (x1 - t2) >> 10;
-            v[16] = (x2 + t1) >> 10; v[40] = (x2 - t1) >> 10;
-            v[24] = (x3 + t0) >> 10; v[32] = (x3 - t0) >> 10;
+            v[0] = J_S(x0 + t3) >> 10; v[56] = J_S(x0 - t3) >> 10;
+            v[8] = J_S(x1 + t2) >> 10; v[48] = J_S(x1 - t2) >> 10;
+            v[16] = J_S(x2 + t1) >> 10; v[40] = J_S(x2 - t1) >> 10;
+            v[24] = J_S(x3 + t0) >> 10; v[32] = J_S(x3 - t0) >> 10;
         }
     }
     v = val;
@@ -639,10 +681,10 @@ void jpegIdct(uint8_t* out, int stride, const short* data)
     for (int i = 0; i < 8; ++i, v += 8, o += stride) {
         J_IDCT_1D(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7])
         x0 += 65536 + (128 << 17); x1 += 65536 + (128 << 17); x2 += 65536 + (128 << 17); x3 += 65536 + (128 << 17);
-        o[0] = jclamp((x0 + t3) >> 17); o[7] = jclamp((x0 - t3) >> 17);
-        o[1] = jclamp((x1 + t2) >> 17); o[6] = jclamp((x1 - t2) >> 17);
-        o[2] = jclamp((x2 + t1) >> 17); o[5] = jclamp((x2 - t1) >> 17);
-        o[3] = jclamp((x3 + t0) >> 17); o[4] = jclamp((x3 - t0) >> 17);
+        o[0] = jclamp(J_S(x0 + t3) >> 17); o[7] = jclamp(J_S(x0 - t3) >> 17);
+        o[1] = jclamp(J_S(x1 + t2) >> 17); o[6] = jclamp(J_S(x1 - t2) >> 17);
+        o[2] = jclamp(J_S(x2 + t1) >> 17); o[5] = jclamp(J_S(x2 - t1) >> 17);
+        o[3] = jclamp(J_S(x3 + t0) >> 17); o[4] = jclamp(J_S(x3 - t0) >> 17);
     }
 }
 // the four row resamplers: out has w * hs samples
@@ -703,9 +745,9 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
     if (file.size() < 4 || file[0] != 0xff || file[1] != 0xd8) return false;
     JpegDec d{file.data(), file.size()};
     d.pos = 2;
-    uint16_t dequant[4][64];
+    uint16_t dequant[4][64] = {};
     JpegHuff hdc[4], hac[4];
-    bool haveDc[4] = {false, false, false, false}, haveAc[4] = {false, false, false, false};
+    bool haveDc[4] = {false, false, false, false}, haveAc[4] = {false, false, false, false}, haveQ[4] = {false, false, false, false};
     JpegComp comp[3];
     int ncomp = 0, hmax = 1, vmax = 1, restart = 0;
     bool sawFrame = false, progressive = false;
@@ -721,6 +763,7 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
                 int q = d.get8(), prec = q >> 4, t = q & 15;
                 if (t > 3 || prec > 1) return false;
                 for (int i = 0; i < 64; i++) dequant[t][kJpegZigzag[i]] = (uint16_t)(prec ? be16() : d.get8());
+                haveQ[t] = true;
                 L -= prec ? 129 : 65;
             }
             if (L != 0) return false;
@@ -762,6 +805,11 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
             for (int i = 0; i < ncomp; i++)
                 if (hmax % comp[i].h || vmax % comp[i].v) return false;
             const int mcuw = hmax * 8, mcuh = vmax * 8, mcux = (w + mcuw - 1) / mcuw, mcuy = (h + mcuh - 1) / mcuh;
+            // The frame's blocks against the bytes that are left to code them, before a sample is allocated: a block costs a
+            // sequential scan at least two bits (a DC code and an end-of-block code), a progressive file's DC scan at least one.
+            uint64_t blocks = 0;
+            for (int i = 0; i < ncomp; i++) blocks += (uint64_t)mcux * comp[i].h * mcuy * comp[i].v;
+            if (blocks * (progressive ? 1 : 2) > (uint64_t)(d.n - std::min(d.pos, d.n)) * 8) return false;
             for (int i = 0; i < ncomp; i++) {
                 comp[i].x = (w * comp[i].h + hmax - 1) / hmax;
                 comp[i].y = (h * comp[i].v + vmax - 1) / vmax;
@@ -796,7 +844,7 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
                     if (specStart == 0 ? (succHigh == 0 && !haveDc[comp[order[i]].hd]) : !haveAc[comp[order[i]].ha]) return false;
             } else {
                 for (int i = 0; i < ns; i++)
-                    if (!haveDc[comp[order[i]].hd] || !haveAc[comp[order[i]].ha]) return false;
+                    if (!haveDc[comp[order[i]].hd] || !haveAc[comp[order[i]].ha] || !haveQ[comp[order[i]].tq]) return false; // a table no DHT / DQT defined
             }
             d.codeBuffer = 0; d.codeBits = 0; d.marker = 0xff; d.nomore = false;
             for (int i = 0; i < ncomp; i++) comp[i].dcPred = 0;
@@ -810,8 +858,8 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
                         const int t = d.decode(hdc[c.hd]);
                         if (t < 0 || t > 15) return false;
                         const int diff = t ? d.extend(t) : 0;
-                        c.dcPred += diff;
-                        data[0] = (short)(c.dcPred * (1 << succLow));
+                        c.dcPred = (int)((uint32_t)c.dcPred + (uint32_t)diff); // (wraps, where a hostile scan would overflow)
+                        data[0] = (short)((uint32_t)c.dcPred * (1u << succLow));
                     } else if (d.bit()) {
                         data[0] = (short)(data[0] + (1 << succLow));
                     }
@@ -897,9 +945,9 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
                 int t = d.decode(hdc[c.hd]);
                 if (t < 0 || t > 15) return false;
                 int diff = t ? d.extend(t) : 0;
-                int dc = c.dcPred + diff;
+                int dc = (int)((uint32_t)c.dcPred + (uint32_t)diff); // (wraps, where a hostile scan would overflow)
                 c.dcPred = dc;
-                data[0] = (short)(dc * dequant[c.tq][0]);
+                data[0] = (short)((uint32_t)dc * dequant[c.tq][0]);
                 int k = 1;
                 do {
                     int rs = d.decode(hac[c.ha]);
@@ -972,6 +1020,7 @@ static bool decodeJpeg(FILE* f, int& w, int& h, int& depth, std::vector<uint8_t>
     if (progressive) // every scan is in: dequantise and transform (stb_image: stbi__jpeg_finish)
         for (int k = 0; k < ncomp; k++) {
             JpegComp& c = comp[k];
+            if (!haveQ[c.tq]) return false; // the component names a quantisation table that no DQT defined
             const int bw = (c.x + 7) >> 3, bh = (c.y + 7) >> 3;
             for (int j = 0; j < bh; j++)
                 for (int i = 0; i < bw; i++) {
@@ -1430,6 +1479,6 @@ Mesh SampleModels::getAtrium(uint32_t targetTris, uint32_t seed, bool alphaMaske
 }
 
 // the same inflate for the OpenEXR reader's ZIP blocks (prt_host.cpp)
-bool inflateZlibBytes(const std::vector<uint8_t>& in, std::vector<uint8_t>& out) { return inflateZlib(in, out); }
+bool inflateZlibBytes(const std::vector<uint8_t>& in, std::vector<uint8_t>& out, size_t limit) { return inflateZlib(in, out, limit); }
 
 } // namespace prt
