@@ -1,8 +1,8 @@
 /*
  * prt_hip_test.h -- row-level entry points of the TEST build of the library (libprt_hip_test.so = the product's sources
- * compiled with -DPRT_TEST_ENTRY_POINTS).  They exist so that the parity tests can drive single rows of SURVEY.md 8(a)
- * (leaf math, the four traversals, the camera packet, sin/cos/pow) on the device; libprt_hip.so, the product, exports
- * none of them and compiles none of their kernels.
+ * compiled with -DPRT_TEST_ENTRY_POINTS, plus the translation units only this build has: prt_amd/_build.py TEST_SOURCES).
+ * They exist so that the parity tests can drive single rows of SURVEY.md 8(a) (leaf math, the four traversals, the camera
+ * packet, sin/cos/pow) on the device; libprt_hip.so, the product, exports none of them and compiles none of their kernels.
  */
 #ifndef PRT_HIP_TEST_H
 #define PRT_HIP_TEST_H
@@ -105,6 +105,11 @@ int prt_hip_test_taps(prt_hip_ctx* ctx, uint32_t n, const uint32_t* records, int
  * the mesh), [6..9] duv01, duv02 and [10..15] dp01, dp02 as the bump record of the triangle holds them (0 in a scene without a bump
  * map), [16..18] sample_bump's normal, [19] taps counted (counting form).  counting, blocks: as above.  Synchronous. */
 int prt_hip_test_surface(prt_hip_ctx* ctx, uint32_t n, const uint32_t* records, int counting, uint32_t blocks, uint32_t* out);
+/* InfiniteAreaLight::sample (light.cpp:86-128) on the uploaded scene's own tables, texels and `first` constants (env_sample / cdf_find,
+ * prt_device.h).  u: n x 2 floats {u.x, u.y}, each in [0, 1) as the generator gives them (anything else is refused: EINVAL); out: n x 8
+ * words: [0..2] dir, [3..5] color, [6] taps counted (counting form: 1), [7] 0.  counting, blocks: as above.  ESTATE without a scene or
+ * when the scene has no environment map.  Synchronous. */
+int prt_hip_test_env_sample(prt_hip_ctx* ctx, uint32_t n, const float* u, uint32_t* out, int counting, uint32_t blocks);
 
 #ifdef __cplusplus
 }

@@ -278,7 +278,7 @@ TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos"
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
                 "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
                 "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile", "prt_hip_test_taps",
-                "prt_hip_test_surface", "prt_hip_test_deform_profile"]
+                "prt_hip_test_surface", "prt_hip_test_deform_profile", "prt_hip_test_env_sample"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -413,6 +413,7 @@ def _load(path, with_test_entry_points):
         L.prt_hip_test_occlusion_skipped.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.prt_hip_test_taps.argtypes = [vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp]
         L.prt_hip_test_surface.argtypes = [vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp]
+        L.prt_hip_test_env_sample.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.c_uint32]
     for n in ("prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
               "prt_host_mesh_atrium", "prt_host_scene_create"):
         getattr(L, n).restype = vp
@@ -1556,6 +1557,15 @@ class PathTracer:
         out = np.zeros((len(rec), 20), dtype=np.uint32)
         self._chk(self._L.prt_hip_test_surface(self._ctx, len(rec), rec.ctypes.data_as(C.c_void_p), int(counting), blocks,
                                                out.ctypes.data_as(C.c_void_p)), "prt_hip_test_surface")
+        return out
+
+    def test_env_sample(self, u, counting=False, blocks=0):
+        """prt_hip_test_env_sample: (n, 2) float32 draws {u.x, u.y} in [0, 1) -> (n, 8) uint32 words {dir[3], color[3], taps counted, 0}."""
+        self._need_row_level()
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        out = np.zeros((len(u), 8), dtype=np.uint32)
+        self._chk(self._L.prt_hip_test_env_sample(self._ctx, len(u), u.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), int(counting),
+                                                  blocks), "prt_hip_test_env_sample")
         return out
 
     def test_camera(self, x, y, state):

@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libprt_hip.so")
-TEST_LIB = os.path.join(LIB_DIR, "libprt_hip_test.so")  # same sources + -DPRT_TEST_ENTRY_POINTS (include/prt_hip_test.h)
+TEST_LIB = os.path.join(LIB_DIR, "libprt_hip_test.so")  # same sources + -DPRT_TEST_ENTRY_POINTS + TEST_SOURCES (include/prt_hip_test.h)
 
 SOURCES = [
     "prt_kernels.hip",
@@ -32,6 +32,9 @@ SOURCES = [
     "host/prt_models.cpp",
     "host/prt_host_capi.cpp",
 ]
+# translation units of the TEST build alone (row-level entry points the product never compiles): not product sources, so they are
+# compiled only with test_entry_points and are no part of source_sha16(), the stamp of what the product's measurements ran
+TEST_SOURCES = ["prt_rowtests_env.hip"]
 # every header under csrc/ (globbed: a new header can never be forgotten here) plus the interface headers: needs_build() and
 # source_sha16() both derive from these lists, so a stale library can neither be loaded silently nor stamp a measurement
 KERNEL_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
@@ -58,7 +61,7 @@ def needs_build(lib=LIB):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS + (TEST_SOURCES if lib == TEST_LIB else [])] + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -69,7 +72,7 @@ def build_library(force=False, verbose=False, test_entry_points=False):
     os.makedirs(LIB_DIR, exist_ok=True)
     tmp = f"{lib}.tmp.{os.getpid()}"  # concurrent builders (several ranks) never share a partial file
     cmd = [hipcc()] + FLAGS + [f'-DPRT_SOURCE_SHA16="{source_sha16()}"'] + (["-DPRT_TEST_ENTRY_POINTS"] if test_entry_points else []) + \
-        [os.path.join(CSRC, s) for s in SOURCES] + ["-o", tmp]
+        [os.path.join(CSRC, s) for s in SOURCES + (TEST_SOURCES if test_entry_points else [])] + ["-o", tmp]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -24,6 +24,9 @@ Outputs (all small, data only -- no reference source text):
   hostile_shade.npz    the reference-defined scenes of tests/prt_hostile_shade.py (hostile materials and lights on a 32x32 stage and in a
                        24x24 closed box): their arrays and light, and PathTracer::TraceBlock's image at 8 spp with its two ray counts
                        (oracle/_ref/ref_path_stats)
+  hostile_env.npz      the environment maps and draws of tests/prt_hostile_env.py; InfiniteAreaLight::create's two tables and
+                       InfiniteAreaLight::sample's (dir, color) for every draw the reference defines (oracle/_ref/ref_path envlight), and
+                       PathTracer::TraceBlock's 40x40 image at 8 spp of the Cornell box under every map no draw can run off
 
 radiance_c1_crop, gbuffer and scene_digests were rendered through ref_path (surface fetch and texture taps forwarded to the oracle);
 tests/test_hostile_taps_cpu.py renders them again through ref_path_real (the reference's own) and requires the committed bytes.
@@ -346,6 +349,30 @@ def dump_hostile_shade():
     assert os.path.getsize(path) <= 256 * 1024, os.path.getsize(path)
 
 
+def dump_hostile_env():
+    # tests/prt_hostile_env.py: hostile maps, and draws on and beside the entries of their tables.  Inputs are stored as generated.  A draw
+    # that runs off the vertical table makes the reference read past its horizontal one: those are not sent to it and stay zeros.
+    import prt_hostile_env as E
+    out = E.generate()
+    w, h, spp = E.RENDER
+    for name, env in E.maps():
+        u, undefined = out[f"{name}/u"], out[f"{name}/undefined"].astype(bool)
+        desc = E.render_desc(env)
+        vp, hp, d, c = T.ref_envlight(desc, u[~undefined])
+        ref_d, ref_c = np.zeros((len(u), 3), np.float32), np.zeros((len(u), 3), np.float32)
+        ref_d[~undefined], ref_c[~undefined] = d, c
+        out.update({f"{name}/ref_vertical": vp, f"{name}/ref_horizontal": hp, f"{name}/ref_dir": ref_d, f"{name}/ref_color": ref_c})
+        if E.always_defined(vp):
+            rgb, st = T.ref_render(desc, spp, (0, 0, w - 1, h - 1), seed=12345, stats=True)
+            out[f"{name}/ref_image"] = rgb
+            out[f"{name}/ref_rays"] = np.array([st["raysTraced"], st["occludedTraced"]], dtype=np.uint64)
+        print("hostile env", name, env.shape[1], "x", env.shape[0], len(u), "draws,", int(undefined.sum()), "undefined, render:", f"{name}/ref_image" in out)
+    path = os.path.join(HERE, "hostile_env.npz")
+    np.savez_compressed(path, **out)
+    print("hostile env:", sum(len(out[k]) for k in out if k.endswith("/u")), "draws;", os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < os.path.getsize(os.path.join(HERE, "c5_tile_rows.npz")), os.path.getsize(path)
+
+
 if __name__ == "__main__":
     subprocess.check_call(["make", "-s", "-C", T.ORACLE_DIR])
     dump_cornell()
@@ -360,3 +387,4 @@ if __name__ == "__main__":
     dump_hostile()
     dump_hostile_taps()
     dump_hostile_shade()
+    dump_hostile_env()
