@@ -1060,6 +1060,67 @@ int prt_hip_lens_accumulate(prt_hip_ctx* ctx, const prt_lens_desc* lens, uint32_
 int prt_hip_lens_render(prt_hip_ctx* ctx, const prt_lens_desc* lens, const prt_render_params* params, float* image /* 3*W*H */,
                         uint32_t flags, void* stream);
 
+/* ---- lightmap filter: an edge-avoiding a-trous filter over the baked values of an atlas, in atlas space.  A lightmap at a few
+ * hundred paths per texel is noisy, and it cannot go through the camera denoiser: its texels are no camera pixels, and neighbouring
+ * texels of different charts lie on unrelated surfaces.  Every texel carries exact guides, though: the world position and normal of
+ * its prt_bake_point.  prt_hip_atlas_filter sits between prt_hip_bake and prt_hip_atlas_resolve, neither of which changes: the n
+ * values of the bake in, n filtered values out, the points and their texel indices as guides.
+ *
+ * Definition.  All arithmetic is f32 with no FMA, every product is rounded before the sum that uses it, sums go left to right as
+ * written, divisions and sqrtf are correctly rounded and subnormals are kept: the rules of the denoised previews.
+ *   f(x):  y = 0.125f*x; r = 1.0f/((1.0f + y) + (0.5f*y)*y), then r = r*r three times (the previews' f).
+ *   lum(v) = (0.2126f*v[0] + 0.7152f*v[1]) + 0.0722f*v[2] of the FIRST three floats of a point's values (the previews' lum).
+ *   Texel t is (x, y) = (t % W, t / W).
+ *   Eligibility.  Point q is eligible iff texels[q] < W*H, points[q].set != 0xffffffff, the six floats of P and N are finite and
+ *     all `stride` floats of values[q] are finite.  map[t] is the smallest eligible q with texels[q] == t, or none.  Point q is
+ *     PLACED iff it is eligible and map[texels[q]] == q.  For a point that is not placed, out gets the bytes of values as they are,
+ *     and such a point is never a tap: a NaN texel is contained instead of spreading over +-62 texels in five iterations, and
+ *     duplicate indices are deterministic.  Everything below is for a placed q, and every r is placed.
+ *   nb(q, dx, dy) = map[(y+dy)*W + (x+dx)] if that texel is inside the image, else none.
+ *   Distance.  d2(q,r) = (ex*ex + ey*ey) + ez*ez with e = P_r - P_q.
+ *   Footprint.  f2_q = +inf; for (dx,dy) = (-1,0), (1,0), (0,-1), (0,1) in that order: if r = nb(q,dx,dy) exists, d2 > 0 and
+ *     d2 < f2_q, then f2_q = d2.  If nothing was taken, f2_q = 0.  It is the squared world size of a texel measured inside the
+ *     point's own chart, so sigmaPosition is in texel footprints and does not depend on the scene's scale.
+ *   Geometric weight for step s.  dn = (Nq.x*Nr.x + Nq.y*Nr.y) + Nq.z*Nr.z;  wn = dn > 0 ? dn : 0, then wn = wn*wn repeated
+ *     normalPowerLog2 times;  invP = 1.0f / ((sigP2 * (float)(s*s)) * f2_q) with sigP2 = sigmaPosition*sigmaPosition computed once
+ *     on the host (invP is per point and per launch, not per tap);  wp = d2 == 0 ? 1.0f : f(d2 * invP);  geo = wn * wp.
+ *   Variance V0_q.  Taps dy = -2..2 outer, dx = -2..2 inner at stride 1, r = nb(q,dx,dy); missing taps are skipped.  g = 1 for the
+ *     centre, else geo(q,r,1).  First loop: sw = sw + g, sl = sl + g*lum_r, both from +0;  m1 = sl/sw.  Second loop in the same
+ *     order: d = lum_r - m1; sv = sv + g*(d*d), from +0;  V0 = sv/sw.
+ *   Iteration i = 0 .. iterations-1 (s = 1 << i) on (C, V), starting from (values, V0):
+ *     a/b is the 3 x 3 stride-1 average of V over existing neighbours, weights (dx==0 ? 0.5f : 0.25f)*(dy==0 ? 0.5f : 0.25f),
+ *       row-major: a = a + wt*V_r, b = b + wt, both from +0, exactly as in the previews' iteration.
+ *     invDen = 1.0f / (sigmaLuminance*sqrtf(a/b) + 1e-6f).
+ *     Taps dy = -2..2 outer, dx = -2..2 inner at stride s, r = nb(q, dx*s, dy*s); missing taps are skipped.  With h = 0.375, 0.25,
+ *       0.0625 for |d| = 0, 1, 2: the centre has w = 0.375f*0.375f, other taps have
+ *       w = ((hy*hx)*geo(q,r,s)) * f(fabsf(lum(C_q) - lum(C_r)) * invDen).
+ *     sumW = sumW + w;  per float j: S_j = S_j + w*C_r[j];  sumV = sumV + (w*w)*V_r;  all from +0.
+ *     C'_q[j] = S_j/sumW,  V'_q = sumV/(sumW*sumW).
+ *   out = C after the last iteration.  The weights come from channel 0 (the first three floats) and apply to every channel.
+ *   IEEE fixes every finite word; which NaN an invalid operation gives is the processor's choice.
+ *
+ * W, H: 1 .. 8192.  n: 1 .. 2^26.  stride: 3*C floats per point, C 1 .. 16.  iterations 1 .. 5, normalPowerLog2 0 .. 7,
+ * sigmaLuminance and sigmaPosition finite and > 0, reserved 0.
+ * Pointers, flags and stream as for the three atlas calls: DEVICE pointers by default (points 16-byte aligned, everything else
+ * 4-byte aligned), asynchronous, ordered after the work queued on stream and before what is queued next; with PRT_HIP_QUERY_HOST
+ * every array is HOST memory, staged in the context's arena, and the call returns with the answer.  The params record is host
+ * memory, read before the call returns.
+ * Refused with PRT_HIP_EINVAL and a message, before anything is queued and with out untouched: a NULL pointer; a parameter out
+ * of range; a stride that is not a multiple of 3; reserved != 0; unknown flag bits; a misaligned device pointer; ranges of values
+ * and out that overlap.
+ * State: the call needs no scene and changes nothing in the context but scratch buffers of its own (the map, 16 bytes per point
+ * and two planes of stride + 1 floats per point, grown on demand); it is not a launch for prt_hip_get_stats.
+ * Not built: a per-sample variance output from the baker (the filter estimates variance spatially); seam stitching; albedo
+ * demodulation; filtering camera or lens images; ranks. ---- */
+typedef struct { uint32_t iterations;      /* 1 .. 5 */
+                 uint32_t normalPowerLog2; /* 0 .. 7 */
+                 float sigmaLuminance;     /* finite, > 0 */
+                 float sigmaPosition;      /* finite, > 0; in texel footprints */
+                 uint32_t reserved[4];     /* 0 */ } prt_atlas_filter_params;   /* 32 bytes */
+int prt_hip_atlas_filter(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t n, const uint32_t* texels,
+                         const prt_bake_point* points, const float* values /* n*stride */, uint32_t stride /* 3*C, C 1 .. 16 */,
+                         const prt_atlas_filter_params* params, float* out /* n*stride */, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

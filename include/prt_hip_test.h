@@ -37,6 +37,11 @@ int prt_hip_test_camera(prt_hip_ctx* ctx, uint32_t x, uint32_t y, uint32_t state
  * kernel, ms[1..5] = the iterations (0 beyond params->iterations) of the second run, ms[6] = the whole first run (no events
  * inside).  Synchronous. */
 int prt_hip_test_denoise_profile(prt_hip_ctx* ctx, const prt_denoise_params* params, float exposure, float* ms7);
+/* tools/query_bench.py --atlas-filter: prt_hip_atlas_filter on DEVICE arrays twice, timed with HIP events; ms[0] = the map's clear and
+ * the index kernel, ms[1] = the prepare kernel, ms[2..6] = the iterations (0 beyond params->iterations) of the second run, ms[7] = the
+ * whole first run (no events inside).  Synchronous; refuses what the call refuses. */
+int prt_hip_test_atlas_filter_profile(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t n, const uint32_t* texels, const prt_bake_point* points,
+                                      const float* values, uint32_t stride, const prt_atlas_filter_params* params, float* out, float* ms8);
 /* the yardstick of the same tool: one launch (after a warm-up launch) of a plain copy kernel in which every thread reads one element
  * of read16 16-byte planes and read12 12-byte planes and writes one of write16 16-byte and write12 12-byte planes of `pixels`
  * elements, in buffers of its own; *ms = its time */

@@ -222,6 +222,15 @@ class AtlasPointParams(C.Structure):
     _fields_ = [("bias", C.c_float), ("setTile", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class AtlasFilterParams(C.Structure):
+    """prt_atlas_filter_params (include/prt_hip.h "lightmap filter"): sigmaPosition is in texel footprints."""
+    _fields_ = [("iterations", C.c_uint32), ("normalPowerLog2", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaPosition", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, iterations=5, normalPowerLog2=5, sigmaLuminance=4.0, sigmaPosition=4.0):
+        super().__init__(iterations=iterations, normalPowerLog2=normalPowerLog2, sigmaLuminance=sigmaLuminance, sigmaPosition=sigmaPosition)
+
+
 # prt_lens_desc (include/prt_hip.h "lens renders")
 LENS_PINHOLE, LENS_ORTHO, LENS_EQUIRECT, LENS_FISHEYE = 0, 1, 2, 3
 LENS_CENTRE, LENS_ACCUMULATE = 1, 2
@@ -263,7 +272,7 @@ EXPORTS = [
     "prt_hip_query_nearest", "prt_hip_query_any", "prt_hip_query_surface", "prt_hip_query_get_counts",
     "prt_hip_query_radiance",
     "prt_hip_bake_rays", "prt_hip_bake_reduce", "prt_hip_bake",
-    "prt_hip_atlas_rasterize", "prt_hip_atlas_points", "prt_hip_atlas_resolve",
+    "prt_hip_atlas_rasterize", "prt_hip_atlas_points", "prt_hip_atlas_resolve", "prt_hip_atlas_filter",
     "prt_hip_lens_rays", "prt_hip_lens_accumulate", "prt_hip_lens_render",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
@@ -278,7 +287,7 @@ TEST_EXPORTS = ["prt_hip_trace_rays", "prt_hip_test_leaf", "prt_hip_test_sincos"
                 "prt_hip_test_denoise_profile", "prt_hip_test_copy_yardstick", "prt_hip_test_temporal_profile", "prt_hip_test_scene_arrays",
                 "prt_hip_test_refit_profile", "prt_hip_test_occlusion_skipped", "prt_hip_test_shading_arrays", "prt_hip_test_env_tables_host",
                 "prt_hip_test_edit_profile", "prt_hip_test_display_host", "prt_hip_test_display_profile", "prt_hip_test_taps",
-                "prt_hip_test_surface", "prt_hip_test_deform_profile", "prt_hip_test_env_sample"]
+                "prt_hip_test_surface", "prt_hip_test_deform_profile", "prt_hip_test_env_sample", "prt_hip_test_atlas_filter_profile"]
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libprt_hip_test.so")
 
 _lib = None
@@ -389,12 +398,14 @@ def _load(path, with_test_entry_points):
     L.prt_hip_atlas_rasterize.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtlasMesh), vp, vp, C.POINTER(AtlasCounts), C.c_uint32, vp]
     L.prt_hip_atlas_points.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AtlasPointParams), vp, C.c_uint32, vp]
     L.prt_hip_atlas_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.prt_hip_atlas_filter.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AtlasFilterParams), vp, C.c_uint32, vp]
     L.prt_hip_lens_rays.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     L.prt_hip_lens_accumulate.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.prt_hip_lens_render.argtypes = [vp, C.POINTER(LensDesc), C.POINTER(RenderParams), vp, C.c_uint32, vp]
     if with_test_entry_points:
         L.prt_hip_test_display_host.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(DisplayParams),
                                                 C.POINTER(DisplayState), vp]
+        L.prt_hip_test_atlas_filter_profile.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AtlasFilterParams), vp, vp]
         L.prt_hip_test_display_profile.argtypes = [vp, C.POINTER(DisplayParams), C.c_uint32, vp]
         L.prt_hip_test_shading_arrays.argtypes = [vp, C.POINTER(C.c_uint64)] + [vp] * 12
         L.prt_hip_test_env_tables_host.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
@@ -1417,13 +1428,41 @@ class PathTracer:
                   "prt_hip_atlas_resolve")
         return image, mask
 
-    def lightmap(self, uvs_per_mesh, W, H, dirs, weights, spp, seed=None, bias=1e-4, set_tile=1, gutter=2, exposure=None, max_depth=None):
+    def atlas_filter_async(self, W, H, n, d_texels, d_points, d_values, stride, d_out, params=None, stream=None):
+        """Queue prt_hip_atlas_filter on device arrays: d_texels (n uint32), d_points (n prt_bake_point, 16-byte aligned), d_values and
+        d_out (n * stride float32 each, stride = 3 * C, ranges that do not overlap) are device pointers (int)."""
+        p = AtlasFilterParams() if params is None else params
+        self._chk(self._L.prt_hip_atlas_filter(self._ctx, W, H, n, d_texels, d_points, d_values, stride, C.byref(p), d_out, 0, stream),
+                  "prt_hip_atlas_filter")
+
+    def atlas_filter(self, texels, points, values, W, H, params=None):
+        """The baked values (n, C, 3) or (n, 3 * C) of the points at their texels, filtered in atlas space by the edge-avoiding a-trous
+        filter of include/prt_hip.h "lightmap filter" (params: an AtlasFilterParams; None = its defaults), guided by the points'
+        positions and normals: float32 of values' shape.  A point that is not placed (a texel outside the atlas, set 0xffffffff, a
+        value, position or normal that is not finite, the later of two points of one texel) keeps its values and is no tap.  Needs
+        no scene."""
+        t = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+        pts = np.ascontiguousarray(points, dtype=BAKE_POINT_DTYPE).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.ndim < 1 or len(v) != len(t) or len(pts) != len(t):
+            raise PrtError(f"atlas_filter: {len(t)} texels for {len(pts)} points and values {v.shape}")
+        stride = int(v.size // max(len(t), 1))
+        out = np.zeros_like(v)
+        p = AtlasFilterParams() if params is None else params
+        self._chk(self._L.prt_hip_atlas_filter(self._ctx, W, H, len(t), t.ctypes.data_as(C.c_void_p), pts.ctypes.data_as(C.c_void_p),
+                                               v.ctypes.data_as(C.c_void_p), stride, C.byref(p), out.ctypes.data_as(C.c_void_p), QUERY_HOST, None),
+                  "prt_hip_atlas_filter")
+        return out
+
+    def lightmap(self, uvs_per_mesh, W, H, dirs, weights, spp, seed=None, bias=1e-4, set_tile=1, gutter=2, exposure=None, max_depth=None,
+                 filter=None):
         """A baked lightmap of the uploaded scene: rasterise the lightmap UVs (uvs_per_mesh as for atlas_rasterize), make a bake point
         per owned texel, bake() them under dirs / weights (as for bake(); a point's set is its texel's place in a set_tile x set_tile
         tile) and resolve with `gutter` dilation passes.  Returns (image (H, W, C, 3) float32, mask (H, W) uint8).  Every array between
         the four calls stays on the device: only the UVs and the table go up and only the image and the mask come down.  More than
         2^24 rays are baked in parts of whole points, part i0 under seed + i0 * K, as include/prt_hip.h "baking" says; sets
-        last_atlas_counts and last_stats (of the last part)."""
+        last_atlas_counts and last_stats (of the last part).  filter: an AtlasFilterParams to run atlas_filter_async on the baked values
+        before they are resolved (they stay on the device); None = no filter."""
         uvs = _atlas_uvs(uvs_per_mesh)
         d, w, table = make_bake_sets(dirs, weights)
         K, Cc = table.K, table.C
@@ -1446,6 +1485,9 @@ class PathTracer:
                 p.seed = (first_seed + i0 * K) & 0xffffffff
                 self._chk(self._L.prt_hip_bake(self._ctx, min(part, n - i0), d_points + BAKE_POINT_DTYPE.itemsize * i0, C.byref(table), C.byref(p),
                                                d_out + 12 * Cc * i0, 0, None), "prt_hip_bake")
+            if filter is not None:
+                d_baked, d_out = d_out, dev.alloc(12 * Cc * n)
+                self.atlas_filter_async(W, H, n, d_texels, d_points, d_baked, 3 * Cc, d_out, params=filter)
             d_image, d_mask = dev.alloc(image.nbytes), dev.alloc(mask.nbytes)
             self.atlas_resolve_async(W, H, n, d_texels, d_out, 3 * Cc, gutter, d_image, d_mask)
             self.last_stats = self.stats()  # synchronises the context's stream; raises on stack overflow

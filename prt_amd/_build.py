@@ -25,6 +25,7 @@ SOURCES = [
     "prt_query.hip",
     "prt_bake.hip",
     "prt_atlas.hip",
+    "prt_atlas_filter.hip",
     "prt_lens.hip",
     "prt_rowtests.hip",
     "host/prt_host.cpp",

@@ -194,6 +194,10 @@ struct prt_hip_ctx {
     DevBuf<unsigned long long> atCounts;    // {pairs, rejected, degenerate, n} of the last rasterise and
     HostBuf<unsigned long long> atCountsHost; // their pinned host copy
     DevBuf<uint8_t> atScratchMask;     // the mask the passes of a prt_hip_atlas_resolve work on when its caller wants none
+    // lightmap filter (prt_atlas_filter.hip): allocated on first use
+    DevBuf<uint32_t> afMap;            // per texel the placed point, and
+    DevBuf<float4> afRec;              // per point {bits(placed), f2, V0, 0}
+    DevBuf<float> afPlane[2];          // ping-pong between the launches: n*stride floats of C, then n of V
 };
 
 

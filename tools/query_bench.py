@@ -38,6 +38,15 @@ route it replaces: rays in numpy, query_radiance on host arrays in chunks the ca
 Also the accumulate kernel alone over 2^24 radiances at K = 1, 8 and 64: the layout of its reads is the one thing K changes.
 
     python tools/query_bench.py --lens [--reps 3] [--out F]
+
+--atlas-filter: prt_hip_atlas_filter (include/prt_hip.h "lightmap filter") on the atlases of --atlas (one grid cell per triangle, 1024 x
+1024 and 4096 x 4096), K = 16 directions, 8 spp, C = 1, five iterations at the default parameters: per kernel (HIP events inside the TEST
+build's prt_hip_test_atlas_filter_profile) and the whole call on device arrays, against the bake launches of the same points, per point
+and iteration, and against ONE run of the numpy restatement tests/prt_atlas_filter_ref.py; and the RMSE of the 8-spp values, unfiltered
+and filtered, against a bake of the same points at --ref-spp (1024 x 1024 only, and on the Cornell box in a 256 x 256 atlas, whose 36
+triangles make charts of some 500 texels where the stand-in's are a few texels each).
+
+    python tools/query_bench.py --atlas-filter [--reps 5] [--ref-spp 2040] [--out F]
 """
 import argparse
 import ctypes as C
@@ -293,6 +302,91 @@ def atlas(args):
     emit(out, args.out)
 
 
+def atlas_filter(args):
+    """Per workload: rasterize, points and an 8-spp bake on device arrays; then (a) the filter's whole call (host clock around
+    atlas_filter_async up to the synchronisation, and the event pair of the profile entry point), its kernels by events, (b) kernelMsSum
+    of the bake launches, (c) the numpy restatement once on host arrays -- whose output must equal the product's byte for byte."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import prt_atlas_filter_ref as AF
+    spp, depth, seed, K, bias = 8, 8, 12345, 16, 1e-4
+    d, w = prt_amd.bake_cosine_set(K, np.random.default_rng(K))
+    params = prt_amd.AtlasFilterParams()
+    out = {"K": K, "spp": spp, "max_depth": depth, "reps": args.reps, "ref_spp": args.ref_spp, "source_sha16": prt_amd.loaded_source_sha16(),
+           "params": {k: getattr(params, k) for k in ("iterations", "normalPowerLog2", "sigmaLuminance", "sigmaPosition")}, "atlas_filter": {}}
+    workloads = [("c3_sponza_standin", lambda: prt_amd.setup_atrium_standin(64, 64, tris=262000, seed=1)[0], 1024, args.ref_spp),
+                 ("c3_sponza_standin", None, 4096, 0),
+                 ("cornell_box", lambda: prt_amd.setup_cornell_box(64, 64)[0], 256, args.ref_spp)]
+    t = None
+    for name, make, W, ref_spp in workloads:
+        if make is not None:
+            if t is not None:
+                t.close()
+            scene = make()
+            t = prt_amd.PathTracer(max_depth=depth, seed=seed, test_entry_points=True)
+            t.upload_scene(scene)
+            out["device"], out["compute_units"] = t.device_info()[0], t.device_info()[1]
+            prims = [len(m["indices"]) for m in scene.arrays()["meshes"]]
+            total = sum(prims)
+            G = int(np.ceil(np.sqrt(total)))
+            cell = np.arange(total)
+            corner = np.array([(0.1, 0.1), (0.9, 0.1), (0.1, 0.9)])
+            uv_all = ((np.stack([cell % G, cell // G], axis=1)[:, None, :] + corner[None]) / G).astype(np.float32)
+            uvs = {m: uv_all[sum(prims[:m]):sum(prims[:m + 1])] for m in range(len(prims))}
+        H = W
+        sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
+        with prt_amd.DeviceArrays() as dev:
+            d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
+            d_texels, d_hits = dev.alloc(4 * W * H), dev.alloc(prt_amd.HIT_DTYPE.itemsize * W * H)
+            n = t.atlas_rasterize_device(W, H, d_uv, dict(enumerate(prims)), d_texels, d_hits)["n"]
+            d_points, d_values, d_out, d_ref = (dev.alloc(s_ * n) for s_ in (32, 12, 12, 12))
+            t.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias)
+            table = prt_amd.BakeSets(K=K, C=1, nSets=1, reserved=0, dirs=dev.upload(d), weights=dev.upload(w))
+
+            def bake_into(dst, samples):
+                ms, part = 0.0, max(1, (1 << 24) // K)
+                for i0 in range(0, n, part):
+                    t.bake_async(min(part, n - i0), d_points + 32 * i0, table, dst + 12 * i0, samples, seed=(seed + i0 * K) & 0xffffffff)
+                    ms += t.stats()["kernelMs"]
+                return ms
+            times = {k: [] for k in ("bake_kernels", "filter_wall", "filter_events", "index", "prepare", "iter0", "iter1", "iter2", "iter3", "iter4")}
+            ms = (C.c_float * 8)()
+            for rep in range(1 + args.reps):
+                bake_ms = bake_into(d_values, spp)
+                sync()
+                t0 = time.perf_counter()
+                t.atlas_filter_async(W, H, n, d_texels, d_points, d_values, 3, d_out, params)
+                sync()
+                wall = (time.perf_counter() - t0) * 1e3
+                t._chk(t._L.prt_hip_test_atlas_filter_profile(t._ctx, W, H, n, d_texels, d_points, d_values, 3, C.byref(params), d_out, ms),
+                       "prt_hip_test_atlas_filter_profile")
+                if rep >= 1:
+                    for k, v in zip(("index", "prepare", "iter0", "iter1", "iter2", "iter3", "iter4", "filter_events"), ms):
+                        times[k].append(float(v))
+                    times["bake_kernels"].append(bake_ms)
+                    times["filter_wall"].append(wall)
+            texels, points = fetch(dev, d_texels, n, np.uint32), fetch(dev, d_points, n, prt_amd.BAKE_POINT_DTYPE)
+            values, got = fetch(dev, d_values, 3 * n, np.float32).reshape(n, 3), fetch(dev, d_out, 3 * n, np.float32).reshape(n, 3)
+            t0 = time.perf_counter()
+            want = AF.filter(texels, points, values, W, H)
+            numpy_ms = (time.perf_counter() - t0) * 1e3
+            is_placed, _ = AF.placed(texels, points.view(AF.POINT_DTYPE), values, W, H)
+            med = {k: float(np.median(v)) for k, v in times.items()}
+            iters = [med[f"iter{i}"] for i in range(5)]
+            row = {"n": int(n), "placed": int(is_placed.sum()), "ms": {k: spread(v) for k, v in times.items()},
+                   "filter_share_of_bake_kernels": med["filter_events"] / med["bake_kernels"],
+                   "ns_per_point_and_iteration": [1e6 * v / n for v in iters], "numpy_restatement_ms": numpy_ms,
+                   "numpy_over_filter": numpy_ms / med["filter_wall"], "equals_the_restatement": got.tobytes() == want.tobytes(),
+                   "changed_fraction": float((got != values).any(axis=1).mean())}
+            if ref_spp:
+                row["reference_bake_kernels_ms"] = bake_into(d_ref, ref_spp)
+                ref = fetch(dev, d_ref, 3 * n, np.float32).reshape(n, 3).astype(np.float64)
+                rmse = lambda a: float(np.sqrt(np.mean((a.astype(np.float64) - ref) ** 2)))  # noqa: E731  (every point is a texel of mask 1)
+                row.update(rmse_unfiltered=rmse(values), rmse_filtered=rmse(got), rmse_ratio=rmse(values) / rmse(got), reference_mean=float(ref.mean()))
+            out["atlas_filter"][f"{name} {W}x{H}"] = row
+    t.close()
+    emit(out, args.out)
+
+
 def lens_host_band(lens, y0, y1, rng):
     """What a caller wrote in numpy for rows [y0, y1): jittered film coordinates, the model's direction, the
     thin lens's disc, in double precision with a generator of its own: (org, dir) of (y1 - y0) * W * K rays."""
@@ -432,6 +526,8 @@ def main():
     ap.add_argument("--bake", action="store_true")
     ap.add_argument("--atlas", action="store_true")
     ap.add_argument("--lens", action="store_true")
+    ap.add_argument("--atlas-filter", action="store_true")
+    ap.add_argument("--ref-spp", type=int, default=2040)
     args = ap.parse_args()
     prt_amd.build()
     if args.radiance:
@@ -440,6 +536,8 @@ def main():
         return bake(args)
     if args.atlas:
         return atlas(args)
+    if args.atlas_filter:
+        return atlas_filter(args)
     if args.lens:
         return lens(args)
     W, H = (int(v) for v in args.size.split("x"))
