@@ -1121,6 +1121,59 @@ int prt_hip_atlas_filter(prt_hip_ctx* ctx, uint32_t W, uint32_t H, uint32_t n, c
                          const prt_bake_point* points, const float* values /* n*stride */, uint32_t stride /* 3*C, C 1 .. 16 */,
                          const prt_atlas_filter_params* params, float* out /* n*stride */, uint32_t flags, void* stream);
 
+/* ---- visibility baking: points and direction sets in, the summed weights of the directions that escape out.  How much of a
+ * hemisphere, or of the sky, a point can see is what a lightmapper asks for most often: ambient occlusion maps, sky-visibility masks
+ * for a separately lit sky, bent normals and SH9 visibility probes are all one computation -- fire a direction set from each point and
+ * sum the weights of the directions that escape.  The points and the table are those of prt_hip_bake; the rays are built in
+ * registers from the point and its direction set and never exist in memory, and the answer per ray is one byte.
+ *
+ * Definition.  No new arithmetic: every piece is one defined above.
+ * Ray r = i*K + k has the org and dir of prt_hip_bake_rays for the same points and table (the frame of path_tracer.cpp:147-153 with
+ *     N as given, org = P + bias*N; the identity frame for N = 0); its tMax is vis->maxDistance, in units of the ray's dir.
+ * Occlusion byte.  occ[r] is the answer of prt_hip_query_any for that ray, with all of that call's rules: alpha tests apply, and a
+ *     NaN in org, dir or tMax gives "not occluded" (0) without a walk.  A point with set >= nSets (0xffffffff included) is never
+ *     traced: its K bytes are 0.
+ * Reduce, one wavefront per point, in the order of prt_hip_bake_reduce, fixed by K alone:
+ *     1. for lane l = 0..63, for channel c: a_l = +0
+ *     2. for k = l, l+64, l+128, ... < K: if occ[r] == 0 then a_l = a_l + weights[(s*K + k)*C + c]
+ *     3. for step = 32, 16, 8, 4, 2, 1, for l < step: a_l = a_l + a_(l+step)
+ *     4. out[i*C + c] = a_0; under PRT_HIP_VIS_TRIPLE out[(i*C + c)*3 + h] = a_0 for h = 0, 1, 2
+ *     Any non-zero byte counts as occluded.  An occluded direction's weight is not read into the sum, so a NaN weight there
+ *     changes nothing; a NaN weight of a direction that escapes gives a NaN in that point's channel and in no other point.
+ *     A point with set >= nSets writes +0 to all its floats.
+ * Recipes: cosine-weighted directions with weights 1/K give ambient occlusion (1 = open) under a finite maxDistance and sky
+ * visibility under +inf; C = 3 with weights d_k/K, d_k in the local frame, gives the bent normal; uniform directions with
+ * weights 4pi/K * Y_c(d_k) and N = 0 give an SH9 visibility probe.
+ *
+ * prt_hip_bake_visibility runs the trace and the reduce in order on the context's stream.  The bytes go to `occluded`, or, when it is
+ * NULL, to a buffer the context owns, grown on demand: 1 byte per ray against the 44 bytes per ray of prt_hip_bake.
+ * prt_hip_bake_visibility_reduce is the second half on the caller's bytes: a baker who kept them sums them again under other
+ * weights without tracing again.  It reads no directions (sets->dirs may be NULL there) and needs no scene.
+ * Limits: K 1 .. 4096, C 1 .. 16, nSets 1 .. 1024, n >= 1, n*K <= 2^30, the limit of the ray queries.  The 2^24 cap of prt_hip_bake
+ * does not apply: no probe launch is involved.
+ * Pointers, flags and stream as for the baker: DEVICE pointers by default, sets->dirs and sets->weights included (points 16-byte
+ * aligned, floats 4-byte aligned, bytes as they come); asynchronous, ordered after the work queued on stream and before what is
+ * queued next.  With PRT_HIP_QUERY_HOST every array is HOST memory, staged in the context's arena, and the call returns with the
+ * answer.  The prt_bake_sets and prt_visibility_params records are host memory, read before the call returns.
+ * Refused with PRT_HIP_EINVAL and a message, before anything is queued and with the outputs untouched: a NULL pointer other than
+ * `occluded` in prt_hip_bake_visibility; a table out of range; maxDistance NaN or <= 0; unknown bits in vis->flags or flags;
+ * reserved != 0; a misaligned device pointer.  prt_hip_bake_visibility without a scene is PRT_HIP_ESTATE.
+ * State: the call reads the scene and changes nothing else in the context, apart from a scratch buffer of its own: the camera, the
+ * accumulator, the moments, the guides, the history, the display state and the framebuffer are untouched.
+ * Statistics: the trace is a launch like prt_hip_query_any's -- raysTraced = occludedTraced = n*K, and a stack overflow is reported
+ * there; the reduce is not a launch for prt_hip_get_stats.
+ * Not built: distance falloff (needs nearest hits); back-face and validity counts; ranks; a per-ray tMax. ---- */
+#define PRT_HIP_VIS_TRIPLE 1u  /* vis->flags: every channel is written three times, the (n, C, 3) layout of prt_hip_bake */
+typedef struct { float maxDistance;   /* > 0 or +inf, in units of the ray's dir */
+                 uint32_t flags;      /* PRT_HIP_VIS_TRIPLE; other bits refused */
+                 uint32_t reserved[2]; /* 0 */ } prt_visibility_params;   /* 16 bytes, host memory, read before the call returns */
+int prt_hip_bake_visibility(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets,
+                            const prt_visibility_params* vis, float* out /* n*C, or 3*n*C under TRIPLE */,
+                            uint8_t* occluded /* n*K, may be NULL */, uint32_t flags, void* stream);
+int prt_hip_bake_visibility_reduce(prt_hip_ctx* ctx, uint32_t n, const prt_bake_point* points, const prt_bake_sets* sets,
+                                   const prt_visibility_params* vis, const uint8_t* occluded /* n*K */, float* out,
+                                   uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

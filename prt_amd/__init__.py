@@ -231,6 +231,18 @@ class AtlasFilterParams(C.Structure):
         super().__init__(iterations=iterations, normalPowerLog2=normalPowerLog2, sigmaLuminance=sigmaLuminance, sigmaPosition=sigmaPosition)
 
 
+# prt_visibility_params (include/prt_hip.h "visibility baking")
+VIS_TRIPLE = 1  # PRT_HIP_VIS_TRIPLE
+
+
+class VisibilityParams(C.Structure):
+    """prt_visibility_params: maxDistance > 0 or +inf, in units of the ray's dir; flags VIS_TRIPLE or 0."""
+    _fields_ = [("maxDistance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    def __init__(self, maxDistance=float("inf"), flags=0):
+        super().__init__(maxDistance=maxDistance, flags=flags)
+
+
 # prt_lens_desc (include/prt_hip.h "lens renders")
 LENS_PINHOLE, LENS_ORTHO, LENS_EQUIRECT, LENS_FISHEYE = 0, 1, 2, 3
 LENS_CENTRE, LENS_ACCUMULATE = 1, 2
@@ -273,6 +285,7 @@ EXPORTS = [
     "prt_hip_query_radiance",
     "prt_hip_bake_rays", "prt_hip_bake_reduce", "prt_hip_bake",
     "prt_hip_atlas_rasterize", "prt_hip_atlas_points", "prt_hip_atlas_resolve", "prt_hip_atlas_filter",
+    "prt_hip_bake_visibility", "prt_hip_bake_visibility_reduce",
     "prt_hip_lens_rays", "prt_hip_lens_accumulate", "prt_hip_lens_render",
     "prt_host_scene_set_material", "prt_host_scene_set_texture_texels",
     "prt_host_mesh_cornell", "prt_host_mesh_load_obj", "prt_host_mesh_from_arrays", "prt_host_mesh_displaced_sphere",
@@ -399,6 +412,8 @@ def _load(path, with_test_entry_points):
     L.prt_hip_atlas_points.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(AtlasPointParams), vp, C.c_uint32, vp]
     L.prt_hip_atlas_resolve.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.prt_hip_atlas_filter.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AtlasFilterParams), vp, C.c_uint32, vp]
+    L.prt_hip_bake_visibility.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), C.POINTER(VisibilityParams), vp, vp, C.c_uint32, vp]
+    L.prt_hip_bake_visibility_reduce.argtypes = [vp, C.c_uint32, vp, C.POINTER(BakeSets), C.POINTER(VisibilityParams), vp, vp, C.c_uint32, vp]
     L.prt_hip_lens_rays.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]
     L.prt_hip_lens_accumulate.argtypes = [vp, C.POINTER(LensDesc), C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp]
     L.prt_hip_lens_render.argtypes = [vp, C.POINTER(LensDesc), C.POINTER(RenderParams), vp, C.c_uint32, vp]
@@ -1490,6 +1505,88 @@ class PathTracer:
                 self.atlas_filter_async(W, H, n, d_texels, d_points, d_baked, 3 * Cc, d_out, params=filter)
             d_image, d_mask = dev.alloc(image.nbytes), dev.alloc(mask.nbytes)
             self.atlas_resolve_async(W, H, n, d_texels, d_out, 3 * Cc, gutter, d_image, d_mask)
+            self.last_stats = self.stats()  # synchronises the context's stream; raises on stack overflow
+            dev.download(image, d_image)
+            dev.download(mask, d_mask)
+        return image, mask
+
+    # ---- visibility baking (include/prt_hip.h "visibility baking"): points and direction sets in, the weights of the open directions out
+    def bake_visibility_async(self, n, d_points, table, d_out, max_distance=float("inf"), triple=False, d_occluded=None, stream=None):
+        """Queue prt_hip_bake_visibility on device arrays: d_points (n prt_bake_point, 16-byte aligned), d_out (n * C float32, or
+        3 * n * C with triple) and d_occluded (n * K bytes, or None: the context keeps them) are device pointers (int), table a
+        BakeSets whose dirs and weights are device pointers."""
+        v = VisibilityParams(max_distance, VIS_TRIPLE if triple else 0)
+        self._chk(self._L.prt_hip_bake_visibility(self._ctx, n, d_points, C.byref(table), C.byref(v), d_out, d_occluded, 0, stream),
+                  "prt_hip_bake_visibility")
+
+    def bake_visibility(self, points, normals, dirs, weights, max_distance=float("inf"), bias=1e-4, sets=None, triple=False, return_bytes=False):
+        """The summed weights of the directions that escape, per point: points, normals, dirs, weights, bias and sets as for bake(),
+        max_distance the length of every ray in units of its direction.  Returns (n, C) float32, or (n, C, 3) with triple (every
+        value three times, the layout of bake()): out[i, c] = sum of weights[set, k, c] over the k whose ray i*K + k meets nothing,
+        rays, any-hit rules and sum as include/prt_hip.h "visibility baking" defines them; with return_bytes (out, occluded (n, K)
+        uint8).  Sets last_stats (raysTraced = n * K).  Needs a scene and no camera."""
+        pts = make_bake_points(points, normals, bias, sets)
+        d, w, table = make_bake_sets(dirs, weights)
+        out = np.zeros((len(pts), table.C, 3) if triple else (len(pts), table.C), dtype=np.float32)
+        occ = np.zeros((len(pts), table.K), dtype=np.uint8) if return_bytes else None
+        v = VisibilityParams(max_distance, VIS_TRIPLE if triple else 0)
+        self._chk(self._L.prt_hip_bake_visibility(self._ctx, len(pts), pts.ctypes.data_as(C.c_void_p), C.byref(table), C.byref(v),
+                                                  out.ctypes.data_as(C.c_void_p), None if occ is None else occ.ctypes.data_as(C.c_void_p),
+                                                  QUERY_HOST, None), "prt_hip_bake_visibility")
+        self.last_stats = self.stats()  # raises on stack overflow
+        return (out, occ) if return_bytes else out
+
+    def bake_visibility_reduce(self, weights, occluded, sets=None, triple=False):
+        """(n, C) float32, or (n, C, 3) with triple: bake_visibility()'s sums of occlusion bytes the caller kept -- occluded (n, K) uint8,
+        weights (K,), (K, C) or (nSets, K, C) -- under other weights, without tracing again (prt_hip_bake_visibility_reduce; needs no
+        scene)."""
+        b = np.ascontiguousarray(occluded, dtype=np.uint8)
+        if b.ndim != 2:
+            raise PrtError(f"bake_visibility_reduce: occluded must be (n, K), not {b.shape}")
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if w.ndim < 3:
+            w = w.reshape(1, b.shape[1], -1)
+        _, w, table = make_bake_sets(None, w)
+        if table.K != b.shape[1]:
+            raise PrtError(f"bake_visibility_reduce: weights for {table.K} directions, bytes for {b.shape[1]}")
+        pts = make_bake_points(np.zeros((len(b), 3), np.float32), np.zeros((len(b), 3), np.float32), 0.0, sets)
+        out = np.zeros((len(b), table.C, 3) if triple else (len(b), table.C), dtype=np.float32)
+        v = VisibilityParams(flags=VIS_TRIPLE if triple else 0)
+        self._chk(self._L.prt_hip_bake_visibility_reduce(self._ctx, len(b), pts.ctypes.data_as(C.c_void_p), C.byref(table), C.byref(v),
+                                                         b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), QUERY_HOST, None),
+                  "prt_hip_bake_visibility_reduce")
+        return out
+
+    def lightmap_visibility(self, uvs_per_mesh, W, H, dirs, weights, max_distance=float("inf"), bias=1e-4, set_tile=1, gutter=2, filter=None):
+        """A visibility lightmap of the uploaded scene (ambient occlusion, sky visibility, bent normals): lightmap() with
+        bake_visibility in the place of bake().  Returns (image (H, W, C) float32, or (H, W, C, 3) when `filter` (an
+        AtlasFilterParams) is given, mask (H, W) uint8): the bake then writes every value three times, because atlas_filter wants a
+        stride that is a multiple of 3.  Every array between the calls stays on the device; sets last_atlas_counts and last_stats."""
+        uvs = _atlas_uvs(uvs_per_mesh)
+        d, w, table = make_bake_sets(dirs, weights)
+        triple = filter is not None
+        stride = table.C * (3 if triple else 1)
+        image, mask = np.zeros((H, W, table.C, 3) if triple else (H, W, table.C), dtype=np.float32), np.zeros((H, W), dtype=np.uint8)
+        with DeviceArrays(self._device) as dev:
+            d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
+            d_texels, d_hits = dev.alloc(4 * W * H), dev.alloc(HIT_DTYPE.itemsize * W * H)
+            counts = self.atlas_rasterize_device(W, H, d_uv, {m: len(uv) for m, uv in uvs.items()}, d_texels, d_hits)
+            self.last_atlas_counts = counts
+            n = counts["n"]
+            if n == 0:
+                return image, mask
+            d_points, d_out = dev.alloc(BAKE_POINT_DTYPE.itemsize * n), dev.alloc(4 * stride * n)
+            self.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias, set_tile=set_tile)
+            table.dirs, table.weights = dev.upload(d), dev.upload(w)
+            part = max(1, (1 << 30) // table.K)  # whole points, n*K <= 2^30 per call
+            for i0 in range(0, n, part):
+                self.bake_visibility_async(min(part, n - i0), d_points + BAKE_POINT_DTYPE.itemsize * i0, table, d_out + 4 * stride * i0,
+                                           max_distance=max_distance, triple=triple)
+            if triple:
+                d_baked, d_out = d_out, dev.alloc(4 * stride * n)
+                self.atlas_filter_async(W, H, n, d_texels, d_points, d_baked, stride, d_out, params=filter)
+            d_image, d_mask = dev.alloc(image.nbytes), dev.alloc(mask.nbytes)
+            self.atlas_resolve_async(W, H, n, d_texels, d_out, stride, gutter, d_image, d_mask)
             self.last_stats = self.stats()  # synchronises the context's stream; raises on stack overflow
             dev.download(image, d_image)
             dev.download(mask, d_mask)

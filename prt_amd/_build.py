@@ -26,6 +26,7 @@ SOURCES = [
     "prt_bake.hip",
     "prt_atlas.hip",
     "prt_atlas_filter.hip",
+    "prt_visibility.hip",
     "prt_lens.hip",
     "prt_rowtests.hip",
     "host/prt_host.cpp",

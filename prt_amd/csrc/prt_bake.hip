@@ -1,7 +1,7 @@
 // prt_bake.hip -- baking (include/prt_hip.h "baking"): points and direction sets in, weighted radiance sums out.  What every baker
 // wrote around prt_hip_query_radiance on the host -- a tangent frame per point, K local directions rotated into it, n*K rays up,
 // n*K radiances down, a weighted mean -- as two kernels around the frame kernel's probe launch (prt_frame_probe, as it stands):
-//     bake_rays_kernel    one lane per ray: the frame of diffuse_dir (prt_lanes.h) through the cross3 and normalize3 of prt_device.h
+//     bake_rays_kernel    one lane per ray: bake_ray of prt_bake_ray.h, which the visibility baker (prt_visibility.hip) traces too
 //     bake_reduce_kernel  one wave per point: per lane a strided sum over k, then a shuffle tree, in an order fixed by K alone
 // The rays and the per-ray radiances of prt_hip_bake live in the context (bkRays, bkRad) and never leave the device.  In a translation
 // unit of its own, as prt_query.hip is, so that the code objects of every other kernel do not move.
@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <string>
 
+#include "prt_bake_ray.h"
 #include "prt_internal.h"
 
 namespace {
@@ -39,24 +40,8 @@ __global__ __launch_bounds__(256) void bake_rays_kernel(BakeRaysArgs A)
     const uint32_t total = A.n * A.K; // <= 2^24: checked by the host
     for (uint32_t r = blockIdx.x * 256u + threadIdx.x; r < total; r += gridDim.x * 256u) {
         const uint32_t i = r / A.K, k = r - i * A.K;
-        const float4 a = gld4(A.points + 2 * (size_t)i), b = gld4(A.points + 2 * (size_t)i + 1);
-        const uint32_t set = asu(b.w);
-        Vec3 org = mk3(0.0f, 0.0f, 0.0f), dir = mk3(0.0f, 0.0f, 0.0f);
-        if (set < A.nSets) { // a set outside the table is never followed
-            const float* dp = A.dirs + ((size_t)set * A.K + k) * 3;
-            const Vec3 d = mk3(dp[0], dp[1], dp[2]);
-            const Vec3 P = mk3(a.x, a.y, a.z), N = mk3(b.x, b.y, b.z);
-            if (N.x == 0.0f && N.y == 0.0f && N.z == 0.0f) { // (either zero) the identity frame
-                org = P;
-                dir = d;
-            } else { // path_tracer.cpp:147-153, N as given
-                const Vec3 u = (fabsf(N.x) > 0.1f) ? mk3(0.0f, 1.0f, 0.0f) : mk3(1.0f, 0.0f, 0.0f);
-                const Vec3 T = normalize3(cross3(N, u));
-                const Vec3 B = normalize3(cross3(T, N));
-                dir = add3(add3(scale3(d.x, B), scale3(d.y, T)), scale3(d.z, N));
-                org = add3(P, scale3(a.w, N));
-            }
-        }
+        Vec3 org, dir;
+        bake_ray(A.points, A.dirs, A.K, A.nSets, i, k, org, dir); // (a set outside the table: org = dir = 0)
         gst4(A.rays + 2 * (size_t)r, make_float4(org.x, org.y, org.z, 0.0f));
         gst4(A.rays + 2 * (size_t)r + 1, make_float4(dir.x, dir.y, dir.z, asf(0u)));
     }

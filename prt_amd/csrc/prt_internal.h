@@ -198,6 +198,8 @@ struct prt_hip_ctx {
     DevBuf<uint32_t> afMap;            // per texel the placed point, and
     DevBuf<float4> afRec;              // per point {bits(placed), f2, V0, 0}
     DevBuf<float> afPlane[2];          // ping-pong between the launches: n*stride floats of C, then n of V
+    // visibility baking (prt_visibility.hip): allocated on first use
+    DevBuf<uint8_t> vsOcc;             // prt_hip_bake_visibility without a caller's array: the n*K occlusion bytes
 };
 
 

@@ -47,6 +47,16 @@ and filtered, against a bake of the same points at --ref-spp (1024 x 1024 only, 
 triangles make charts of some 500 texels where the stand-in's are a few texels each).
 
     python tools/query_bench.py --atlas-filter [--reps 5] [--ref-spp 2040] [--out F]
+
+--visibility: prt_hip_bake_visibility (include/prt_hip.h "visibility baking") on the 1024 x 1024 atlas of --atlas (one grid cell per
+triangle), one cosine set of K = 64 directions with weights 1/K, maxDistance +inf and a tenth of the scene's radius.  (a) the call
+end to end on device arrays (host clock between synchronisations), its trace kernel (event pair, prt_hip_get_stats) and its reduce
+alone (prt_hip_bake_visibility_reduce on the bytes, host clock); (b) prt_hip_query_any alone on the same rays, materialised once in
+parts of 2^24 rays by prt_hip_bake_rays with tMax written on the host: the traversal floor, on code the visibility baker does not
+touch; (c) the bake_rays kernel for the same rays (host clock); (d) ONE run of the host-array route every caller had: bake_rays,
+numpy tMax, query_any, numpy sum.  The bytes of (a), (b) and (d) must be equal.
+
+    python tools/query_bench.py --visibility [--reps 5] [--out F]
 """
 import argparse
 import ctypes as C
@@ -504,6 +514,112 @@ def lens(args):
     emit(out, args.out)
 
 
+def visibility(args):
+    """See the module's docstring.  Every timed call follows two warm-up calls; the sides are interleaved per repetition."""
+    K, bias, W = 64, 1e-4, 1024
+    scene, _, _ = prt_amd.setup_atrium_standin(64, 64, tris=262000, seed=1)
+    t = prt_amd.PathTracer(max_depth=8)
+    t.upload_scene(scene)
+    L, ctx = t._L, t._ctx
+    box = np.array(scene.bbox(), np.float64).reshape(2, 3)
+    radius = 0.5 * float(np.linalg.norm(box[1] - box[0]))
+    meshes = scene.arrays()["meshes"]
+    prims = [len(m["indices"]) for m in meshes]
+    total = sum(prims)
+    G = int(np.ceil(np.sqrt(total)))
+    cell = np.arange(total)
+    corner = np.array([(0.1, 0.1), (0.9, 0.1), (0.1, 0.9)])
+    uv_all = ((np.stack([cell % G, cell // G], axis=1)[:, None, :] + corner[None]) / G).astype(np.float32)
+    uvs = {m: uv_all[sum(prims[:m]):sum(prims[:m + 1])] for m in range(len(prims))}
+    d, _ = prt_amd.bake_cosine_set(K, np.random.default_rng(K))
+    w = np.full((K, 1), 1.0 / K, np.float32)
+    out = {"workload": "c3_sponza_standin", "layout": f"{total} triangles, one cell each of a {G} x {G} grid, {W} x {W} atlas", "K": K,
+           "reps": args.reps, "device": t.device_info()[0], "compute_units": t.device_info()[1], "scene_radius": radius,
+           "source_sha16": prt_amd.loaded_source_sha16(), "visibility": {}}
+    sync = lambda: t.stats()  # noqa: E731  (prt_hip_get_stats synchronises the context's stream)
+
+    def wall(call):
+        sync()
+        t0 = time.perf_counter()
+        call()
+        st = sync()
+        return (time.perf_counter() - t0) * 1e3, st["kernelMs"]
+
+    with prt_amd.DeviceArrays() as dev:
+        d_uv = {m: dev.upload(uv) for m, uv in uvs.items()}
+        d_texels, d_hits = dev.alloc(4 * W * W), dev.alloc(prt_amd.HIT_DTYPE.itemsize * W * W)
+        n = t.atlas_rasterize_device(W, W, d_uv, dict(enumerate(prims)), d_texels, d_hits)["n"]
+        d_points = dev.alloc(32 * n)
+        t.atlas_points_async(n, W, d_texels, d_hits, d_points, bias=bias)
+        sync()
+        pts = np.zeros(n, prt_amd.BAKE_POINT_DTYPE)
+        dev.download(pts, d_points)
+        table = prt_amd.BakeSets(K=K, C=1, nSets=1, reserved=0, dirs=dev.upload(d), weights=dev.upload(w))
+        d_out, d_occ = dev.alloc(4 * n), dev.alloc(n * K)
+        part = (1 << 24) // K
+        d_rays = dev.alloc(32 * part * K)
+        out["points"], out["rays"] = n, n * K
+        for label, md in (("inf", float("inf")), ("radius_over_10", radius / 10.0)):
+            v = prt_amd.VisibilityParams(md, 0)
+            times = {k: [] for k in ("a_bake_visibility_wall", "a_vis_trace_kernel", "a_vis_reduce_wall", "b_query_any_kernels", "c_bake_rays_wall")}
+            fused = lambda: t.bake_visibility_async(n, d_points, table, d_out, max_distance=md, d_occluded=d_occ)  # noqa: E731
+            reduce_ = lambda: t._chk(L.prt_hip_bake_visibility_reduce(ctx, n, d_points, C.byref(table), C.byref(v), d_occ, d_out, 0, None), "reduce")  # noqa: E731
+            for rep in range(2 + args.reps):
+                a_wall, a_kernel = wall(fused)
+                r_wall, _ = wall(reduce_)
+                if rep >= 2:
+                    times["a_bake_visibility_wall"].append(a_wall)
+                    times["a_vis_trace_kernel"].append(a_kernel)
+                    times["a_vis_reduce_wall"].append(r_wall)
+            occ = np.zeros(n * K, np.uint8)
+            dev.download(occ, d_occ)
+            ao = np.zeros(n, np.float32)
+            dev.download(ao, d_out)
+            # (b) and (c): the rays of every part once, tMax written on the host, then the repetitions of query_any on them
+            b_sum, c_sum, equal = np.zeros(2 + args.reps), np.zeros(2 + args.reps), True
+            for i0 in range(0, n, part):
+                m = min(part, n - i0)
+                rays_call = lambda: t._chk(L.prt_hip_bake_rays(ctx, m, d_points + 32 * i0, C.byref(table), d_rays, 0, None), "bake_rays")  # noqa: E731
+                for rep in range(2 + args.reps):
+                    c_sum[rep] += wall(rays_call)[0]
+                rays = np.zeros(m * K, prt_amd.RAY_DTYPE)
+                dev.download(rays, d_rays)
+                rays["tMax"] = np.float32(md)
+                dev.upload(rays, d_rays)
+                d_any = dev.alloc(m * K)
+                for rep in range(2 + args.reps):
+                    b_sum[rep] += wall(lambda: t.query_any_async(m * K, d_rays, d_any))[1]
+                got = np.zeros(m * K, np.uint8)
+                dev.download(got, d_any)
+                equal = equal and got.tobytes() == occ[i0 * K:(i0 + m) * K].tobytes()
+            times["b_query_any_kernels"], times["c_bake_rays_wall"] = list(b_sum[2:]), list(c_sum[2:])
+            med = {k: float(np.median(x)) for k, x in times.items()}
+            res = {"maxDistance": md, "ms": {k: spread(x) for k, x in times.items()}, "occluded_fraction": float(occ.mean()),
+                   "mean_visibility": float(ao.mean()), "bytes_equal_query_any": equal,
+                   "vis_trace_over_b_plus_c": med["a_vis_trace_kernel"] / (med["b_query_any_kernels"] + med["c_bake_rays_wall"]),
+                   "vis_trace_minus_b_plus_c_ms": med["a_vis_trace_kernel"] - (med["b_query_any_kernels"] + med["c_bake_rays_wall"]),
+                   "spread_of_b_ms": float(np.max(times["b_query_any_kernels"]) - np.min(times["b_query_any_kernels"])),
+                   "mrays_per_s": {"a_end_to_end": n * K / med["a_bake_visibility_wall"] / 1e3, "a_vis_trace_kernel": n * K / med["a_vis_trace_kernel"] / 1e3,
+                                   "b_query_any": n * K / med["b_query_any_kernels"] / 1e3}}
+            if label == "inf":  # (d) the host-array route, once
+                t0 = time.perf_counter()
+                sums, same = [], True
+                for i0 in range(0, n, part):
+                    p = pts[i0:i0 + part]
+                    r = t.bake_rays(p["P"], p["N"], d, bias=p["bias"])
+                    r["tMax"] = np.float32(md)
+                    o = t.query_any(r["org"], r["dir"], r["tMax"])
+                    same = same and o.tobytes() == occ[i0 * K:(i0 + len(p)) * K].tobytes()
+                    sums.append(((o.reshape(len(p), K) == 0) * w[:, 0]).sum(axis=1, dtype=np.float32))
+                res["d_host_route_ms"] = (time.perf_counter() - t0) * 1e3
+                res["d_bytes_equal"] = same
+                res["d_largest_difference_of_the_numpy_sum"] = float(np.abs(np.concatenate(sums) - ao).max())
+                res["d_over_a"] = res["d_host_route_ms"] / med["a_bake_visibility_wall"]
+            out["visibility"][label] = res
+    t.close()
+    emit(out, args.out)
+
+
 def host_rays(pts, d):
     """What a baker wrote in numpy: a tangent frame per point, the K directions rotated into it, the origin tiled."""
     N = pts["N"].astype(np.float64)
@@ -527,6 +643,7 @@ def main():
     ap.add_argument("--atlas", action="store_true")
     ap.add_argument("--lens", action="store_true")
     ap.add_argument("--atlas-filter", action="store_true")
+    ap.add_argument("--visibility", action="store_true")
     ap.add_argument("--ref-spp", type=int, default=2040)
     args = ap.parse_args()
     prt_amd.build()
@@ -540,6 +657,8 @@ def main():
         return atlas_filter(args)
     if args.lens:
         return lens(args)
+    if args.visibility:
+        return visibility(args)
     W, H = (int(v) for v in args.size.split("x"))
     scene, camera, _ = prt_amd.setup_atrium_standin(W, H, tris=262000, seed=1)
     t = prt_amd.PathTracer(max_depth=8, test_entry_points=True)
